@@ -1,19 +1,26 @@
 #!/usr/bin/env python3
 """bench.py -- ML-KEM-768 encapsulations/sec on MI355X (BASELINE.json's metric), plus every other BASELINE config.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--mode M] [--extras contract|all|none] [--no-cpu-baseline] [--no-pmc] [--sample-parity]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--mode M] [--dump-outputs DIR]
+                    [--full [--extras contract|all|none] [--no-cpu-baseline] [--no-pmc] [--sample-parity]]
 
-OUTPUT: the LAST stdout line is the bench contract's JSON line and nothing but the contract (contract_line(): metric / value / config /
-parity / roofline / cpu_baseline / value_host_abi / strong + one figure and verdict per other BASELINE config; < 6 KB, strict JSON,
-tests/test_bench_line.py).  The full record -- every config's kernel times, rooflines, parity details, probes, notes and definitions --
-is written to bench_extras.json next to this file (--extras-file), which the line names as "extras".
+A plain run does what the headline needs and nothing else: it sets up the inputs, settles the clocks (>= 2 s of the same step,
+untimed), runs W warm-up steps, times exactly K steps and prints the JSON line (metric / value / unit / n_gpus / steps / warmup /
+ms_per_step = milliseconds per timed step / higher_is_better / dtype / config).  --dump-outputs DIR then also writes what the last timed
+step computed to DIR/<name>.npy (dump()); the inputs are seeded, so two builds run with the same arguments can be compared output for output.
+
+--full adds everything else, as below: oracle parity, strong scaling, the other BASELINE configs (--extras), rooflines with live PMC
+passes, the CPU baseline.  Its LAST stdout line is the bench contract's JSON line and nothing but the contract (contract_line(): metric /
+value / config / parity / roofline / cpu_baseline / value_host_abi / strong + one figure and verdict per other BASELINE config; < 6 KB,
+strict JSON, tests/test_bench_line.py).  The full record -- every config's kernel times, rooflines, parity details, probes, notes and
+definitions -- is written to bench_extras.json next to this file (--extras-file), which the line names as "extras".
 
 A "step" is one pass of the hot path over one batch of synthetic inputs that are already resident in HBM when the timed
 region starts.  The headline (default --mode encaps) is BASELINE.json configs[1]: "ML-KEM-768 Encapsulate batch=2^20 on
 1xMI355X", distinct-key form of SURVEY.md section 8(d): ek_i are valid keys from seeded keygen
 (d||z = SHAKE256("circl-hip/keygen" || LE64(i))[:64]), ONE KEY PER ITEM (2^20 keys made by the GPU keygen, untimed);
-m_i = SHAKE256("circl-hip/m" || LE64(i))[:32] are all distinct.  Every ciphertext and shared secret of the batch is compared with the
-oracle (--sample-parity: a 2^16 sample instead).  `configs.pooled` keeps the figure of earlier rounds (a pool of 2^16 keys cycled 16x).
+m_i = SHAKE256("circl-hip/m" || LE64(i))[:32] are all distinct.  With --full, every ciphertext and shared secret of the batch is compared
+with the oracle (--sample-parity: a 2^16 sample instead).  `configs.pooled` keeps the figure of earlier rounds (a pool of 2^16 keys cycled 16x).
 
 The full record carries, under "configs", a measured figure (own HIP-event kernel times, own roofline against SURVEY
 8(d)'s algorithmic bytes, own sampled oracle parity) for every other BASELINE config on this rank's GPU:
@@ -23,13 +30,14 @@ The full record carries, under "configs", a measured figure (own HIP-event kerne
     config4       ML-DSA-65 Verify 2^18, DISTINCT keys (GPU keygen + GPU deterministic signing), >= 1 % corrupted signatures
     config5       ML-KEM-1024 Encapsulate + ML-DSA-87 Verify submitted concurrently on two streams (per-GPU share 2^16 + 2^16)
     host_abi      the host-buffer C ABI end to end (H2D + kernels + D2H), page-locked and ordinary pageable buffers
-and with --extras all (opt-in: the default run is the contract's):
+and with --full --extras all (opt-in: the default --full run is the contract's):
     pooled               the figure of rounds 1-4 (keys from a pool of 2^16)
     shared_key / keyed   one key for the batch / a table of 1000 keys (the reference's parsed-key cache)
     hybrid               X-Wing and X25519MLKEM768 on resident arrays, 2^18 per GPU
     small_batches / concurrent_callers   per-call cost of small batches; T one-item callers through the coalescer and R reactors on the asynchronous form (tools/bin/concurrent_bench)
 
---mode config3 | config4 | config5 | host makes that workload the headline (metric / value / ms_per_step) instead.
+--mode config3 | config4 | config5 | host makes that workload the headline (metric / value / ms_per_step) instead (host: K calls of
+the host-buffer C ABI on pageable memory after W untimed ones).
 
 N > 1: one rank per GPU.  `python bench.py --gpus N` without a launcher re-executes itself as N ranks under torch.distributed.run
 (127.0.0.1, a free port); under a launcher it refuses to run (exit code 3) unless WORLD_SIZE == N and the box has N GPUs.  Every rank
@@ -38,7 +46,7 @@ owns its own batch of --batch items (`value`: weak scaling, per-GPU work fixed a
 host-pointer C ABI (PCIe-inclusive).  There is no data-path collective (the only collectives are the timing barrier and the
 reductions of timings: RCCL); rank 0 prints ONE JSON line with whole-job aggregates and per-rank rates.
 
-`cpu_baseline` (rank 0, N = 1): the same workload on the host cores this process may use -- `value` = oracle/vec, a batch-vectorised
+`cpu_baseline` (--full, rank 0, N = 1): the same workload on the host cores this process may use -- `value` = oracle/vec, a batch-vectorised
 port (16 / 32 items per AVX2 / AVX-512 vector, Keccak on 4 / 8 states; bytes checked against the scalar oracle in the run), with the
 scalar oracle (the restatement of CIRCL's generic Go the parity legs use) as `scalar_oracle`; CIRCL's own AVX2 path needs a Go toolchain
 (`cpu_baseline_reference` runs it when $CIRCL_REFERENCE and `go` exist).
@@ -132,6 +140,30 @@ def roofline(kernel_name, ops_per_step, bytes_per_op, kernel_ms_per_step, note=N
     if note:
         r["note"] = note
     return r
+
+
+DUMP_BYTES = 48 << 20   # --dump-outputs: at most this much over all ranks (the bound is 64 MB)
+
+
+def dump(dirpath, arrays, rank, world):
+    """--dump-outputs: writes `arrays` (the outputs of the timed path's last step, all with the same number of rows n) to
+    DIR/<name>.npy as float32, which holds bytes and flags exactly.  When all n rows would exceed this rank's share of DUMP_BYTES,
+    a sample of rows fixed by n and the seed is written instead; DIR/sample_rows.npy (float64) holds the row numbers either way.
+    With N > 1 every rank writes its own batch, with the suffix _rank<r>."""
+    if not dirpath:
+        return
+    n = {int(a.shape[0]) for a in arrays.values()}
+    assert len(n) == 1, {k: tuple(a.shape) for k, a in arrays.items()}
+    n = n.pop()
+    row_bytes = 8 + 4 * sum(int(np.prod(a.shape[1:])) for a in arrays.values())
+    cap = max(1, DUMP_BYTES // world // row_bytes)
+    rows = np.arange(n) if n <= cap else np.sort(np.random.default_rng(20261016).choice(n, size=cap, replace=False))
+    sfx = "_rank%d" % rank if world > 1 else ""
+    os.makedirs(dirpath, exist_ok=True)
+    for name, a in arrays.items():
+        a = a[torch.from_numpy(rows).to(a.device)].cpu().numpy() if torch.is_tensor(a) else a[rows]
+        np.save(os.path.join(dirpath, name + sfx + ".npy"), a.astype(np.float32))
+    np.save(os.path.join(dirpath, "sample_rows" + sfx + ".npy"), rows.astype(np.float64))
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -373,17 +405,21 @@ def concurrent_callers(seconds=1.0):
     return out
 
 
-def host_abi(work, dev_index, runs=3):
+def host_abi(work, dev_index, runs=3, warmup=1, full=True):
     """End to end through circl_hip_mlkem_encaps (host pointers): H2D + kernels + D2H, first with buffers from
-    circl_hip_alloc_host (page-locked), then with ordinary pageable numpy memory, as a Go caller's []byte would be."""
+    circl_hip_alloc_host (page-locked), then with ordinary pageable numpy memory, as a Go caller's []byte would be.  Each leg:
+    `warmup` untimed calls, then `runs` timed ones.  full=False: the pageable leg alone, without the comparison with the
+    device-resident run.  Returns the record and the pageable leg's outputs {ct, ss, status} of its last call."""
     from circl_amd import _native as nat
     L = nat.lib()
     B, EK, CT = work.B, work.eng.EK, work.eng.CT
     ek_np, m_np = work.ek.cpu().numpy(), work.m.cpu().numpy()
-    ct_ref = work.eng.ct.cpu().numpy()
+    ct_ref = work.eng.ct.cpu().numpy() if full else None
     out = {}
 
     def run(p_ek, p_m, p_ct, p_ss, p_st):
+        for _ in range(warmup):  # staging slots, streams
+            assert L.circl_hip_mlkem_encaps(work.param, p_ek, p_m, p_ct, p_ss, p_st, B, dev_index) == 0
         best, tot = 1e9, 0.0
         for _ in range(runs):
             t = time.perf_counter()
@@ -391,29 +427,28 @@ def host_abi(work, dev_index, runs=3):
             dt = time.perf_counter() - t
             assert rc == 0, rc
             best, tot = min(best, dt), tot + dt
-        return best, tot / runs
+        return best, tot
 
-    def figure(best, mean):
+    def figure(best, tot):
         h2d, d2h = B * (EK + 32), B * (CT + 32 + 1)
-        return {"value": B / best, "unit": "encaps/s", "best_s": best, "mean_s": mean, "h2d_GBps": h2d / best / 1e9, "d2h_GBps": d2h / best / 1e9,
-                "pcie_gen5_x16_GBps_per_direction": 64.0}
+        return {"value": B / best, "unit": "encaps/s", "best_s": best, "mean_s": tot / runs, "total_s": tot, "runs": runs,
+                "h2d_GBps": h2d / best / 1e9, "d2h_GBps": d2h / best / 1e9, "pcie_gen5_x16_GBps_per_direction": 64.0}
 
     # page-locked
-    bufs = []
+    if full:
+        bufs = []
 
-    def pinned(nbytes):
-        p = L.circl_hip_alloc_host(nbytes)
-        assert p
-        bufs.append(p)
-        return p, np.ctypeslib.as_array((C.c_uint8 * nbytes).from_address(p))
-    p_ek, a_ek = pinned(B * EK); p_m, a_m = pinned(B * 32); p_ct, a_ct = pinned(B * CT); p_ss, a_ss = pinned(B * 32); p_st, a_st = pinned(B)
-    a_ek[:] = ek_np.reshape(-1); a_m[:] = m_np.reshape(-1)
-    L.circl_hip_mlkem_encaps(work.param, p_ek, p_m, p_ct, p_ss, p_st, B, dev_index)  # warm: staging slots, streams
-    best, mean = run(p_ek, p_m, p_ct, p_ss, p_st)
-    out["pinned"] = figure(best, mean)
-    out["pinned"]["all_ct_equal_device_resident_run"] = bool((a_ct.reshape(B, CT) == ct_ref).all())
-    for p in bufs:
-        L.circl_hip_free_host(p)
+        def pinned(nbytes):
+            p = L.circl_hip_alloc_host(nbytes)
+            assert p
+            bufs.append(p)
+            return p, np.ctypeslib.as_array((C.c_uint8 * nbytes).from_address(p))
+        p_ek, a_ek = pinned(B * EK); p_m, a_m = pinned(B * 32); p_ct, a_ct = pinned(B * CT); p_ss, a_ss = pinned(B * 32); p_st, a_st = pinned(B)
+        a_ek[:] = ek_np.reshape(-1); a_m[:] = m_np.reshape(-1)
+        out["pinned"] = figure(*run(p_ek, p_m, p_ct, p_ss, p_st))
+        out["pinned"]["all_ct_equal_device_resident_run"] = bool((a_ct.reshape(B, CT) == ct_ref).all())
+        for p in bufs:
+            L.circl_hip_free_host(p)
     # pageable, deliberately byte-misaligned sub-slices (a Go sub-slice is 1-byte aligned)
     def pageable(nbytes, off):
         raw = np.zeros(nbytes + 64, np.uint8)  # touched: no first-touch page faults inside the timed call
@@ -422,14 +457,13 @@ def host_abi(work, dev_index, runs=3):
     g_ct, g_ss, g_st = pageable(B * CT, 5), pageable(B * 32, 7), pageable(B, 9)
     g_ek[:] = ek_np.reshape(-1); g_m[:] = m_np.reshape(-1)
     ptr = lambda a: a.ctypes.data_as(C.c_void_p)
-    L.circl_hip_mlkem_encaps(work.param, ptr(g_ek), ptr(g_m), ptr(g_ct), ptr(g_ss), ptr(g_st), B, dev_index)
-    best, mean = run(ptr(g_ek), ptr(g_m), ptr(g_ct), ptr(g_ss), ptr(g_st))
-    out["pageable"] = figure(best, mean)
+    out["pageable"] = figure(*run(ptr(g_ek), ptr(g_m), ptr(g_ct), ptr(g_ss), ptr(g_st)))
     out["pageable"]["misaligned_by_bytes"] = [1, 3, 5, 7, 9]
-    out["pageable"]["all_ct_equal_device_resident_run"] = bool((g_ct.reshape(B, CT) == ct_ref).all() and not g_st.any())
+    if full:
+        out["pageable"]["all_ct_equal_device_resident_run"] = bool((g_ct.reshape(B, CT) == ct_ref).all() and not g_st.any())
     out["note"] = ("circl_hip_mlkem_encaps with host pointers, %d items, one device: staged through the library's page-locked slots by its "
-                   "host thread pool (pageable) or DMA-ed directly (page-locked); PCIe-inclusive, never the headline value" % B)
-    return out
+                   "host thread pool (pageable) or DMA-ed directly (page-locked); PCIe-inclusive" % B)
+    return out, {"ciphertext": g_ct.reshape(B, CT), "shared_secret": g_ss.reshape(B, 32), "status": g_st}
 
 
 def cpu_baseline(work, budget_s=10.0):
@@ -947,7 +981,16 @@ def main():
     ap.add_argument("--no-pmc", action="store_true", help="skip the live rocprofv3 --pmc passes (traffic / valu then come from profiles/*.json if they match this build)")
     ap.add_argument("--sample-parity", action="store_true", help="compare 2^16-item samples with the oracle instead of whole batches (headline: 2^20, config 4: 2^18)")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: oracle parity, strong scaling, the --extras legs, rooflines, PMC passes, cpu_baseline, "
+                         "the --extras-file record (off: set up, warm up, time the steps, print the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (float32; a fixed seeded "
+                         "sample of rows when the whole would exceed 64 MB, its row numbers in DIR/sample_rows.npy)")
     args = ap.parse_args()
+    if args.steps < 1:
+        print("bench.py: --steps must be >= 1", file=sys.stderr)
+        sys.exit(3)
 
     share = bool(os.environ.get("CIRCL_BENCH_SHARE_GPU"))  # test aid: several ranks on one device (then with CIRCL_DIST_BACKEND=gloo; RCCL wants one GPU per rank)
     if args.gpus < 1:
@@ -977,8 +1020,9 @@ def main():
     B = args.batch
     if args.no_extras:
         args.extras = "none"
-    extras = args.extras != "none"      # the BASELINE configs' legs (3, 4, 5), strong, host ABI
-    more = args.extras == "all"         # opt-in legs: pooled keys, shared key / key table, hybrids, small batches, concurrent callers
+    full = args.full
+    extras = full and args.extras != "none"   # the BASELINE configs' legs (3, 4, 5), host ABI
+    more = full and args.extras == "all"      # opt-in legs: pooled keys, shared key / key table, hybrids, small batches, concurrent callers
 
     if args.pmc_child:  # a few launches of the dominant kernel of every BASELINE config for the counter passes, nothing else
         w = KemWork(768, B, 0, dev, shake_inputs=False)
@@ -1015,7 +1059,7 @@ def main():
         kem.encaps()
     torch.cuda.synchronize()
     est = (time.perf_counter() - t) / 10
-    sus_steps = max(args.steps, int(2.2 / est) + 1)
+    sus_steps = int(2.2 / est) + 1   # not scaled with --steps: a plain run's time outside its timed steps stays bounded
     ranks.barrier()
     t = time.perf_counter()
     for _ in range(sus_steps):
@@ -1038,21 +1082,27 @@ def main():
         elapsed, kern = timer_kem.run(step, args.steps, args.warmup)
         value, elapsed = parallel.whole_job_rate(ranks, ops * args.steps, elapsed)
         headline = {"elapsed": elapsed, "value": value, "kern": kern}
+        arrays = {"ciphertext": kem.eng.ct, "shared_secret": kem.eng.ss, "status": kem.eng.status}
+        if args.mode == "config3":
+            arrays.update(shared_secret_decaps=kem.ss_dec, status_decaps=kem.st_dec)
+        dump(args.dump_outputs, arrays, rank, world)
     enc_kern = headline["kern"] if args.mode == "encaps" else None
     if enc_kern is None and extras:  # the encaps figures are wanted in any mode
         el, enc_kern = timer_kem.run(kem.encaps, max(5, min(args.steps, 20)), 2)
         v, el = parallel.whole_job_rate(ranks, B * max(5, min(args.steps, 20)), el)
         out_cfg["encaps"] = {"value": v, "unit": "encaps/s", "ms_per_step": el / max(5, min(args.steps, 20)) * 1e3}
-    status_sum = int(kem.eng.status.sum().item())
-    full = not args.sample_parity
-    parity_enc = kem.parity_encaps((None if full else 1 << 16) if rank == 0 else 1 << 12)
-    parity_fail = ranks.sum(0 if parity_enc["bit_exact_vs_oracle"] else 1)
-    parity_enc["ranks_failing"] = int(parity_fail)
+    status_sum = int(kem.eng.status.sum().item()) if full else None
+    whole = not args.sample_parity
+    parity_enc = None
+    if full:
+        parity_enc = kem.parity_encaps((None if whole else 1 << 16) if rank == 0 else 1 << 12)
+        parity_fail = ranks.sum(0 if parity_enc["bit_exact_vs_oracle"] else 1)
+        parity_enc["ranks_failing"] = int(parity_fail)
     per_rank = {"encaps_per_s": ranks.gather(B * args.steps / headline["elapsed"]) if args.mode == "encaps" else None}
 
     # ---- strong scaling: the metric read literally -- ONE batch of B items, n/G contiguous items per rank ----
     strong = None
-    if args.mode == "encaps":
+    if full and args.mode == "encaps":
         lo, hi = parallel.shard_bounds(B, world, rank)
         if world == 1:
             strong = {"value": headline["value"], "ms_per_step": headline["elapsed"] / args.steps * 1e3, "items_per_rank": [B],
@@ -1085,7 +1135,7 @@ def main():
         torch.cuda.empty_cache()
 
     # ---- decaps + config 3 (second half of Encaps + Decaps on the same items) ----
-    if extras or args.mode == "config3":
+    if extras or (full and args.mode == "config3"):
         ksteps = args.steps if args.mode == "config3" else 10
         if args.mode != "config3":
             el, kd = timer_kem.run(kem.decaps, ksteps, 2)
@@ -1169,9 +1219,14 @@ def main():
     # ---- host-buffer ABI, end to end ----
     host = None
     if (extras and args.mode == "encaps") or args.mode == "host":
-        host = host_abi(kem, local)
+        hm = args.mode == "host"   # the headline: exactly --steps timed calls after --warmup untimed ones
+        host, host_arrays = host_abi(kem, local, runs=args.steps if hm else 3, warmup=args.warmup if hm else 1, full=full)
+        if hm:
+            dump(args.dump_outputs, host_arrays, rank, world)
+        del host_arrays
         host["pageable"]["whole_job_value"] = ranks.sum(host["pageable"]["value"])
-        host["pinned"]["whole_job_value"] = ranks.sum(host["pinned"]["value"])
+        if full:
+            host["pinned"]["whole_job_value"] = ranks.sum(host["pinned"]["value"])
         host["per_rank_pageable_per_s"] = ranks.gather(host["pageable"]["value"])
         out_cfg["host_abi"] = host
 
@@ -1183,7 +1238,11 @@ def main():
         k4 = args.steps if args.mode == "config4" else 5
         el, kv = tm.run(d65.verify, k4, args.warmup if args.mode == "config4" else 1)
         v4, el = parallel.whole_job_rate(ranks, n4 * k4, el)
-        par4 = d65.parity((None if full else 1 << 16) if rank == 0 else 1 << 10, 1 << 11)
+        if args.mode == "config4":
+            headline = {"elapsed": el, "value": v4, "kern": kv}
+            dump(args.dump_outputs, {"verified": d65.eng.ok}, rank, world)
+    if full and (extras or args.mode == "config4"):
+        par4 = d65.parity((None if whole else 1 << 16) if rank == 0 else 1 << 10, 1 << 11)
         par4["ranks_failing"] = int(ranks.sum(0 if (par4["bit_exact_vs_oracle"] and par4["all_items_as_expected"]) else 1))
         cfg4 = {"value": v4, "unit": "verifications/s", "ms_per_step": el / k4 * 1e3, "n_per_gpu": n4, "steps": k4,
                 "workload": "ML-DSA-65 Verify, %d items per GPU, DISTINCT keys (GPU keygen + GPU deterministic signing at %.2e sig/s incl. setup), "
@@ -1191,9 +1250,8 @@ def main():
                 "kernel_ms_per_step": {k: v["ms_per_step"] for k, v in kv.items()},
                 "roofline": roofline("mldsa_verify_kernel<65>", n4, BYTES["mldsa65_verify"], kv["mldsa_verify"]["ms_per_step"]),
                 "parity": par4, "per_rank_per_s": ranks.gather(n4 * k4 / el)}
-        if args.mode == "config4":
-            headline = {"elapsed": el, "value": v4, "kern": kv}
         out_cfg["config4"] = cfg4
+    if extras or args.mode == "config4":
         del d65
         torch.cuda.empty_cache()
 
@@ -1213,6 +1271,11 @@ def main():
         k5 = args.steps if args.mode == "config5" else 10
         el, km = tm.run(mixed, k5, args.warmup if args.mode == "config5" else 2)
         v5, el = parallel.whole_job_rate(ranks, 2 * n5 * k5, el)
+        if args.mode == "config5":
+            headline = {"elapsed": el, "value": v5, "kern": km}
+            dump(args.dump_outputs, {"ciphertext": k1024.eng.ct, "shared_secret": k1024.eng.ss, "status": k1024.eng.status,
+                                     "verified": d87.eng.ok}, rank, world)
+    if full and (extras or args.mode == "config5"):
         tk = Timer(ranks, ["mlkem_hash", "mlkem_encrypt"])
         el_k, kk = tk.run(k1024.encaps, 10, 1)
         td = Timer(ranks, ["mldsa_hash", "mldsa_verify"])
@@ -1229,14 +1292,14 @@ def main():
                 "roofline_mlkem1024": roofline("mlkem_encrypt_kernel<4>", n5, BYTES["mlkem1024_encaps"], kk["mlkem_encrypt"]["ms_per_step"]),
                 "roofline_mldsa87": roofline("mldsa_verify_kernel<87>", n5, BYTES["mldsa87_verify"], kd87["mldsa_verify"]["ms_per_step"]),
                 "parity": {"mlkem1024": pk5, "mldsa87": pd5, "ranks_failing": int(fails)}, "per_rank_per_s": ranks.gather(2 * n5 * k5 / el)}
-        if args.mode == "config5":
-            headline = {"elapsed": el, "value": v5, "kern": km}
         out_cfg["config5"] = cfg5
+    if extras or args.mode == "config5":
         del k1024, d87
         torch.cuda.empty_cache()
 
     if args.mode == "host":
-        headline = {"elapsed": B / host["pageable"]["value"] * args.steps, "value": host["pageable"]["whole_job_value"], "kern": {}}
+        value, elapsed = parallel.whole_job_rate(ranks, B * args.steps, host["pageable"]["total_s"])
+        headline = {"elapsed": elapsed, "value": value, "kern": {}}
 
     if more and rank == 0 and world == 1:
         out_cfg["small_batches"] = small_batches(dev)
@@ -1246,7 +1309,7 @@ def main():
 
     # ---- PMC: traffic / VALU instructions of the dominant kernels ----
     traffic, valu, pmc_note = None, None, None
-    if rank == 0 and enc_kern is not None:
+    if full and rank == 0 and enc_kern is not None:
         enc_avg_ms = enc_kern["mlkem_encrypt"]["ms_per_step"]
         probe = live_valu_probe(local)
         live_all, why = (None, "disabled (--no-pmc)") if (args.no_pmc or world > 1) else pmc_live(B)
@@ -1307,13 +1370,17 @@ def main():
             "strong": strong,
             "value_host_abi": ({"value": host["pageable"]["whole_job_value"], "pinned": host["pinned"]["whole_job_value"], "unit": "encaps/s",
                                 "what": "circl_hip_mlkem_encaps with host pointers (SURVEY 8d scope ii): H2D + kernels + D2H, pageable / page-locked caller buffers"}
-                               if host else None),
+                               if host and full else None),
             "sustained": sustained,
             "parity": parity_enc,
             "per_rank": per_rank,
             "configs": out_cfg,
             "bench_wall_s": time.perf_counter() - t_start,
         }
+        if not full:   # the headline alone: no roofline, CPU baseline or record file
+            print(contract_line(_finite(out), None), flush=True)
+            ranks.close()
+            return
         if enc_kern is not None:
             enc_avg_ms = enc_kern["mlkem_encrypt"]["ms_per_step"]
             r = roofline("mlkem_encrypt_kernel<3>", B, BYTES["mlkem768_encaps"], enc_avg_ms, traffic=traffic,

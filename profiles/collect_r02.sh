@@ -15,8 +15,8 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/prof_r02
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-python $ROOT/bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/r02_bench.json" 2> "$OUT/r02_bench.err"
-CMD="python $ROOT/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-pmc"
+python $ROOT/bench.py --full --gpus 1 --steps 20 --warmup 5 > "$OUT/r02_bench.json" 2> "$OUT/r02_bench.err"
+CMD="python $ROOT/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-pmc"
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/kt" -o kt -- $CMD > "$OUT/kt.log" 2>&1
 PCMD="python $ROOT/bench.py --pmc-child"
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d "$OUT/fetch" -o fetch -- $PCMD > "$OUT/fetch.log" 2>&1

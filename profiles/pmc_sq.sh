@@ -5,7 +5,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/sq
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-CMD="python $ROOT/bench.py --steps 2 --warmup 1 --no-cpu-baseline"
+CMD="python $ROOT/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline"
 i=0
 for grp in "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAVES" \
            "SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VMEM GRBM_GUI_ACTIVE" \
@@ -34,6 +34,6 @@ for k, d in agg.items():
         med = lambda c: sorted(d[c])[len(d[c]) // 2]
         out = {"mlkem768_encrypt_valu_insts_per_launch_2p20": med("SQ_INSTS_VALU"), "salu": med("SQ_INSTS_SALU"), "lds": med("SQ_INSTS_LDS"),
                "grbm_gui_active_per_xcd": med("GRBM_GUI_ACTIVE") / 8, "wave_quad_cycles": med("SQ_WAVE_CYCLES"),
-               "method": "rocprofv3 --pmc SQ_* (own passes, kernel-trace only), median over the launches of bench.py --steps 2; GRBM_GUI_ACTIVE is summed over the 8 XCDs; SQ_WAVE_CYCLES counts in units of 4 cycles"}
+               "method": "rocprofv3 --pmc SQ_* (own passes, kernel-trace only), median over the launches of bench.py --full --steps 2; GRBM_GUI_ACTIVE is summed over the 8 XCDs; SQ_WAVE_CYCLES counts in units of 4 cycles"}
 json.dump(out, open("gpurun_out/sq/valu.json", "w"), indent=1)
 PY

@@ -6,6 +6,7 @@ import json
 import os
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -103,3 +104,20 @@ def test_cpu_baseline_prints_each_figure_once():
     """No `vectorized` block repeating value / per_thread / shared_key (bench.py cpu_baseline)."""
     src = open(os.path.join(ROOT, "bench.py")).read()
     assert '"vectorized": vec' not in src
+
+
+def test_dump_outputs_stays_under_64_mb_and_samples_the_same_rows(tmp_path):
+    # bench.py --dump-outputs on an output too large to write whole: a float32 sample of rows, the same rows in every run
+    n = 1 << 16
+    ct = np.random.default_rng(0).integers(0, 256, (n, 1088), dtype=np.uint8)
+    st = (np.arange(n) % 7 == 0).astype(np.uint8)
+    for run in ("a", "b"):
+        bench.dump(str(tmp_path / run), {"ciphertext": ct, "status": st}, 0, 1)
+    a, b = tmp_path / "a", tmp_path / "b"
+    assert sorted(os.listdir(a)) == ["ciphertext.npy", "sample_rows.npy", "status.npy"]
+    assert sum(f.stat().st_size for f in a.iterdir()) <= 64 << 20
+    rows = np.load(a / "sample_rows.npy").astype(np.int64)
+    assert 1000 < len(rows) < n and (np.diff(rows) > 0).all()
+    got = np.load(a / "ciphertext.npy")
+    assert got.dtype == np.float32 and (got == ct[rows]).all() and (np.load(a / "status.npy") == st[rows]).all()
+    assert all((np.load(a / f) == np.load(b / f)).all() for f in os.listdir(a))

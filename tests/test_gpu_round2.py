@@ -389,7 +389,7 @@ print("proc ok")
 def test_bench_py_small_run_emits_every_config(tmp_path):
     xf = str(tmp_path / "extras.json")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--batch", str(1 << 14), "--no-pmc",
-                        "--no-cpu-baseline", "--extras", "all", "--extras-file", xf], cwd=ROOT, capture_output=True, text=True, timeout=900)
+                        "--no-cpu-baseline", "--full", "--extras", "all", "--extras-file", xf], cwd=ROOT, capture_output=True, text=True, timeout=900)
     line, out = bench_record(r, xf)
     assert line["parity"]["bit_exact_vs_oracle"] and line["parity"]["whole_batch"] and line["roofline"]["frac"] > 0
     for k in ("decaps", "config3", "config4", "config5"):
@@ -418,6 +418,32 @@ def test_bench_py_small_run_emits_every_config(tmp_path):
     assert out["roofline"]["frac"] > 0
 
 
+@pytest.mark.parametrize("mode", ["encaps", "host"])
+def test_bench_py_plain_run_times_its_steps_and_dumps_its_outputs(mode, tmp_path):
+    # a plain run (no --full) is the headline alone: exactly --steps timed steps, no parity / roofline / CPU baseline / record file;
+    # --dump-outputs holds what the last timed step computed (every row at this size), equal to the oracle's on the same seeded inputs
+    import bench
+    from oracle import orc
+    B, d, xf = 1 << 12, tmp_path / "out", tmp_path / "extras.json"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "1", "--batch", str(B), "--mode", mode,
+                        "--dump-outputs", str(d), "--extras-file", str(xf)], cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-6000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, lines
+    line = json.loads(lines[0])
+    assert line["steps"] == 4 and line["config"]["mode"] == mode and line["ms_per_step"] > 0 and line["higher_is_better"]
+    assert abs(line["value"] - B * 1e3 / line["ms_per_step"]) <= 1e-4 * line["value"]
+    assert all(line.get(k) is None for k in ("parity", "roofline", "cpu_baseline", "strong", "configs", "value_host_abi")), line
+    assert not xf.exists()
+    rows = np.load(d / "sample_rows.npy")
+    assert rows.dtype == np.float64 and (rows == np.arange(B)).all()
+    ct, ss, st = (np.load(d / (n + ".npy")) for n in ("ciphertext", "shared_secret", "status"))
+    assert ct.dtype == ss.dtype == st.dtype == np.float32 and ct.shape == (B, 1088) and ss.shape == (B, 32) and st.shape == (B,)
+    ek, _dk = orc.mlkem_keygen(768, bench.shake_seeds("circl-hip/keygen", B, 64))
+    ct0, ss0, st0 = orc.mlkem_encaps(768, ek, bench.shake_seeds("circl-hip/m", B, 32))
+    assert (ct == ct0).all() and (ss == ss0).all() and not st.any() and not st0.any()
+
+
 def test_bench_py_two_ranks_control_flow(tmp_path):
     # bench.py --gpus 2 as the driver launches it (torch.distributed.run, one rank per GPU) cannot run on a 1-GPU box with
     # RCCL; with the process group on gloo and both ranks sharing the one device, everything else of the N > 1 path runs:
@@ -428,7 +454,7 @@ def test_bench_py_two_ranks_control_flow(tmp_path):
     xf = str(tmp_path / "extras.json")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", str(1 << 13),
-                        "--extras-file", xf], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
+                        "--full", "--extras-file", xf], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     line, out = bench_record(r, xf)
     assert len(line["per_rank"]["encaps_per_s"]) == 2 and line["strong"]["items_per_rank"] == [1 << 12] * 2 and "cpu_baseline" not in line
     assert out["n_gpus"] == 2 and out["scaling"] == "weak" and out["parity"]["ranks_failing"] == 0

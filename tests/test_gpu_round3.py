@@ -73,7 +73,7 @@ def test_bench_py_eight_ranks(mode, tmp_path):
     xf = str(tmp_path / "extras.json")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
                         "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "3", "--warmup", "1", "--batch", str(1 << 12),
-                        "--mode", mode, "--no-pmc", "--extras-file", xf], cwd=ROOT, env=env, capture_output=True, text=True, timeout=1500)
+                        "--mode", mode, "--full", "--no-pmc", "--extras-file", xf], cwd=ROOT, env=env, capture_output=True, text=True, timeout=1500)
     line, out = bench_record(r, xf)   # the contract line (< 6 KB) and the full record it names
     assert line["n_gpus"] == 8 and line["config"]["mode"] == mode and line["value"] > 0
     assert out["n_gpus"] == 8 and out["scaling"] == "weak" and out["config"]["mode"] == mode and out["value"] > 0

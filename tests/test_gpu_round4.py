@@ -26,7 +26,7 @@ def test_bench_py_launches_its_own_eight_ranks(tmp_path):
         env.pop(k, None)
     xf = str(tmp_path / "extras.json")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "3", "--warmup", "1", "--batch", str(1 << 12),
-                        "--mode", "encaps", "--no-extras", "--no-pmc", "--extras-file", xf], cwd=ROOT, env=env, capture_output=True, text=True, timeout=1500)
+                        "--mode", "encaps", "--full", "--no-extras", "--no-pmc", "--extras-file", xf], cwd=ROOT, env=env, capture_output=True, text=True, timeout=1500)
     line, out = bench_record(r, xf)
     # what the driver's SCALE run keeps of an 8-rank line: the strong block and the per-rank rates, inside the 6 KB
     assert line["n_gpus"] == 8 and line["strong"]["items_per_rank"] == [512] * 8 and len(line["per_rank"]["encaps_per_s"]) == 8

@@ -28,7 +28,7 @@ note() { echo "[gpu_round +$((SECONDS - T0))s] $*"; }
 hdr() { echo "# command: $1"; echo "# box: $(grep -m1 'model name' /proc/cpuinfo | cut -d: -f2 | xargs), $(nproc) CPUs usable; lib sha256 $(sha256sum circl_amd/libcirclhip.so | cut -c1-16); $(date -u +%FT%TZ)"; }
 
 step_bench() {
-  local cmd="python bench.py --gpus 1 --steps 20 --warmup 5"
+  local cmd="python bench.py --full --gpus 1 --steps 20 --warmup 5"
   ( cd "$ROOT" && timeout 600 $cmd > "$OUT/bench.stdout" 2> "$OUT/bench.err" ); local rc=$?
   tail -n 1 "$OUT/bench.stdout" > "$OUT/bench.json"
   cp -f bench_extras.json "$OUT/bench_extras.json" 2>/dev/null
@@ -50,7 +50,7 @@ PY
 }
 
 step_stats() {
-  local cmd="python $ROOT/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-pmc --sample-parity"
+  local cmd="python $ROOT/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-pmc --sample-parity"
   ( cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/kt" -o kt -- $cmd > "$OUT/kt.log" 2>&1 )
   python profiles/summarize.py "$OUT" r06 > "$OUT/summarize.log" 2>&1
   { hdr "rocprofv3 --kernel-trace --stats --output-format csv -- $cmd  (condensed by profiles/summarize.py)"; cat "$OUT/r06_kernel_stats.txt"; } > "$OUT/kernel_stats.txt"

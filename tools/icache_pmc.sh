@@ -1,6 +1,6 @@
 ROOT=$GRAFT_REPO_ROOT; cd /tmp; export TMPDIR=/tmp
 rocprofv3 --list-avail 2>/dev/null | grep -oE "SQC?_[A-Z_0-9]*(ICACHE|IFETCH|INST_PREFETCH|DCACHE)[A-Z_0-9]*" | sort -u | tr '\n' ' '; echo
-CMD="python $ROOT/bench.py --steps 2 --warmup 1 --no-cpu-baseline"
+CMD="python $ROOT/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline"
 for grp in "SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQC_ICACHE_MISSES_DUPLICATE SQ_IFETCH" "SQC_DCACHE_REQ SQC_DCACHE_HITS SQC_DCACHE_MISSES SQ_WAIT_INST_ANY SQ_WAVE_CYCLES"; do
 rocprofv3 --kernel-trace --pmc $grp --output-format csv -d $ROOT/gpurun_out/ic -o ic -- $CMD > $ROOT/gpurun_out/ic.log 2>&1
 python - <<PY
