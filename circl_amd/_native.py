@@ -44,6 +44,9 @@ SYMBOLS = [
     "circl_hip_queue_open", "circl_hip_queue_close", "circl_hip_queue_eventfd", "circl_hip_queue_stats", "circl_hip_queue_submit", "circl_hip_queue_poll",
     "circl_hip_queue_wait",
     "circl_hip_poll", "circl_hip_wait", "circl_hip_profile_call_stamps",
+    "circl_hip_ed25519_workspace_size", "circl_hip_ed25519_keygen", "circl_hip_ed25519_sign", "circl_hip_ed25519_verify",
+    "circl_hip_ed25519_keygen_dev", "circl_hip_ed25519_sign_dev", "circl_hip_ed25519_verify_dev", "circl_hip_sha512",
+    "circl_hip_eddilithium2_keygen", "circl_hip_eddilithium2_sign", "circl_hip_eddilithium2_verify",
 ]
 
 OK, EPARAM, ENODEV, EHIP, ENOMEM, EWORKSPACE, EBUSY, EAGAIN = 0, -1, -2, -3, -4, -5, -6, -7
@@ -189,6 +192,18 @@ def lib():
         L.circl_hip_k12.argtypes = [vp, vp, vp, vp, vp, sz, sz, i]
         L.circl_hip_x25519.argtypes = [vp, vp, vp, vp, sz, i]
         L.circl_hip_x25519_dev.argtypes = [vp, vp, vp, vp, sz, vp]
+        L.circl_hip_ed25519_workspace_size.restype = sz
+        L.circl_hip_ed25519_workspace_size.argtypes = [sz]
+        L.circl_hip_ed25519_keygen.argtypes = [vp, vp, vp, sz, i]
+        L.circl_hip_ed25519_sign.argtypes = [vp, vp, vp, vp, sz, i]
+        L.circl_hip_ed25519_verify.argtypes = [vp, vp, vp, vp, vp, sz, i]
+        L.circl_hip_ed25519_keygen_dev.argtypes = [vp, vp, vp, sz, vp, sz, vp]
+        L.circl_hip_ed25519_sign_dev.argtypes = [vp, vp, vp, vp, sz, vp, sz, vp]
+        L.circl_hip_ed25519_verify_dev.argtypes = [vp, vp, vp, vp, vp, sz, vp, sz, vp]
+        L.circl_hip_sha512.argtypes = [vp, vp, vp, sz, i]
+        L.circl_hip_eddilithium2_keygen.argtypes = [vp, vp, vp, sz, i]
+        L.circl_hip_eddilithium2_sign.argtypes = [vp, vp, vp, vp, sz, i]
+        L.circl_hip_eddilithium2_verify.argtypes = [vp, vp, vp, vp, vp, sz, i]
         for f in ("seed", "eseed", "pk", "sk", "ct", "ss"):
             fn = getattr(L, "circl_hip_hybrid_%s_size" % f)
             fn.restype, fn.argtypes = sz, [i]

@@ -319,12 +319,15 @@ namespace x25519 {
 // addresses and selected per lane by compares, so neither addresses nor control flow depend on the scalar.
 // P + Q for Q = ((y+x)/2, (y-x)/2, dxy):  A = (Y+X) q0, B = (Y-X) q1, C = T q2;  E = A-B, H = A+B, G = Z+C, F = Z-C;
 // (X, Y, Z, T) <- (E F, G H, F G, E H) -- the extended coordinates of the sum scaled by 1/4.  For -Q: q0 <-> q1, G <-> F.
-CIRCL_HD void base_mult(uint32_t out[8], const uint32_t k_in[8]) {
+// base_comb: (X : Y : Z : T) = k B for any scalar below 2^255 (its top digit is at most 7 + 1).  Shared by X25519 KeyGen
+// (base_mult below) and Ed25519 key generation and signing (ed25519_dev.h).
+struct EdPoint {
+    Fe X, Y, Z, T;
+};
+CIRCL_HD EdPoint base_comb(const uint32_t k_in[8]) {
     uint32_t k[8];
 #pragma unroll
     for (int i = 0; i < 8; i++) k[i] = k_in[i];
-    k[0] &= ~7u;
-    k[7] = (k[7] & 0x7fffffffu) | 0x40000000u;
     Fe X = fe_const(0), Y = fe_const(1), Z = fe_const(1), T = fe_const(0);
     uint32_t carry = 0;
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -363,7 +366,17 @@ CIRCL_HD void base_mult(uint32_t out[8], const uint32_t k_in[8]) {
         Z = fe_mul(F, G);
         T = fe_mul(E, H);
     }
-    fe_to_words(out, fe_mul(fe_add(Z, Y), fe_inv(fe_sub(Z, Y))));  // u = (1 + y) / (1 - y)
+    return {X, Y, Z, T};
+}
+
+CIRCL_HD void base_mult(uint32_t out[8], const uint32_t k_in[8]) {
+    uint32_t k[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) k[i] = k_in[i];
+    k[0] &= ~7u;
+    k[7] = (k[7] & 0x7fffffffu) | 0x40000000u;
+    const EdPoint p = base_comb(k);
+    fe_to_words(out, fe_mul(fe_add(p.Z, p.Y), fe_inv(fe_sub(p.Z, p.Y))));  // u = (1 + y) / (1 - y)
 }
 
 }  // namespace x25519

@@ -697,3 +697,93 @@ class CallQueue:
         if rc == 0:
             self.handle = None
         return rc
+
+
+
+def ed25519_keygen(seeds, device=0):
+    """NewKeyFromSeed for every 32-byte seed -> (pk (n, 32), sk (n, 64) = seed || pk)"""
+    seeds = _u8(seeds, 32)
+    n = seeds.shape[0]
+    pk, sk = np.empty((n, 32), np.uint8), np.empty((n, 64), np.uint8)
+    nat.check(nat.lib().circl_hip_ed25519_keygen(_p(seeds), _p(pk), _p(sk), n, device), "ed25519_keygen")
+    return pk, sk
+
+
+def ed25519_sign(sk, msgs, device=0):
+    """Sign(sk_i, msg_i) -> (n, 64)"""
+    sk = _u8(sk, 64)
+    n = sk.shape[0]
+    assert len(msgs) == n
+    mb, mo = _blob(msgs)
+    sig = np.empty((n, 64), np.uint8)
+    nat.check(nat.lib().circl_hip_ed25519_sign(_p(sk), _p(mb), _p(mo), _p(sig), n, device), "ed25519_sign")
+    return sig
+
+
+def _rows_of_length(items, want):
+    """(indices of the items of exactly `want` bytes, those items as an (m, want) array)"""
+    items = [bytes(x) for x in items]
+    idx = [i for i, x in enumerate(items) if len(x) == want]
+    return idx, items
+
+
+def _verify_fixed(fn, pk, sig, msgs, PK, SIG, where, device):
+    """ok (n,): an item whose key is not PK bytes or whose signature is not SIG bytes is false without reaching the device, as in
+    the reference; every other item is decided on the device"""
+    n = len(msgs)
+    pk_i, pk_l = _rows_of_length(pk, PK)
+    sig_i, sig_l = _rows_of_length(sig, SIG)
+    assert len(pk_l) == n and len(sig_l) == n
+    idx = sorted(set(pk_i) & set(sig_i))
+    ok = np.zeros(n, np.uint8)
+    if idx:
+        pka = np.frombuffer(b"".join(pk_l[i] for i in idx), np.uint8).reshape(-1, PK).copy()
+        sga = np.frombuffer(b"".join(sig_l[i] for i in idx), np.uint8).reshape(-1, SIG).copy()
+        mb, mo = _blob([msgs[i] for i in idx])
+        sub = np.empty(len(idx), np.uint8)
+        nat.check(fn(_p(pka), _p(sga), _p(mb), _p(mo), _p(sub), len(idx), device), where)
+        ok[idx] = sub
+    return ok
+
+
+def ed25519_verify(pk, sig, msgs, device=0):
+    """Verify(pk_i, msg_i, sig_i) -> ok (n,) of 0 / 1; pk and sig are sequences of byte strings or (n, 32) / (n, 64) arrays.
+    Same argument order as mldsa_verify and the C ABI.  Wrong-length keys or signatures are false without a launch."""
+    return _verify_fixed(nat.lib().circl_hip_ed25519_verify, pk, sig, msgs, 32, 64, "ed25519_verify", device)
+
+
+def sha512(msgs, device=0):
+    """SHA-512 of every message -> (n, 64)"""
+    n = len(msgs)
+    mb, mo = _blob(msgs)
+    out = np.empty((n, 64), np.uint8)
+    nat.check(nat.lib().circl_hip_sha512(_p(mb), _p(mo), _p(out), n, device), "sha512")
+    return out
+
+
+EDDILITHIUM2_SIZES = dict(pk=1344, sk=2560, sig=2484)
+
+
+def eddilithium2_keygen(seeds, device=0):
+    """sign/eddilithium2 NewKeyFromSeed for every 32-byte seed -> (pk (n, 1344), sk (n, 2560))"""
+    seeds = _u8(seeds, 32)
+    n = seeds.shape[0]
+    pk, sk = np.empty((n, 1344), np.uint8), np.empty((n, 2560), np.uint8)
+    nat.check(nat.lib().circl_hip_eddilithium2_keygen(_p(seeds), _p(pk), _p(sk), n, device), "eddilithium2_keygen")
+    return pk, sk
+
+
+def eddilithium2_sign(sk, msgs, device=0):
+    """SignTo(sk_i, msg_i) -> (n, 2484) = deterministic Dilithium2 signature || Ed25519 signature"""
+    sk = _u8(sk, 2560)
+    n = sk.shape[0]
+    assert len(msgs) == n
+    mb, mo = _blob(msgs)
+    sig = np.empty((n, 2484), np.uint8)
+    nat.check(nat.lib().circl_hip_eddilithium2_sign(_p(sk), _p(mb), _p(mo), _p(sig), n, device), "eddilithium2_sign")
+    return sig
+
+
+def eddilithium2_verify(pk, sig, msgs, device=0):
+    """Verify(pk_i, msg_i, sig_i) -> ok (n,): both halves must verify; wrong lengths are false without a launch"""
+    return _verify_fixed(nat.lib().circl_hip_eddilithium2_verify, pk, sig, msgs, 1344, 2484, "eddilithium2_verify", device)

@@ -565,6 +565,52 @@ int circl_hip_k12(const uint8_t *msg_blob, const uint64_t *msg_off, const uint8_
 int circl_hip_x25519(const uint8_t *scalar, const uint8_t *point, uint8_t *out, uint8_t *ok, size_t n, int device);
 int circl_hip_x25519_dev(const uint8_t *d_scalar, const uint8_t *d_point, uint8_t *d_out, uint8_t *d_ok, size_t n, void *stream);
 
+/* ---- Ed25519 (sign/ed25519, pure Ed25519 of RFC 8032 5.1) -------------------------------------------------------
+ * One key / signature per item, each item with its own key; messages are ragged: item i's message is
+ * msg_blob[msg_off[i] .. msg_off[i+1]) (n + 1 offsets; msg_blob may be NULL when every message is empty).
+ * circl_hip_ed25519_keygen: NewKeyFromSeed(seed_i) (ed25519.go:206-223).  pk[i] (32) = A = enc([s]B) with
+ *   s = clamp(SHA-512(seed)[0..32)); sk[i] (64) = seed (32) || A (32), the reference's PrivateKey.  pk or sk may be NULL.
+ * circl_hip_ed25519_sign: Sign(sk_i, msg_i) (ed25519.go:225-284 signAll, no context, no pre-hash).  sig[i] (64) = R (32) ||
+ *   S (32, little-endian, below L): r = SHA-512(prefix || M) mod L with prefix = SHA-512(seed)[32..64), R = enc([r]B),
+ *   k = SHA-512(R || sk[32..64) || M) mod L, S = r + k s mod L.  The second half of sk is hashed AS STORED: it is never
+ *   recomputed from the seed nor checked against it, as in the reference.
+ * circl_hip_ed25519_verify: Verify(pk_i, msg_i, sig_i) (ed25519.go:329-366).  ok[i] = 1 iff S < L, pk decodes (y < p, x
+ *   exists, not x = 0 with the sign bit set: point.go:54-87) and enc([S]B - [k]A) equals the 32 bytes of R, k = SHA-512(R ||
+ *   pk || M) mod L -- the cofactorless check, item by item (no batch shortcut: every ok[i] is the reference's verdict).  The
+ *   ABI takes 64-byte signatures; a signature of any other length is the caller's to reject (the reference returns false).
+ * The scheme has no context (SupportsContext() == false).
+ * _dev forms: device pointers (rows 4-byte aligned, msg_off 8-byte aligned), any stream.  Verification needs
+ *   circl_hip_ed25519_workspace_size(n) bytes of workspace (public multiples of the keys); key generation and signing keep
+ *   their secrets (seed, s, prefix, r) in registers and leave the workspace untouched (it may be NULL).  The host forms
+ *   wipe the device staging of seeds and private keys. */
+size_t circl_hip_ed25519_workspace_size(size_t n);
+int circl_hip_ed25519_keygen(const uint8_t *seed32, uint8_t *pk32, uint8_t *sk64, size_t n, int device);
+int circl_hip_ed25519_sign(const uint8_t *sk64, const uint8_t *msg_blob, const uint64_t *msg_off, uint8_t *sig64, size_t n, int device);
+int circl_hip_ed25519_verify(const uint8_t *pk32, const uint8_t *sig64, const uint8_t *msg_blob, const uint64_t *msg_off, uint8_t *ok,
+                             size_t n, int device);
+int circl_hip_ed25519_keygen_dev(const uint8_t *d_seed32, uint8_t *d_pk32, uint8_t *d_sk64, size_t n, void *d_workspace,
+                                 size_t workspace_bytes, void *stream);
+int circl_hip_ed25519_sign_dev(const uint8_t *d_sk64, const uint8_t *d_msg_blob, const uint64_t *d_msg_off, uint8_t *d_sig64, size_t n,
+                               void *d_workspace, size_t workspace_bytes, void *stream);
+int circl_hip_ed25519_verify_dev(const uint8_t *d_pk32, const uint8_t *d_sig64, const uint8_t *d_msg_blob, const uint64_t *d_msg_off,
+                                 uint8_t *d_ok, size_t n, void *d_workspace, size_t workspace_bytes, void *stream);
+/* FIPS 180-4 SHA-512 of every message (crypto/sha512.Sum512): out64[i] = the 64-byte digest of item i. */
+int circl_hip_sha512(const uint8_t *msg_blob, const uint64_t *msg_off, uint8_t *out64, size_t n, int device);
+
+/* ---- Ed25519-Dilithium2 (sign/eddilithium2/eddilithium.go): round-3 Dilithium2 (sign/dilithium/mode2) next to Ed25519 ----
+ * circl_hip_eddilithium2_keygen: NewKeyFromSeed(seed_i): SHAKE256(seed) -> 32 bytes for mode2, then 32 for Ed25519.
+ *   pk[i] (1344) = mode2 pk (1312) || Ed25519 pk (32); sk[i] (2560) = mode2 sk (2528) || the Ed25519 SEED (32).
+ * circl_hip_eddilithium2_sign: SignTo (:150-162): sig[i] (2484) = the deterministic mode2 signature (2420) || the Ed25519
+ *   signature (64) of the same message, the Ed25519 key re-derived from the seed in sk (Unpack, :127-132).
+ * circl_hip_eddilithium2_verify: Verify (:166-171): ok[i] = 1 iff both halves verify.  A signature of any other length than
+ *   2484 bytes is false in the reference; the ABI takes 2484-byte rows, so that check is the caller's.
+ * No context (SupportsContext() == false).  Both halves run on the device, on one stream per chunk, with no host round trip
+ * between them; the device staging and workspace of keygen and sign (both private keys) are zeroed after every chunk. */
+int circl_hip_eddilithium2_keygen(const uint8_t *seed32, uint8_t *pk, uint8_t *sk, size_t n, int device);
+int circl_hip_eddilithium2_sign(const uint8_t *sk, const uint8_t *msg_blob, const uint64_t *msg_off, uint8_t *sig, size_t n, int device);
+int circl_hip_eddilithium2_verify(const uint8_t *pk, const uint8_t *sig, const uint8_t *msg_blob, const uint64_t *msg_off, uint8_t *ok,
+                                  size_t n, int device);
+
 /* ---- hybrid KEMs around ML-KEM-768, composed on the device -------------------------------
  * scheme = CIRCL_HIP_HYBRID_XWING: kem/xwing/xwing.go -- DeriveKeyPairPacked (:98-144), EncapsulateTo (:223-265),
  *   DecapsulateTo (:270-299), combiner (:53-71).  seed 32, eseed 64 (seedm || ekx), pk 1216 (ek || pk_X), sk 32 (the
@@ -637,7 +683,11 @@ int circl_hip_hybrid_decaps_table_dev(const circl_hip_keytable *table, const uin
 #define CIRCL_HIP_KERNEL_MLKEM_KEYTABLE 9  /* key tables: H(ek) + A^T per table entry */
 #define CIRCL_HIP_KERNEL_MLDSA_KEYTABLE 10 /* key tables: tr + ExpandA per table entry */
 #define CIRCL_HIP_KERNEL_X25519 11         /* X25519 ladder                            */
-#define CIRCL_HIP_KERNEL_COUNT 12
+#define CIRCL_HIP_KERNEL_ED25519_KEYGEN 12 /* Ed25519 NewKeyFromSeed                   */
+#define CIRCL_HIP_KERNEL_ED25519_SIGN 13   /* Ed25519 Sign                             */
+#define CIRCL_HIP_KERNEL_ED25519_VERIFY 14 /* Ed25519 Verify                           */
+#define CIRCL_HIP_KERNEL_SHA512 15         /* batch SHA-512                            */
+#define CIRCL_HIP_KERNEL_COUNT 16
 int circl_hip_profile_enable(int on);
 int circl_hip_profile_read(int kernel, double *total_ms, uint64_t *launches);
 /* The VALU issue rates this chip sustains, measured live (bench.py prices the kernels' VALU time against them instead of against
