@@ -103,10 +103,17 @@ int circl_hip_keccak_f1600_split(uint64_t *states, size_t n, int device) {
 
 int circl_hip_kyber_ntt(int16_t *polys, size_t n, int inverse, int device) {
     uint8_t *p = reinterpret_cast<uint8_t *>(polys);
+    // The exchange form of the transforms (kyber::Exchange).  The default is the form of the big-batch ML-KEM kernels' ring phase; the knob,
+    // read at every call, lets a test or a probe force each form in turn.
+    const int xch = env_int("CIRCL_HIP_NTT_XCH", CIRCL_KEM_RING_XCH, 0, 3);
+    auto *kern = xch == circl::kyber::XCH_LDS      ? circl::prim::kyber_ntt_kernel<circl::kyber::XCH_LDS>
+                 : xch == circl::kyber::XCH_LDS_NW ? circl::prim::kyber_ntt_kernel<circl::kyber::XCH_LDS_NW>
+                 : xch == circl::kyber::XCH_LANES  ? circl::prim::kyber_ntt_kernel<circl::kyber::XCH_LANES>
+                                                   : circl::prim::kyber_ntt_kernel<circl::kyber::XCH_LANES_TOP>;
     return shard(n, device, [&](int dev, size_t lo, size_t cnt) {
         return run_pipeline(dev, cnt, {{p + lo * 512, 512}}, {}, {{p + lo * 512, 512}}, no_ws, prim_opts(512), [&](Chunk &c) {
             HIP_TRY(hipMemcpyAsync(c.out[0], c.in[0], c.cnt * 512, hipMemcpyDeviceToDevice, c.st));
-            hipLaunchKernelGGL(circl::prim::kyber_ntt_kernel, dim3((unsigned)c.cnt), dim3(64), 0, c.st, reinterpret_cast<int16_t *>(c.out[0]), inverse);
+            hipLaunchKernelGGL(kern, dim3((unsigned)c.cnt), dim3(64), 0, c.st, reinterpret_cast<int16_t *>(c.out[0]), inverse);
             HIP_TRY(hipGetLastError());
             return CIRCL_HIP_OK;
         });

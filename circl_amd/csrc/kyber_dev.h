@@ -20,11 +20,20 @@
 //   L3: n = ((l>>2)<<4) | (r<<2) | (l&3)           bits 3,2 local
 //   L4: n = 4 l + r                                bits 1,0 local ("4 consecutive coefficients")
 // The 7 NTT layers (strides 128..2) are done two at a time on register-local pairs; between
-// them the wave re-distributes the polynomial through a 1 KB LDS scratch (3 exchanges per
-// transform).  L4 is the layout of MulHat (pairs (4l,4l+1) and (4l+2,4l+3) share zeta =
+// them the wave re-distributes the polynomial (3 exchanges per transform): across its lanes, or
+// through a 1 KB LDS scratch (the forms of `Exchange` below).  L4 is the layout of MulHat (pairs (4l,4l+1) and (4l+2,4l+3) share zeta =
 // Zetas[64+l], poly.go:63-100), of the 12-bit codec and of coalesced 8-byte LDS/global access.
 #pragma once
 #include "keccak_dev.h"
+
+// How the transforms of the big-batch kernels' ring phase (mlkem_encrypt_kernel, mlkem_keygen_kernel) re-distribute a polynomial between
+// register layouts (kyber::Exchange below): 0 = through LDS with barriers, 2 = across the lanes, 3 = L1 <-> L2 across the lanes and the
+// rest through LDS.  The one-launch chain kernels keep their no-wait LDS form.  Measured (profiles/kem_ring_xlane_ab.txt, five libraries
+// alternating on one box, five rounds): the headline 1.4405e8 -> 1.4539e8 encapsulations/s with 2 (+0.9 %; 3: a little less), although the
+// cross-lane moves are NOT full-rate instructions (DPP moves 4.3, the lane swaps 8.2 cycles at 4 wavefronts per SIMD).
+#ifndef CIRCL_KEM_RING_XCH
+#define CIRCL_KEM_RING_XCH 2
+#endif
 
 namespace circl {
 namespace kyber {
@@ -172,34 +181,103 @@ template <bool NW = false> __device__ __forceinline__ void wave_sync() {
     else __syncthreads();
 }
 
-// Re-distribute a polynomial between register layouts through `xch` (256 elements of T in LDS: 512 bytes for
-// uint16_t, 1 KB for uint32_t -- values must fit T).
-template <int FROM, int TO, class T, bool NW = false> __device__ __forceinline__ void relayout(int (&c)[4], void *xch_raw, int lane) {
-    T *xch = reinterpret_cast<T *>(xch_raw);
-    auto idx = [&](int which, int r) {
-        return which == 1 ? idx_l1(lane, r) : which == 2 ? idx_l2(lane, r) : which == 3 ? idx_l3(lane, r) : idx_l4(lane, r);
-    };
-    wave_sync<NW>();  // earlier readers of xch are done
+// The exchange between two layouts comes in three forms, chosen by the template parameter XCH of relayout / ntt / invntt (the
+// first two are the values false / true of the former `bool NW`, so callers that pass a bool keep their meaning):
+//   XCH_LDS       through `xch` in LDS, workgroup barriers around the stores
+//   XCH_LDS_NW    through `xch` in LDS, no-wait form (above)
+//   XCH_LANES     cross-lane moves, no memory: see lane_transpose below.  `xch` is not touched.
+//   XCH_LANES_TOP L1 <-> L2 by cross-lane swaps, the other two exchanges as XCH_LDS (kept for A/B measurements)
+enum Exchange { XCH_LDS = 0, XCH_LDS_NW = 1, XCH_LANES = 2, XCH_LANES_TOP = 3 };
+
+// The four layouts differ only in WHICH two bits of the coefficient index are the register number r (the other six are the
+// lane number, in order): L1 <-> L2 trades r with lane bits 5,4; L2 <-> L3 with lane bits 3,2; L3 <-> L4 with lane bits 1,0.
+// Every exchange between neighbours is therefore a 4 x 4 transpose between r and one pair of lane bits, i.e. two stages of
+// 2 x 2 transposes: stage "r bit 1 with the upper lane bit" on the register pairs (c0,c2), (c1,c3) and stage "r bit 0 with the
+// lower lane bit" on (c0,c1), (c2,c3).  Each transpose is its own inverse, so FROM -> TO and TO -> FROM are the same code.
+//
+// lane_swap<B>(a, b): the 2 x 2 transpose of the register pair (a, b) with lane bit B -- lanes with bit B clear keep a and
+// receive, as their new b, the a of the partner lane (lane ^ 2^B); lanes with bit B set keep b and receive the partner's b as a:
+//     a'[l] = bit_B(l) ? b[l ^ 2^B] : a[l]          b'[l] = bit_B(l) ? b[l] : a[l ^ 2^B]
+//   B = 5  V_PERMLANE32_SWAP_B32 vdst = a, src0 = b: "swap lanes 32..63 of vdst with lanes 0..31 of src0" (CDNA4 ISA, VOP1)
+//   B = 4  V_PERMLANE16_SWAP_B32 vdst = a, src0 = b: "swap the odd rows of vdst with the even rows of src0" (rows of 16 lanes)
+//   B = 3  DPP row_ror:8 (lane l reads lane l ^ 8 of its row of 16), written under a bank mask (a bank is 4 lanes): banks 2,3 of a, banks 0,1 of b
+//   B = 2  DPP row_shr:4 into banks 1,3 of a (lane l reads l - 4), row_shl:4 into banks 0,2 of b (lane l reads l + 4)
+//   B = 1, 0  DPP quad_perm [2,3,0,1] / [1,0,3,2] (lane l reads l ^ 2 / l ^ 1 of its quad); DPP has no per-lane write mask, so the
+//          value to send is selected first and the received one is selected into place: 3 selects + 1 move
+// All 64 lanes must be active (every caller runs the transforms in wave-uniform control flow): a cross-lane move reads nothing from a
+// disabled lane.  tests/test_gpu_relayout.py pins every index path of every stage against the oracle's transform.
+template <int B> __device__ __forceinline__ void lane_swap(int &a, int &b, int lane) {
+    static_assert(B >= 0 && B <= 5, "lane bit");
+    constexpr int ROW_SHL = 0x100, ROW_SHR = 0x110, ROW_ROR = 0x120;
+    if constexpr (B == 5) {
+        const auto v = __builtin_amdgcn_permlane32_swap((unsigned)a, (unsigned)b, false, false);
+        a = (int)v[0];
+        b = (int)v[1];
+    } else if constexpr (B == 4) {
+        const auto v = __builtin_amdgcn_permlane16_swap((unsigned)a, (unsigned)b, false, false);
+        a = (int)v[0];
+        b = (int)v[1];
+    } else if constexpr (B == 3) {
+        const int t = a;
+        a = __builtin_amdgcn_update_dpp(a, b, ROW_ROR + 8, 0xf, 0xc, false);
+        b = __builtin_amdgcn_update_dpp(b, t, ROW_ROR + 8, 0xf, 0x3, false);
+    } else if constexpr (B == 2) {
+        const int t = a;
+        a = __builtin_amdgcn_update_dpp(a, b, ROW_SHR + 4, 0xf, 0xa, false);
+        b = __builtin_amdgcn_update_dpp(b, t, ROW_SHL + 4, 0xf, 0x5, false);
+    } else {
+        constexpr int QUAD = B == 1 ? 0x4e : 0xb1;  // quad_perm:[2,3,0,1] / [1,0,3,2]
+        const bool up = (lane >> B) & 1;
+        const int send = up ? a : b;
+        const int recv = __builtin_amdgcn_update_dpp(0, send, QUAD, 0xf, 0xf, true);
+        a = up ? recv : a;
+        b = up ? b : recv;
+    }
+}
+// The 4 x 4 transpose between the register number and lane bits HI, HI - 1
+template <int HI> __device__ __forceinline__ void lane_transpose(int (&c)[4], int lane) {
+    lane_swap<HI>(c[0], c[2], lane);
+    lane_swap<HI>(c[1], c[3], lane);
+    lane_swap<HI - 1>(c[0], c[1], lane);
+    lane_swap<HI - 1>(c[2], c[3], lane);
+}
+
+// Re-distribute a polynomial between register layouts: through `xch` (256 elements of T in LDS: 512 bytes for
+// uint16_t, 1 KB for uint32_t -- values must fit T) or across the lanes (neighbouring layouts only).
+template <int FROM, int TO, class T, int XCH = XCH_LDS> __device__ __forceinline__ void relayout(int (&c)[4], void *xch_raw, int lane) {
+    constexpr int LOW = FROM < TO ? FROM : TO;
+    static_assert(XCH >= XCH_LDS && XCH <= XCH_LANES_TOP, "exchange form");
+    if constexpr (XCH == XCH_LANES || (XCH == XCH_LANES_TOP && LOW == 1)) {
+        static_assert(FROM - TO == 1 || TO - FROM == 1, "cross-lane exchanges are between neighbouring layouts");
+        lane_transpose<7 - 2 * LOW>(c, lane);
+    } else {
+        constexpr bool NW = XCH == XCH_LDS_NW;
+        T *xch = reinterpret_cast<T *>(xch_raw);
+        auto idx = [&](int which, int r) {
+            return which == 1 ? idx_l1(lane, r) : which == 2 ? idx_l2(lane, r) : which == 3 ? idx_l3(lane, r) : idx_l4(lane, r);
+        };
+        wave_sync<NW>();  // earlier readers of xch are done
 #pragma unroll
-    for (int r = 0; r < 4; r++) xch[idx(FROM, r)] = (T)c[r];
-    wave_sync<NW>();
+        for (int r = 0; r < 4; r++) xch[idx(FROM, r)] = (T)c[r];
+        wave_sync<NW>();
 #pragma unroll
-    for (int r = 0; r < 4; r++) c[r] = (int)xch[idx(TO, r)];
+        for (int r = 0; r < 4; r++) c[r] = (int)xch[idx(TO, r)];
+    }
 }
 
 // Poly.NTT (ntt.go:60-135).  In: layout L1, 0 <= c < IN_BOUND (any bound up to 2^16 - 7q).  Out: layout L4,
 // 0 <= c < IN_BOUND + 7q, congruent to the reference's transform.
-template <bool NW = false> __device__ __forceinline__ void ntt(int (&c)[4], const LaneZetas &z, void *xch, int lane) {
+template <int XCH = XCH_LDS> __device__ __forceinline__ void ntt(int (&c)[4], const LaneZetas &z, void *xch, int lane) {
     const uint32_t z1 = zeta_c(1), z2 = zeta_c(2), z3 = zeta_c(3);
     ct(c[0], c[2], z1); ct(c[1], c[3], z1);
     ct(c[0], c[1], z2); ct(c[2], c[3], z3);
-    relayout<1, 2, uint16_t, NW>(c, xch, lane);
+    relayout<1, 2, uint16_t, XCH>(c, xch, lane);
     ct(c[0], c[2], z.f2); ct(c[1], c[3], z.f2);
     ct(c[0], c[1], z.f3a); ct(c[2], c[3], z.f3b);
-    relayout<2, 3, uint16_t, NW>(c, xch, lane);
+    relayout<2, 3, uint16_t, XCH>(c, xch, lane);
     ct(c[0], c[2], z.f4); ct(c[1], c[3], z.f4);
     ct(c[0], c[1], z.f5a); ct(c[2], c[3], z.f5b);
-    relayout<3, 4, uint16_t, NW>(c, xch, lane);
+    relayout<3, 4, uint16_t, XCH>(c, xch, lane);
     ct(c[0], c[2], z.f6); ct(c[1], c[3], z.f6);
 }
 
@@ -208,16 +286,16 @@ template <bool NW = false> __device__ __forceinline__ void ntt(int (&c)[4], cons
 // 128^-1 R^2 after Montgomery products that each carried R^-1.)  In: layout L4, 0 <= c < q.  Out: layout L1, 0 <= c < q.
 // The sums double per layer (below 2^k q after k layers) and are never reduced on the way: 128 q is far below
 // MULC_LIMIT.  The first two exchanges fit 16-bit elements (< 8q), the third (< 32q) uses 32-bit ones.
-template <uint32_t SCALE, bool NW = false> __device__ __forceinline__ void invntt(int (&c)[4], const LaneZetas &z, void *xch, int lane) {
+template <uint32_t SCALE, int XCH = XCH_LDS> __device__ __forceinline__ void invntt(int (&c)[4], const LaneZetas &z, void *xch, int lane) {
     static_assert(128u * Q < MULC_LIMIT, "lazy sums stay inside the mulc domain");
     gs<Q>(c[0], c[2], z.i6); gs<Q>(c[1], c[3], z.i6);
-    relayout<4, 3, uint16_t, NW>(c, xch, lane);
+    relayout<4, 3, uint16_t, XCH>(c, xch, lane);
     gs<2 * Q>(c[0], c[1], z.i5a); gs<2 * Q>(c[2], c[3], z.i5b);
     gs<4 * Q>(c[0], c[2], z.i4); gs<4 * Q>(c[1], c[3], z.i4);
-    relayout<3, 2, uint16_t, NW>(c, xch, lane);
+    relayout<3, 2, uint16_t, XCH>(c, xch, lane);
     gs<8 * Q>(c[0], c[1], z.i3a); gs<8 * Q>(c[2], c[3], z.i3b);
     gs<16 * Q>(c[0], c[2], z.i2); gs<16 * Q>(c[1], c[3], z.i2);
-    relayout<2, 1, uint32_t, NW>(c, xch, lane);
+    relayout<2, 1, uint32_t, XCH>(c, xch, lane);
     const uint32_t z1 = zeta_c(1), z2 = zeta_c(2), z3 = zeta_c(3);
     gs<32 * Q>(c[0], c[1], z3); gs<32 * Q>(c[2], c[3], z2);
     gs<64 * Q>(c[0], c[2], z1); gs<64 * Q>(c[1], c[3], z1);

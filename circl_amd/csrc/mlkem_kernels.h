@@ -40,6 +40,7 @@
 #ifndef CIRCL_KEM_WAVES_PER_EU
 #define CIRCL_KEM_WAVES_PER_EU 4
 #endif
+// (CIRCL_KEM_RING_XCH, the exchange form of the big-batch kernels' transforms, is set in kyber_dev.h.)
 
 namespace circl {
 namespace mlkem {
@@ -419,6 +420,21 @@ __device__ __forceinline__ void sample_matrix(uint8_t *lds_a, const uint8_t *__r
     }
 }
 
+// cnt += v < q, the sampler's accept counter.  Left to the compiler this is V_CMP -> (S_NOP) -> V_CNDMASK 0,1 -> V_ADDC on two alternating
+// counters; the plain form is the compare and ONE add with carry-in (VOP2, the carry straight from VCC: no mask materialised, no hazard
+// wait): 710 of the headline kernel's 7 303 static instructions and 317 of its 370 S_NOP fewer.  Same value either way; CIRCL_KEM_ACCEPT_ASM=0
+// restores the compiler's form for A/B runs (profiles/kem_ring_xlane_ab.txt: the headline +0.6 % on its own, +1.6 % with the cross-lane exchange).
+#ifndef CIRCL_KEM_ACCEPT_ASM
+#define CIRCL_KEM_ACCEPT_ASM 1
+#endif
+__device__ __forceinline__ void count_accept(int &cnt, uint32_t v) {
+#if defined(__HIP_DEVICE_COMPILE__) && CIRCL_KEM_ACCEPT_ASM
+    asm("v_cmp_gt_u32_e32 vcc, %2, %1\n\tv_addc_co_u32_e32 %0, vcc, 0, %0, vcc" : "+v"(cnt) : "v"(v), "s"((uint32_t)Q) : "vcc");
+#else
+    cnt += v < (uint32_t)Q ? 1 : 0;
+#endif
+}
+
 // Scratch variant of phase A.  Each lane appends accepted coefficients to a 32-slot LDS FIFO and
 // flushes 8 of them (16 bytes) at a time to its 512-byte row of the workgroup's global scratch, so
 // every global store is a full 16-byte segment.  Same branch-free acceptance as above.
@@ -436,7 +452,7 @@ __device__ __forceinline__ void parse_shake128_block_fifo(const KeccakState &s, 
             if constexpr (sh <= 20) v = (word(w) >> sh) & 0xfffu;
             else v = alignbit(word(w + 1), word(w), sh) & 0xfffu;
             fifo[cnt & (SLOTS - 1)] = (int16_t)v;
-            cnt += v < (uint32_t)Q ? 1 : 0;
+            count_accept(cnt, v);
             if constexpr (c % 8 == 7) {
                 // The count is capped at the row length here, once per 8 candidates, not per candidate: between two checks a
                 // finished stream runs at most 8 entries past 256, into FIFO slots that hold nothing pending (fewer than 8
@@ -1054,7 +1070,7 @@ __global__ void __launch_bounds__(64, SCRATCH ? CIRCL_KEM_WAVES_PER_EU : 1) mlke
         for (int j = 0; j < K; j++) {
 #pragma unroll
             for (int r = 0; r < 4; r++) rh[j][r] = cbd_coeff<P::ETA1>(noise + j * Gm::NOISE_STRIDE, kyber::idx_l1(lane, r));
-            kyber::ntt(rh[j], z, xch, lane);
+            kyber::ntt<CIRCL_KEM_RING_XCH>(rh[j], z, xch, lane);
         }
         kyber::HatOperand rop[K];
 #pragma unroll
@@ -1078,7 +1094,7 @@ __global__ void __launch_bounds__(64, SCRATCH ? CIRCL_KEM_WAVES_PER_EU : 1) mlke
                 kyber::mulhat_acc_packed(acc, a01, a23, rop[j]);
             }
             kyber::mulhat_finish(acc);
-            kyber::invntt<kyber::NEG_R32>(acc, z, xch, lane);  // undoes mulhat_finish's -2^-32: plain coefficients in [0, q)
+            kyber::invntt<kyber::NEG_R32, CIRCL_KEM_RING_XCH>(acc, z, xch, lane);  // undoes mulhat_finish's -2^-32: plain coefficients in [0, q)
             const uint8_t *e1 = noise + (K + i) * Gm::NOISE_STRIDE;
             unsigned cv[4];
 #pragma unroll
@@ -1098,7 +1114,7 @@ __global__ void __launch_bounds__(64, SCRATCH ? CIRCL_KEM_WAVES_PER_EU : 1) mlke
 #pragma unroll
             for (int j = 0; j < K; j++) kyber::mulhat_acc_packed(acc, kyber::pack16(th[j][0], th[j][1]), kyber::pack16(th[j][2], th[j][3]), rop[j]);
             kyber::mulhat_finish(acc);
-            kyber::invntt<kyber::NEG_R32>(acc, z, xch, lane);  // undoes mulhat_finish's -2^-32: plain coefficients in [0, q)
+            kyber::invntt<kyber::NEG_R32, CIRCL_KEM_RING_XCH>(acc, z, xch, lane);  // undoes mulhat_finish's -2^-32: plain coefficients in [0, q)
             const uint8_t *e2 = noise + 2 * K * Gm::NOISE_STRIDE;
             const uint8_t *mp = m + item * 32;
             unsigned cv[4];
@@ -1950,7 +1966,7 @@ __global__ void __launch_bounds__(64, SCRATCH ? CIRCL_KEM_WAVES_PER_EU : 1) mlke
         for (int j = 0; j < K; j++) {
 #pragma unroll
             for (int r = 0; r < 4; r++) sh[j][r] = cbd_coeff<P::ETA1>(noise + j * Gm::NOISE_STRIDE, kyber::idx_l1(lane, r));
-            kyber::ntt(sh[j], z, xch, lane);
+            kyber::ntt<CIRCL_KEM_RING_XCH>(sh[j], z, xch, lane);
 #pragma unroll
             for (int r = 0; r < 4; r++) sh[j][r] = kyber::normalize(sh[j][r]);
             pack12_l4(dkp + 384 * j, sh[j], lane);
@@ -1963,7 +1979,7 @@ __global__ void __launch_bounds__(64, SCRATCH ? CIRCL_KEM_WAVES_PER_EU : 1) mlke
             int eh[4], acc[4] = {0, 0, 0, 0};
 #pragma unroll
             for (int r = 0; r < 4; r++) eh[r] = cbd_coeff<P::ETA1>(noise + (K + i) * Gm::NOISE_STRIDE, kyber::idx_l1(lane, r));
-            kyber::ntt(eh, z, xch, lane);
+            kyber::ntt<CIRCL_KEM_RING_XCH>(eh, z, xch, lane);
 #pragma unroll
             for (int j = 0; j < K; j++) {
                 uint32_t a01, a23;

@@ -85,8 +85,9 @@ __global__ void __launch_bounds__(256) keccak_f1600_split_kernel(uint64_t *state
 
 // One polynomial per single-wave workgroup, int16[256] in standard order, in place.
 // Outputs are normalised to [0,q).  The inverse carries the reference's factor: Poly.InvNTT returns 2^16 times the
-// exact inverse (ntt.go:145-193; ntt_test.go:83-109 checks InvNTT(NTT(p)) = p * 2^16).
-__global__ void __launch_bounds__(64) kyber_ntt_kernel(int16_t *polys, int inverse) {
+// exact inverse (ntt.go:145-193; ntt_test.go:83-109 checks InvNTT(NTT(p)) = p * 2^16).  XCH = the exchange form of the transforms
+// (kyber::Exchange): every form computes the same values, tests/test_gpu_relayout.py forces each in turn.
+template <int XCH> __global__ void __launch_bounds__(64) kyber_ntt_kernel(int16_t *polys, int inverse) {
     __shared__ __attribute__((aligned(16))) uint32_t xch[256];
     const int lane = threadIdx.x;
     int16_t *p = polys + (size_t)blockIdx.x * 256;
@@ -95,13 +96,13 @@ __global__ void __launch_bounds__(64) kyber_ntt_kernel(int16_t *polys, int inver
     if (!inverse) {
 #pragma unroll
         for (int r = 0; r < 4; r++) c[r] = kyber::normalize(p[kyber::idx_l1(lane, r)]);
-        kyber::ntt(c, z, xch, lane);
+        kyber::ntt<XCH>(c, z, xch, lane);
 #pragma unroll
         for (int r = 0; r < 4; r++) p[kyber::idx_l4(lane, r)] = (int16_t)kyber::normalize(c[r]);
     } else {
 #pragma unroll
         for (int r = 0; r < 4; r++) c[r] = kyber::normalize(p[kyber::idx_l4(lane, r)]);
-        kyber::invntt<65536u>(c, z, xch, lane);
+        kyber::invntt<65536u, XCH>(c, z, xch, lane);
 #pragma unroll
         for (int r = 0; r < 4; r++) p[kyber::idx_l1(lane, r)] = (int16_t)c[r];
     }

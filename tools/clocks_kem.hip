@@ -4,7 +4,7 @@
 // for a ticket, in the sampling phase (matrix A^T on 9 / 16 streams + the PRF streams: Keccak rounds back to back) and in the ring phase
 // (NTTs through LDS exchanges, the products against the scratch rows, compression) -- while three other wavefronts of the same SIMD are in
 // whatever phase they are in.  Real keys (GPU key generation), real r (the hash kernel): the kernel does exactly the headline's work.
-//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -Icircl_amd/csrc -Iinclude [-DCIRCL_KEM_RING_PRIO=0] tools/clocks_kem.hip -o tools/bin/clocks_kem
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -Icircl_amd/csrc -Iinclude [-DCIRCL_KEM_RING_PRIO=0] [-DCIRCL_KEM_RING_XCH=0|2|3] tools/clocks_kem.hip -o tools/bin/clocks_kem
 //   tools/bin/clocks_kem [log2 n = 20]
 #include <hip/hip_runtime.h>
 

@@ -5,6 +5,8 @@ issue cost of a VALU instruction on gfx950, and how long is the dependent-issue 
 Every test is a block of 64 instructions on PHYSICAL registers (v16..v47, clobbered), so the operand banks are
 what the test says and not what the register allocator happened to pick.  Output: cycles per wave-instruction
 per SIMD at 1 / 2 / 4 / 8 waves per SIMD (wall time x 2.4 GHz nominal).
+
+    python tools/gen_bank_probe.py [out.hip [label-regex]]     (the regular expression keeps only the tests whose label matches)
 """
 import sys
 
@@ -129,10 +131,29 @@ def cross_chain(nacc):
 for n in (1, 2, 4, 8):
     add(f"bitop3->alignbit chain, {n} acc", cross_chain(n))
 
+
+# ---- cross-lane moves (the exchange form XCH_LANES of kyber_dev.h): DPP moves under a bank mask / on quads, and the two gfx950 lane swaps.
+# Sources come from v32..v47, which nothing in the block writes (a DPP read of a VGPR needs two wait states behind the VALU write of it;
+# the swaps write BOTH operands, so theirs are 8 disjoint pairs (v16+i, v32+i) and every register is 8 instructions old when it is read).
+def dpp_mov(ctrl):
+    return [f"v_mov_b32_dpp v{16 + i}, v{bank_reg(32, (i + 1) % 4, rep % 4)} {ctrl}" for rep in range(8) for i in range(8)]
+
+
+add("mov_dpp row_ror:8 bank 0xc", dpp_mov("row_ror:8 row_mask:0xf bank_mask:0xc"))
+add("mov_dpp row_shl:4 bank 0x5", dpp_mov("row_shl:4 row_mask:0xf bank_mask:0x5"))
+add("mov_dpp quad_perm", dpp_mov("quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf bound_ctrl:1"))
+add("mov plain (for comparison)", [f"v_mov_b32 v{16 + i}, v{bank_reg(32, (i + 1) % 4, rep % 4)}" for rep in range(8) for i in range(8)])
+add("cndmask vcc", [f"v_cndmask_b32 v{16 + i}, v{16 + i}, v{bank_reg(32, (i + 1) % 4, rep % 4)}, vcc" for rep in range(8) for i in range(8)])
+add("permlane32_swap", [f"v_permlane32_swap_b32 v{16 + i}, v{32 + i}" for rep in range(8) for i in range(8)])
+add("permlane16_swap", [f"v_permlane16_swap_b32 v{16 + i}, v{32 + i}" for rep in range(8) for i in range(8)])
+
 out = ['#include <hip/hip_runtime.h>', '#include <cstdio>', '#include <cstdlib>',
        '#define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("HIP error %s at %s:%d\\n", hipGetErrorString(e), __FILE__, __LINE__); exit(1); } } while (0)']
 clob = ", ".join(f'"v{r}"' for r in range(16, 48))
 init = "\\n ".join(f"v_mov_b32 v{r}, %0" for r in range(16, 48))
+if len(sys.argv) > 2:  # only the tests whose label matches the second argument (a regular expression)
+    import re
+    TESTS = [t for t in TESTS if re.search(sys.argv[2], t[0])]
 for idx, (label, insts) in enumerate(TESTS):
     body = "\\n ".join(insts)
     out.append(f'''__global__ void __launch_bounds__(256) k{idx}(unsigned *out, int iters) {{
@@ -158,8 +179,8 @@ out.append('''template <class K> double run(K kern, int wps) {
     return ms * 1e-3 * 2.4e9 / ((double)iters * 64 * wps);
 }
 int main() {
-    printf("%-28s %8s %8s %8s %8s   (cycles per wave-instruction per SIMD at 2.4 GHz nominal)\\n", "test", "1 w/SIMD", "2 w/SIMD", "4 w/SIMD", "8 w/SIMD");''')
+    printf("%-30s %8s %8s %8s %8s   (cycles per wave-instruction per SIMD at 2.4 GHz nominal)\\n", "test", "1 w/SIMD", "2 w/SIMD", "4 w/SIMD", "8 w/SIMD");''')
 for idx, (label, _) in enumerate(TESTS):
-    out.append(f'    printf("%-28s %8.2f %8.2f %8.2f %8.2f\\n", "{label}", run(k{idx}, 1), run(k{idx}, 2), run(k{idx}, 4), run(k{idx}, 8));')
+    out.append(f'    printf("%-30s %8.2f %8.2f %8.2f %8.2f\\n", "{label}", run(k{idx}, 1), run(k{idx}, 2), run(k{idx}, 4), run(k{idx}, 8));')
 out.append("    return 0;\n}")
 open(sys.argv[1] if len(sys.argv) > 1 else "build/bank_probe_gen.hip", "w").write("\n".join(out) + "\n")
