@@ -47,6 +47,9 @@ SYMBOLS = [
     "circl_hip_ed25519_workspace_size", "circl_hip_ed25519_keygen", "circl_hip_ed25519_sign", "circl_hip_ed25519_verify",
     "circl_hip_ed25519_keygen_dev", "circl_hip_ed25519_sign_dev", "circl_hip_ed25519_verify_dev", "circl_hip_sha512",
     "circl_hip_eddilithium2_keygen", "circl_hip_eddilithium2_sign", "circl_hip_eddilithium2_verify",
+    "circl_hip_x448", "circl_hip_x448_dev", "circl_hip_ed448_workspace_size", "circl_hip_ed448_keygen", "circl_hip_ed448_sign",
+    "circl_hip_ed448_verify", "circl_hip_ed448_keygen_dev", "circl_hip_ed448_sign_dev", "circl_hip_ed448_verify_dev",
+    "circl_hip_eddilithium3_keygen", "circl_hip_eddilithium3_sign", "circl_hip_eddilithium3_verify",
 ]
 
 OK, EPARAM, ENODEV, EHIP, ENOMEM, EWORKSPACE, EBUSY, EAGAIN = 0, -1, -2, -3, -4, -5, -6, -7
@@ -204,6 +207,19 @@ def lib():
         L.circl_hip_eddilithium2_keygen.argtypes = [vp, vp, vp, sz, i]
         L.circl_hip_eddilithium2_sign.argtypes = [vp, vp, vp, vp, sz, i]
         L.circl_hip_eddilithium2_verify.argtypes = [vp, vp, vp, vp, vp, sz, i]
+        L.circl_hip_x448.argtypes = [vp, vp, vp, vp, sz, i]
+        L.circl_hip_x448_dev.argtypes = [vp, vp, vp, vp, sz, vp]
+        L.circl_hip_ed448_workspace_size.restype = sz
+        L.circl_hip_ed448_workspace_size.argtypes = [sz]
+        L.circl_hip_ed448_keygen.argtypes = [vp, vp, vp, sz, i]
+        L.circl_hip_ed448_sign.argtypes = [vp, vp, vp, vp, vp, vp, sz, i]
+        L.circl_hip_ed448_verify.argtypes = [vp, vp, vp, vp, vp, vp, vp, sz, i]
+        L.circl_hip_ed448_keygen_dev.argtypes = [vp, vp, vp, sz, vp, sz, vp]
+        L.circl_hip_ed448_sign_dev.argtypes = [vp, vp, vp, vp, vp, vp, sz, vp, sz, vp]
+        L.circl_hip_ed448_verify_dev.argtypes = [vp, vp, vp, vp, vp, vp, vp, sz, vp, sz, vp]
+        L.circl_hip_eddilithium3_keygen.argtypes = [vp, vp, vp, sz, i]
+        L.circl_hip_eddilithium3_sign.argtypes = [vp, vp, vp, vp, sz, i]
+        L.circl_hip_eddilithium3_verify.argtypes = [vp, vp, vp, vp, vp, sz, i]
         for f in ("seed", "eseed", "pk", "sk", "ct", "ss"):
             fn = getattr(L, "circl_hip_hybrid_%s_size" % f)
             fn.restype, fn.argtypes = sz, [i]

@@ -14,7 +14,8 @@ DSA_SIZES = {44: (1312, 2560, 2420), 65: (1952, 4032, 3309), 87: (2592, 4896, 46
              2: (1312, 2528, 2420), 3: (1952, 4000, 3293), 5: (2592, 4864, 4595)}
 KERNELS = {"mlkem_hash": 0, "mlkem_encrypt": 1, "mlkem_decrypt": 2, "mlkem_keygen": 3, "mlkem_finish": 4,
            "mldsa_hash": 5, "mldsa_verify": 6, "mldsa_keygen": 7, "mldsa_sign": 8, "mlkem_keytable": 9, "mldsa_keytable": 10, "x25519": 11,
-           "ed25519_keygen": 12, "ed25519_sign": 13, "ed25519_verify": 14, "sha512": 15}
+           "ed25519_keygen": 12, "ed25519_sign": 13, "ed25519_verify": 14, "sha512": 15,
+           "x448": 16, "ed448_keygen": 17, "ed448_sign": 18, "ed448_verify": 19}
 
 
 def _stream():

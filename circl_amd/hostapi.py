@@ -787,3 +787,95 @@ def eddilithium2_sign(sk, msgs, device=0):
 def eddilithium2_verify(pk, sig, msgs, device=0):
     """Verify(pk_i, msg_i, sig_i) -> ok (n,): both halves must verify; wrong lengths are false without a launch"""
     return _verify_fixed(nat.lib().circl_hip_eddilithium2_verify, pk, sig, msgs, 1344, 2484, "eddilithium2_verify", device)
+
+
+def x448(scalar, point=None, device=0):
+    """Batch X448 (dh/x448): Shared(scalar_i, point_i), or KeyGen(scalar_i) when point is None.
+    Returns (out (n, 56), ok (n,)): ok = 0 where the reference's Shared reports a low-order public key."""
+    scalar = _u8(scalar, 56)
+    n = scalar.shape[0]
+    out = np.empty((n, 56), np.uint8)
+    ok = np.empty(n, np.uint8)
+    pt = None if point is None else _u8(point, 56)
+    nat.check(nat.lib().circl_hip_x448(_p(scalar), None if pt is None else _p(pt), _p(out), _p(ok), n, device), "x448")
+    return out, ok
+
+
+def ed448_keygen(seeds, device=0):
+    """sign/ed448 NewKeyFromSeed for every 57-byte seed -> (pk (n, 57), sk (n, 114) = seed || pk)"""
+    seeds = _u8(seeds, 57)
+    n = seeds.shape[0]
+    pk, sk = np.empty((n, 57), np.uint8), np.empty((n, 114), np.uint8)
+    nat.check(nat.lib().circl_hip_ed448_keygen(_p(seeds), _p(pk), _p(sk), n, device), "ed448_keygen")
+    return pk, sk
+
+
+def _ctx_args(ctxs, n):
+    """(blob pointer, offsets pointer, keep-alive) for a list of n contexts, or NULLs for None (every context empty)"""
+    if ctxs is None:
+        return None, None, None
+    assert len(ctxs) == n
+    cb, co = _blob(ctxs)
+    return _p(cb), _p(co), (cb, co)
+
+
+def ed448_sign(sk, msgs, ctxs=None, device=0):
+    """Sign(sk_i, msg_i, ctx_i) -> (n, 114); ctxs=None: every context empty.  A context over 255 bytes raises (the reference
+    panics)."""
+    sk = _u8(sk, 114)
+    n = sk.shape[0]
+    assert len(msgs) == n
+    mb, mo = _blob(msgs)
+    cb, co, _keep = _ctx_args(ctxs, n)
+    sig = np.empty((n, 114), np.uint8)
+    nat.check(nat.lib().circl_hip_ed448_sign(_p(sk), _p(mb), _p(mo), cb, co, _p(sig), n, device), "ed448_sign")
+    return sig
+
+
+def ed448_verify(pk, sig, msgs, ctxs=None, device=0):
+    """Verify(pk_i, msg_i, sig_i, ctx_i) -> ok (n,) of 0 / 1; pk and sig are sequences of byte strings or (n, 57) / (n, 114)
+    arrays; ctxs=None: every context empty.  Wrong-length keys or signatures are false without a launch; a context over 255 bytes
+    is false."""
+    n = len(msgs)
+    pk_i, pk_l = _rows_of_length(pk, 57)
+    sig_i, sig_l = _rows_of_length(sig, 114)
+    assert len(pk_l) == n and len(sig_l) == n and (ctxs is None or len(ctxs) == n)
+    idx = sorted(set(pk_i) & set(sig_i))
+    ok = np.zeros(n, np.uint8)
+    if idx:
+        pka = np.frombuffer(b"".join(pk_l[i] for i in idx), np.uint8).reshape(-1, 57).copy()
+        sga = np.frombuffer(b"".join(sig_l[i] for i in idx), np.uint8).reshape(-1, 114).copy()
+        mb, mo = _blob([msgs[i] for i in idx])
+        cb, co, _keep = _ctx_args(None if ctxs is None else [ctxs[i] for i in idx], len(idx))
+        sub = np.empty(len(idx), np.uint8)
+        nat.check(nat.lib().circl_hip_ed448_verify(_p(pka), _p(sga), _p(mb), _p(mo), cb, co, _p(sub), len(idx), device), "ed448_verify")
+        ok[idx] = sub
+    return ok
+
+
+EDDILITHIUM3_SIZES = dict(seed=57, pk=2009, sk=4057, sig=3407)
+
+
+def eddilithium3_keygen(seeds, device=0):
+    """sign/eddilithium3 NewKeyFromSeed for every 57-byte seed -> (pk (n, 2009), sk (n, 4057))"""
+    seeds = _u8(seeds, 57)
+    n = seeds.shape[0]
+    pk, sk = np.empty((n, 2009), np.uint8), np.empty((n, 4057), np.uint8)
+    nat.check(nat.lib().circl_hip_eddilithium3_keygen(_p(seeds), _p(pk), _p(sk), n, device), "eddilithium3_keygen")
+    return pk, sk
+
+
+def eddilithium3_sign(sk, msgs, device=0):
+    """SignTo(sk_i, msg_i) -> (n, 3407) = deterministic Dilithium3 signature || Ed448 signature (empty context)"""
+    sk = _u8(sk, 4057)
+    n = sk.shape[0]
+    assert len(msgs) == n
+    mb, mo = _blob(msgs)
+    sig = np.empty((n, 3407), np.uint8)
+    nat.check(nat.lib().circl_hip_eddilithium3_sign(_p(sk), _p(mb), _p(mo), _p(sig), n, device), "eddilithium3_sign")
+    return sig
+
+
+def eddilithium3_verify(pk, sig, msgs, device=0):
+    """Verify(pk_i, msg_i, sig_i) -> ok (n,): both halves must verify; wrong lengths are false without a launch"""
+    return _verify_fixed(nat.lib().circl_hip_eddilithium3_verify, pk, sig, msgs, 2009, 3407, "eddilithium3_verify", device)

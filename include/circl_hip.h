@@ -611,6 +611,69 @@ int circl_hip_eddilithium2_sign(const uint8_t *sk, const uint8_t *msg_blob, cons
 int circl_hip_eddilithium2_verify(const uint8_t *pk, const uint8_t *sig, const uint8_t *msg_blob, const uint64_t *msg_off, uint8_t *ok,
                                   size_t n, int device);
 
+/* ---- X448 (dh/x448, RFC 7748) -----------------------------------------------------------------------------------------
+ * Shared(shared, secret, public) (key.go:41-46) with point != NULL, KeyGen(public, secret) (key.go:33-35) with point == NULL
+ * (base point u = 5).  scalar, point, out are n rows of 56 bytes; the scalar is clamped (k[0] &= 252, k[55] |= 128,
+ * key.go:15-20).  ok[i] = 0 where Shared returns false: the point, reduced mod p = 2^448 - 2^224 - 1, is 0, 1 or p - 1
+ * (lowOrderPoints, curve.go:76; out[i] is then all zero), 1 otherwise; ok may be NULL.  One Montgomery ladder per lane for both
+ * (the reference's KeyGen is a Joye ladder over table.go; same bytes); device pointers 4-byte aligned. */
+int circl_hip_x448(const uint8_t *scalar, const uint8_t *point, uint8_t *out, uint8_t *ok, size_t n, int device);
+int circl_hip_x448_dev(const uint8_t *d_scalar, const uint8_t *d_point, uint8_t *d_out, uint8_t *d_ok, size_t n, void *stream);
+
+/* ---- Ed448 (sign/ed448, pure Ed448 of RFC 8032 5.2, with a context) -----------------------------------------------------
+ * One key / signature per item, each item with its own key, message and context; messages and contexts are ragged: item i's
+ * message is msg_blob[msg_off[i] .. msg_off[i+1]) and its context ctx_blob[ctx_off[i] .. ctx_off[i+1]) (n + 1 offsets each).
+ * ctx_blob == NULL: every context is empty (ctx_off is then ignored), as in circl_hip_k12 and the ML-DSA calls.
+ * circl_hip_ed448_keygen: NewKeyFromSeed(seed_i) (ed448.go).  pk[i] (57) = A = enc([s]B) with s = SHAKE256(seed, 114)[0..57)
+ *   clamped (h[0] &= 0xFC, h[55] |= 0x80, h[56] = 0); sk[i] (114) = seed (57) || A (57), the reference's PrivateKey.  pk or sk
+ *   may be NULL.
+ * circl_hip_ed448_sign: Sign(sk_i, msg_i, ctx_i) (ed448.go signAll, no pre-hash).  sig[i] (114) = R (57) || S (57, little-endian,
+ *   below l, byte 56 zero): dom4 = "SigEd448" || 0x00 || len(ctx) || ctx, r = SHAKE256(dom4 || prefix || M, 114) mod l with
+ *   prefix = SHAKE256(seed, 114)[57..114), R = enc([r]B), k = SHAKE256(dom4 || R || sk[57..114) || M, 114) mod l, S = r + k s mod
+ *   l.  The second half of sk is hashed AS STORED, as in the reference.  A context over 255 bytes: CIRCL_HIP_EPARAM before any
+ *   launch (the reference panics); the _dev form, which cannot see the offsets, writes an all-zero signature for that item.
+ * circl_hip_ed448_verify: Verify(pk_i, msg_i, sig_i, ctx_i) (ed448.go:294-339).  ok[i] = 1 iff the context is at most 255 bytes,
+ *   S < l with byte 56 zero (isLessThanOrder), pk decodes (ecc/goldilocks point.go:43-80: low seven bits of byte 56 zero, y < p,
+ *   x exists, not x = 0 with the sign bit set) and enc(Q) equals the 57 bytes of R, where Q is what goldilocks.Curve.
+ *   CombinedMult(S, k, -A) returns (curve.go:80-90): 4 ([S/4 mod l]B + [k/4 mod l](-A)), k = SHAKE256(dom4 || R || pk || M, 114)
+ *   mod l.  That is [S]B - [k]A with A's 4-torsion component dropped: neither the cofactorless nor RFC 8032's cofactored check;
+ *   item by item, every ok[i] is the reference's verdict.  The ABI takes 57-byte keys and 114-byte signatures; other lengths are
+ *   the caller's to reject (the reference returns false).  SupportsContext() == true; Ed448ph is not provided.
+ * _dev forms: device pointers, any stream; the 57- and 114-byte rows need no alignment (they are READ as the aligned 4-byte
+ *   words that hold them, so up to 3 bytes before and after a row's buffer are touched and masked off; writes are exact), offsets
+ *   8-byte aligned.  Verification
+ *   needs circl_hip_ed448_workspace_size(n) bytes of workspace (public multiples of the keys, 4-byte aligned); key generation
+ *   and signing keep their secrets (seed, s, prefix, r) in registers and leave the workspace untouched (it may be NULL).  The
+ *   host forms wipe the device staging of seeds and private keys. */
+size_t circl_hip_ed448_workspace_size(size_t n);
+int circl_hip_ed448_keygen(const uint8_t *seed57, uint8_t *pk57, uint8_t *sk114, size_t n, int device);
+int circl_hip_ed448_sign(const uint8_t *sk114, const uint8_t *msg_blob, const uint64_t *msg_off, const uint8_t *ctx_blob,
+                         const uint64_t *ctx_off, uint8_t *sig114, size_t n, int device);
+int circl_hip_ed448_verify(const uint8_t *pk57, const uint8_t *sig114, const uint8_t *msg_blob, const uint64_t *msg_off,
+                           const uint8_t *ctx_blob, const uint64_t *ctx_off, uint8_t *ok, size_t n, int device);
+int circl_hip_ed448_keygen_dev(const uint8_t *d_seed57, uint8_t *d_pk57, uint8_t *d_sk114, size_t n, void *d_workspace,
+                               size_t workspace_bytes, void *stream);
+int circl_hip_ed448_sign_dev(const uint8_t *d_sk114, const uint8_t *d_msg_blob, const uint64_t *d_msg_off, const uint8_t *d_ctx_blob,
+                             const uint64_t *d_ctx_off, uint8_t *d_sig114, size_t n, void *d_workspace, size_t workspace_bytes,
+                             void *stream);
+int circl_hip_ed448_verify_dev(const uint8_t *d_pk57, const uint8_t *d_sig114, const uint8_t *d_msg_blob, const uint64_t *d_msg_off,
+                               const uint8_t *d_ctx_blob, const uint64_t *d_ctx_off, uint8_t *d_ok, size_t n, void *d_workspace,
+                               size_t workspace_bytes, void *stream);
+
+/* ---- Ed448-Dilithium3 (sign/eddilithium3/eddilithium.go): round-3 Dilithium3 (sign/dilithium/mode3) next to Ed448 -------
+ * circl_hip_eddilithium3_keygen: NewKeyFromSeed(seed_i) (57 bytes): SHAKE256(seed) -> 32 bytes for mode3, then 57 for Ed448.
+ *   pk[i] (2009) = mode3 pk (1952) || Ed448 pk (57); sk[i] (4057) = mode3 sk (4000) || the Ed448 SEED (57).
+ * circl_hip_eddilithium3_sign: SignTo: sig[i] (3407) = the deterministic mode3 signature (3293) || the Ed448 signature (114) of
+ *   the same message under the empty context, the Ed448 key re-derived from the seed in sk (Unpack).
+ * circl_hip_eddilithium3_verify: Verify: ok[i] = 1 iff both halves verify.  A signature of any other length than 3407 bytes is
+ *   false in the reference; the ABI takes 3407-byte rows, so that check is the caller's.
+ * No context (SupportsContext() == false).  Both halves run on the device, on one stream per chunk, with no host round trip
+ * between them; the device staging and workspace of keygen and sign (both private keys) are zeroed after every chunk. */
+int circl_hip_eddilithium3_keygen(const uint8_t *seed57, uint8_t *pk, uint8_t *sk, size_t n, int device);
+int circl_hip_eddilithium3_sign(const uint8_t *sk, const uint8_t *msg_blob, const uint64_t *msg_off, uint8_t *sig, size_t n, int device);
+int circl_hip_eddilithium3_verify(const uint8_t *pk, const uint8_t *sig, const uint8_t *msg_blob, const uint64_t *msg_off, uint8_t *ok,
+                                  size_t n, int device);
+
 /* ---- hybrid KEMs around ML-KEM-768, composed on the device -------------------------------
  * scheme = CIRCL_HIP_HYBRID_XWING: kem/xwing/xwing.go -- DeriveKeyPairPacked (:98-144), EncapsulateTo (:223-265),
  *   DecapsulateTo (:270-299), combiner (:53-71).  seed 32, eseed 64 (seedm || ekx), pk 1216 (ek || pk_X), sk 32 (the
@@ -687,7 +750,11 @@ int circl_hip_hybrid_decaps_table_dev(const circl_hip_keytable *table, const uin
 #define CIRCL_HIP_KERNEL_ED25519_SIGN 13   /* Ed25519 Sign                             */
 #define CIRCL_HIP_KERNEL_ED25519_VERIFY 14 /* Ed25519 Verify                           */
 #define CIRCL_HIP_KERNEL_SHA512 15         /* batch SHA-512                            */
-#define CIRCL_HIP_KERNEL_COUNT 16
+#define CIRCL_HIP_KERNEL_X448 16           /* X448 ladder                              */
+#define CIRCL_HIP_KERNEL_ED448_KEYGEN 17   /* Ed448 NewKeyFromSeed                     */
+#define CIRCL_HIP_KERNEL_ED448_SIGN 18     /* Ed448 Sign                               */
+#define CIRCL_HIP_KERNEL_ED448_VERIFY 19   /* Ed448 Verify                             */
+#define CIRCL_HIP_KERNEL_COUNT 20
 int circl_hip_profile_enable(int on);
 int circl_hip_profile_read(int kernel, double *total_ms, uint64_t *launches);
 /* The VALU issue rates this chip sustains, measured live (bench.py prices the kernels' VALU time against them instead of against
