@@ -50,6 +50,8 @@ SYMBOLS = [
     "circl_hip_x448", "circl_hip_x448_dev", "circl_hip_ed448_workspace_size", "circl_hip_ed448_keygen", "circl_hip_ed448_sign",
     "circl_hip_ed448_verify", "circl_hip_ed448_keygen_dev", "circl_hip_ed448_sign_dev", "circl_hip_ed448_verify_dev",
     "circl_hip_eddilithium3_keygen", "circl_hip_eddilithium3_sign", "circl_hip_eddilithium3_verify",
+    "circl_hip_frodo640shake_workspace_size", "circl_hip_frodo640shake_keygen", "circl_hip_frodo640shake_encaps", "circl_hip_frodo640shake_decaps",
+    "circl_hip_frodo640shake_keygen_dev", "circl_hip_frodo640shake_encaps_dev", "circl_hip_frodo640shake_decaps_dev",
 ]
 
 OK, EPARAM, ENODEV, EHIP, ENOMEM, EWORKSPACE, EBUSY, EAGAIN = 0, -1, -2, -3, -4, -5, -6, -7
@@ -220,6 +222,14 @@ def lib():
         L.circl_hip_eddilithium3_keygen.argtypes = [vp, vp, vp, sz, i]
         L.circl_hip_eddilithium3_sign.argtypes = [vp, vp, vp, vp, sz, i]
         L.circl_hip_eddilithium3_verify.argtypes = [vp, vp, vp, vp, vp, sz, i]
+        L.circl_hip_frodo640shake_workspace_size.restype = sz
+        L.circl_hip_frodo640shake_workspace_size.argtypes = [sz]
+        L.circl_hip_frodo640shake_keygen.argtypes = [vp, vp, vp, sz, i]
+        L.circl_hip_frodo640shake_encaps.argtypes = [vp, vp, vp, vp, sz, i]
+        L.circl_hip_frodo640shake_decaps.argtypes = [vp, vp, vp, sz, i]
+        L.circl_hip_frodo640shake_keygen_dev.argtypes = [vp, vp, vp, sz, vp, sz, vp]
+        L.circl_hip_frodo640shake_encaps_dev.argtypes = [vp, vp, vp, vp, sz, vp, sz, vp]
+        L.circl_hip_frodo640shake_decaps_dev.argtypes = [vp, vp, vp, sz, vp, sz, vp]
         for f in ("seed", "eseed", "pk", "sk", "ct", "ss"):
             fn = getattr(L, "circl_hip_hybrid_%s_size" % f)
             fn.restype, fn.argtypes = sz, [i]

@@ -15,7 +15,8 @@ DSA_SIZES = {44: (1312, 2560, 2420), 65: (1952, 4032, 3309), 87: (2592, 4896, 46
 KERNELS = {"mlkem_hash": 0, "mlkem_encrypt": 1, "mlkem_decrypt": 2, "mlkem_keygen": 3, "mlkem_finish": 4,
            "mldsa_hash": 5, "mldsa_verify": 6, "mldsa_keygen": 7, "mldsa_sign": 8, "mlkem_keytable": 9, "mldsa_keytable": 10, "x25519": 11,
            "ed25519_keygen": 12, "ed25519_sign": 13, "ed25519_verify": 14, "sha512": 15,
-           "x448": 16, "ed448_keygen": 17, "ed448_sign": 18, "ed448_verify": 19}
+           "x448": 16, "ed448_keygen": 17, "ed448_sign": 18, "ed448_verify": 19,
+           "frodo_keygen": 20, "frodo_encaps": 21, "frodo_decaps": 22}
 
 
 def _stream():
@@ -281,3 +282,34 @@ def x25519(scalar, point=None, out=None, ok=None):
     nat.check(nat.lib().circl_hip_x25519_dev(_chk(scalar, 32), None if point is None else _chk(point, 32), _chk(out, 32), _chk(ok), n, _stream()),
               "x25519_dev")
     return out, ok
+
+
+class FrodoDevice:
+    """FrodoKEM-640-SHAKE on resident tensors (circl_hip_frodo640shake_*_dev), on torch's current stream."""
+    PK, SK, CT, SS, SEED, ESEED = 9616, 19888, 9720, 16, 48, 16
+
+    def __init__(self, n, device="cuda"):
+        self.n = n
+        self.L = nat.lib()
+        self.wsb = self.L.circl_hip_frodo640shake_workspace_size(n)
+        self.ws = torch.empty(max(self.wsb, 256), dtype=torch.uint8, device=device)
+        self.pk = torch.empty((n, self.PK), dtype=torch.uint8, device=device)
+        self.sk = torch.empty((n, self.SK), dtype=torch.uint8, device=device)
+        self.ct = torch.empty((n, self.CT), dtype=torch.uint8, device=device)
+        self.ss = torch.empty((n, self.SS), dtype=torch.uint8, device=device)
+        self.ss2 = torch.empty((n, self.SS), dtype=torch.uint8, device=device)
+
+    def keygen(self, seeds):
+        nat.check(self.L.circl_hip_frodo640shake_keygen_dev(_chk(seeds, self.SEED), _chk(self.pk), _chk(self.sk), self.n, self.ws.data_ptr(), self.wsb,
+                                                            _stream()), "frodo640shake_keygen_dev")
+        return self.pk, self.sk
+
+    def encaps(self, pk, eseeds):
+        nat.check(self.L.circl_hip_frodo640shake_encaps_dev(_chk(pk, self.PK), _chk(eseeds, self.ESEED), _chk(self.ct), _chk(self.ss), self.n,
+                                                            self.ws.data_ptr(), self.wsb, _stream()), "frodo640shake_encaps_dev")
+        return self.ct, self.ss
+
+    def decaps(self, sk, ct):
+        nat.check(self.L.circl_hip_frodo640shake_decaps_dev(_chk(sk, self.SK), _chk(ct, self.CT), _chk(self.ss2), self.n, self.ws.data_ptr(), self.wsb,
+                                                            _stream()), "frodo640shake_decaps_dev")
+        return self.ss2

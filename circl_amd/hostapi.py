@@ -879,3 +879,53 @@ def eddilithium3_sign(sk, msgs, device=0):
 def eddilithium3_verify(pk, sig, msgs, device=0):
     """Verify(pk_i, msg_i, sig_i) -> ok (n,): both halves must verify; wrong lengths are false without a launch"""
     return _verify_fixed(nat.lib().circl_hip_eddilithium3_verify, pk, sig, msgs, 2009, 3407, "eddilithium3_verify", device)
+
+
+FRODO640SHAKE_SIZES = dict(pk=9616, sk=19888, ct=9720, ss=16, seed=48, eseed=16)
+
+
+def _frodo_rows(x, cols, what):
+    """an (n, cols) uint8 array from a 2-D array or a sequence of byte strings; any row of another length is refused here, before
+    anything is launched (the reference panics or returns kem.ErrCiphertextSize / ErrSeedSize, frodo.go:517-547)"""
+    if isinstance(x, np.ndarray):
+        if x.ndim != 2 or x.shape[1] != cols:
+            raise ValueError("frodo640shake: %s must be rows of %d bytes, got shape %r" % (what, cols, x.shape))
+        return np.ascontiguousarray(x, dtype=np.uint8)
+    items = [x] if isinstance(x, (bytes, bytearray, memoryview)) else list(x)
+    for it in items:
+        if len(it) != cols:
+            raise ValueError("frodo640shake: %s must be %d bytes, got %d" % (what, cols, len(it)))
+    return np.frombuffer(b"".join(bytes(it) for it in items), np.uint8).reshape(len(items), cols).copy()
+
+
+def frodo640shake_keygen(seeds, device=0):
+    """kem/frodo/frodo640shake DeriveKeyPair for every 48-byte seed (s || seedSE || z) -> (pk (n, 9616), sk (n, 19888))"""
+    seeds = _frodo_rows(seeds, 48, "a key seed")
+    n = seeds.shape[0]
+    pk, sk = np.empty((n, 9616), np.uint8), np.empty((n, 19888), np.uint8)
+    nat.check(nat.lib().circl_hip_frodo640shake_keygen(_p(seeds), _p(pk), _p(sk), n, device), "frodo640shake_keygen")
+    return pk, sk
+
+
+def frodo640shake_encaps(pk, seeds, device=0):
+    """EncapsulateDeterministically(pk_i, seed_i) (16-byte seeds) -> (ct (n, 9720), ss (n, 16))"""
+    pk = _frodo_rows(pk, 9616, "a public key")
+    seeds = _frodo_rows(seeds, 16, "an encapsulation seed")
+    n = pk.shape[0]
+    if seeds.shape[0] != n:
+        raise ValueError("frodo640shake: %d public keys, %d seeds" % (n, seeds.shape[0]))
+    ct, ss = np.empty((n, 9720), np.uint8), np.empty((n, 16), np.uint8)
+    nat.check(nat.lib().circl_hip_frodo640shake_encaps(_p(pk), _p(seeds), _p(ct), _p(ss), n, device), "frodo640shake_encaps")
+    return ct, ss
+
+
+def frodo640shake_decaps(sk, ct, device=0):
+    """Decapsulate(sk_i, ct_i) -> ss (n, 16); a ciphertext that does not re-encrypt gives SHAKE128(ct || s), as in the reference"""
+    sk = _frodo_rows(sk, 19888, "a private key")
+    ct = _frodo_rows(ct, 9720, "a ciphertext")
+    n = sk.shape[0]
+    if ct.shape[0] != n:
+        raise ValueError("frodo640shake: %d private keys, %d ciphertexts" % (n, ct.shape[0]))
+    ss = np.empty((n, 16), np.uint8)
+    nat.check(nat.lib().circl_hip_frodo640shake_decaps(_p(sk), _p(ct), _p(ss), n, device), "frodo640shake_decaps")
+    return ss

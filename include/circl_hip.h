@@ -674,6 +674,43 @@ int circl_hip_eddilithium3_sign(const uint8_t *sk, const uint8_t *msg_blob, cons
 int circl_hip_eddilithium3_verify(const uint8_t *pk, const uint8_t *sig, const uint8_t *msg_blob, const uint64_t *msg_off, uint8_t *ok,
                                   size_t n, int device);
 
+/* ---- FrodoKEM-640-SHAKE (kem/frodo/frodo640shake): N = 640, nbar = 8, q = 2^15, B = 2 ------------------------------------
+ * circl_hip_frodo640shake_keygen: newKeyFromSeed(seed_i) (48 bytes = s || seedSE || z): seedA = SHAKE128(z)[:16],
+ *   S^T || E sampled from SHAKE128(0x5F || seedSE), B = A S + E; pk[i] (9616) = seedA || pack15(B); sk[i] (19888) = s || pk ||
+ *   S^T as 16-bit little-endian words || SHAKE128(pk)[:16].
+ * circl_hip_frodo640shake_encaps: EncapsulateTo(pk_i, seed_i) (16 bytes = mu): ct[i] (9720) = pack15(S'A + E') ||
+ *   pack15(S'B + E'' + encode(mu)), ss[i] (16) = SHAKE128(ct || k)[:16].
+ * circl_hip_frodo640shake_decaps: DecapsulateTo: mu' from C - B'S, re-encryption to the pk stored in sk with the hpk stored in
+ *   sk, ss[i] = SHAKE128(ct || k') when both halves match and SHAKE128(ct || s) otherwise, chosen without a branch.
+ * The keys are taken as stored, as the reference takes them: A's words are raw 16-bit SHAKE output, arithmetic is mod 2^16 with
+ *   the 15-bit mask only where the reference has it, the S words of a private key are arbitrary uint16, and neither the stored
+ *   hpk nor the key's own consistency is checked.  The ABI takes rows of the six sizes below; other lengths are the caller's to
+ *   reject (the reference panics or returns kem.ErrCiphertextSize).
+ * A (800 KB per item) is never stored: its 640 SHAKE128 rows are squeezed and consumed inside the matrix kernel.
+ * _dev forms: device pointers, any stream.  The key, ciphertext, seed and secret rows need NO alignment: they are read as the
+ *   aligned 4-byte words that hold them (up to 3 bytes before and after a row's buffer are touched and masked off) and written
+ *   byte by byte.  The workspace (S', E', E'', mu', k', the re-encryption -- all secret) is
+ *   circl_hip_frodo640shake_workspace_size(n) bytes, 16-byte aligned, the same for the three calls and monotone in n; every
+ *   call zeroes it on the stream behind its kernels.  The host forms also wipe the device staging of every chunk.
+ * Errors: CIRCL_HIP_ENODEV without a device, CIRCL_HIP_EPARAM for a NULL pointer, CIRCL_HIP_EWORKSPACE for a short or misaligned
+ *   workspace; n = 0 is CIRCL_HIP_OK. */
+#define CIRCL_HIP_FRODO640SHAKE_PK_BYTES 9616
+#define CIRCL_HIP_FRODO640SHAKE_SK_BYTES 19888
+#define CIRCL_HIP_FRODO640SHAKE_CT_BYTES 9720
+#define CIRCL_HIP_FRODO640SHAKE_SS_BYTES 16
+#define CIRCL_HIP_FRODO640SHAKE_KEYSEED_BYTES 48
+#define CIRCL_HIP_FRODO640SHAKE_ENCSEED_BYTES 16
+size_t circl_hip_frodo640shake_workspace_size(size_t n);
+int circl_hip_frodo640shake_keygen(const uint8_t *seed48, uint8_t *pk, uint8_t *sk, size_t n, int device);
+int circl_hip_frodo640shake_encaps(const uint8_t *pk, const uint8_t *seed16, uint8_t *ct, uint8_t *ss, size_t n, int device);
+int circl_hip_frodo640shake_decaps(const uint8_t *sk, const uint8_t *ct, uint8_t *ss, size_t n, int device);
+int circl_hip_frodo640shake_keygen_dev(const uint8_t *d_seed48, uint8_t *d_pk, uint8_t *d_sk, size_t n, void *d_workspace,
+                                       size_t workspace_bytes, void *stream);
+int circl_hip_frodo640shake_encaps_dev(const uint8_t *d_pk, const uint8_t *d_seed16, uint8_t *d_ct, uint8_t *d_ss, size_t n,
+                                       void *d_workspace, size_t workspace_bytes, void *stream);
+int circl_hip_frodo640shake_decaps_dev(const uint8_t *d_sk, const uint8_t *d_ct, uint8_t *d_ss, size_t n, void *d_workspace,
+                                       size_t workspace_bytes, void *stream);
+
 /* ---- hybrid KEMs around ML-KEM-768, composed on the device -------------------------------
  * scheme = CIRCL_HIP_HYBRID_XWING: kem/xwing/xwing.go -- DeriveKeyPairPacked (:98-144), EncapsulateTo (:223-265),
  *   DecapsulateTo (:270-299), combiner (:53-71).  seed 32, eseed 64 (seedm || ekx), pk 1216 (ek || pk_X), sk 32 (the
@@ -754,7 +791,10 @@ int circl_hip_hybrid_decaps_table_dev(const circl_hip_keytable *table, const uin
 #define CIRCL_HIP_KERNEL_ED448_KEYGEN 17   /* Ed448 NewKeyFromSeed                     */
 #define CIRCL_HIP_KERNEL_ED448_SIGN 18     /* Ed448 Sign                               */
 #define CIRCL_HIP_KERNEL_ED448_VERIFY 19   /* Ed448 Verify                             */
-#define CIRCL_HIP_KERNEL_COUNT 20
+#define CIRCL_HIP_KERNEL_FRODO_KEYGEN 20   /* FrodoKEM-640-SHAKE KeyGen (three launches) */
+#define CIRCL_HIP_KERNEL_FRODO_ENCAPS 21   /* FrodoKEM-640-SHAKE Encaps                */
+#define CIRCL_HIP_KERNEL_FRODO_DECAPS 22   /* FrodoKEM-640-SHAKE Decaps                */
+#define CIRCL_HIP_KERNEL_COUNT 23
 int circl_hip_profile_enable(int on);
 int circl_hip_profile_read(int kernel, double *total_ms, uint64_t *launches);
 /* The VALU issue rates this chip sustains, measured live (bench.py prices the kernels' VALU time against them instead of against
