@@ -1,6 +1,6 @@
 // api_frodo.hip -- batch FrodoKEM-640-SHAKE (kem/frodo/frodo640shake) behind the C ABI (include/circl_hip.h).  No CPU compute path.
 #include "frodo_kernels.h"
-#include "host_common.h"
+#include "host_compose.h"
 
 using namespace circl::host;
 namespace fr = circl::frodo;
@@ -29,8 +29,6 @@ void launch_encaps_matrix(size_t n, hipStream_t st, const uint8_t *pk, size_t pk
     }
 }
 
-dim3 lanes_of(size_t n) { return dim3((unsigned)((n + 63) / 64)); }
-
 // a chunk's workspace: the noise rows, k, mu' and the re-encryption, each region 256-byte aligned; all of it is secret
 struct Ws {
     uint32_t *noise, *k, *mu, *ct2;
@@ -45,7 +43,7 @@ struct Ws {
 size_t ws_size(size_t n) { return up256(n * fr::kNoiseRow) + 2 * up256(n * 16) + up256(n * fr::kCt); }
 
 int check_ws(const void *ws, size_t bytes, size_t n) {
-    if (bytes < ws_size(n) || (reinterpret_cast<uintptr_t>(ws) & 15) != 0) return CIRCL_HIP_EWORKSPACE;
+    if (bytes < ws_size(n) || !aligned<16>(ws)) return CIRCL_HIP_EWORKSPACE;
     return CIRCL_HIP_OK;
 }
 
@@ -75,11 +73,11 @@ int circl_hip_frodo640shake_keygen_dev(const uint8_t *d_seed48, uint8_t *d_pk, u
     Ws w(d_workspace, n);
     {
         ProfScope ps(CIRCL_HIP_KERNEL_FRODO_KEYGEN, st);
-        hipLaunchKernelGGL(fr::frodo_keygen_pre_kernel, lanes_of(n), dim3(64), 0, st, d_seed48, d_pk, d_sk, w.noise, n);
+        hipLaunchKernelGGL(fr::frodo_keygen_pre_kernel, lanes_grid(n), dim3(64), 0, st, d_seed48, d_pk, d_sk, w.noise, n);
         HIP_TRY(hipGetLastError());
         launch_keygen_matrix(n, st, d_pk, d_sk, w.noise);
         HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(fr::frodo_keygen_post_kernel, lanes_of(n), dim3(64), 0, st, d_pk, d_sk, n);
+        hipLaunchKernelGGL(fr::frodo_keygen_post_kernel, lanes_grid(n), dim3(64), 0, st, d_pk, d_sk, n);
         HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipMemsetAsync(d_workspace, 0, ws_size(n), st));  // S, E
@@ -96,11 +94,11 @@ int circl_hip_frodo640shake_encaps_dev(const uint8_t *d_pk, const uint8_t *d_see
     Ws w(d_workspace, n);
     {
         ProfScope ps(CIRCL_HIP_KERNEL_FRODO_ENCAPS, st);
-        hipLaunchKernelGGL(fr::frodo_encaps_pre_kernel, lanes_of(n), dim3(64), 0, st, d_pk, d_seed16, w.noise, w.k, n);
+        hipLaunchKernelGGL(fr::frodo_encaps_pre_kernel, lanes_grid(n), dim3(64), 0, st, d_pk, d_seed16, w.noise, w.k, n);
         HIP_TRY(hipGetLastError());
         launch_encaps_matrix(n, st, d_pk, fr::kPk, d_seed16, w.noise, d_ct);
         HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(fr::frodo_ss_kernel<false>, lanes_of(n), dim3(64), 0, st, d_ss, d_ct, w.k, static_cast<const uint32_t *>(nullptr),
+        hipLaunchKernelGGL(fr::frodo_ss_kernel<false>, lanes_grid(n), dim3(64), 0, st, d_ss, d_ct, w.k, static_cast<const uint32_t *>(nullptr),
                            static_cast<const uint8_t *>(nullptr), n);
         HIP_TRY(hipGetLastError());
     }
@@ -118,12 +116,12 @@ int circl_hip_frodo640shake_decaps_dev(const uint8_t *d_sk, const uint8_t *d_ct,
     Ws w(d_workspace, n);
     {
         ProfScope ps(CIRCL_HIP_KERNEL_FRODO_DECAPS, st);
-        hipLaunchKernelGGL(fr::frodo_decaps_pre_kernel, lanes_of(n), dim3(64), 0, st, d_sk, d_ct, w.noise, w.k, w.mu, n);
+        hipLaunchKernelGGL(fr::frodo_decaps_pre_kernel, lanes_grid(n), dim3(64), 0, st, d_sk, d_ct, w.noise, w.k, w.mu, n);
         HIP_TRY(hipGetLastError());
         // re-encrypt mu' to the pk stored in the key
         launch_encaps_matrix(n, st, d_sk + fr::kSs, fr::kSk, reinterpret_cast<const uint8_t *>(w.mu), w.noise, reinterpret_cast<uint8_t *>(w.ct2));
         HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(fr::frodo_ss_kernel<true>, lanes_of(n), dim3(64), 0, st, d_ss, d_ct, w.k, w.ct2, d_sk, n);
+        hipLaunchKernelGGL(fr::frodo_ss_kernel<true>, lanes_grid(n), dim3(64), 0, st, d_ss, d_ct, w.k, w.ct2, d_sk, n);
         HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipMemsetAsync(d_workspace, 0, ws_size(n), st));  // S', E', E'', mu', k', the re-encryption

@@ -6,7 +6,7 @@
 // A call is a handful of launches per chunk over HBM-resident arrays: strided splits of the packed keys / ciphertexts,
 // seed expansion (SHAKE256, lane = item), the ML-KEM-768 batch kernels, two X25519 ladders per item (lane = item), the
 // combiner, strided joins.  Nothing is computed on the host.
-#include "host_common.h"
+#include "host_compose.h"
 #include "hybrid_kernels.h"
 #include "keytable.h"
 
@@ -64,43 +64,29 @@ bool desc_of(int scheme, Desc &d) {
     return true;
 }
 
-// temporaries of one call, carved from the caller's workspace in front of the lattice KEM's workspace
-struct Carve {
-    uint8_t *p;
-    uint8_t *take(size_t bytes) {
-        uint8_t *r = p;
-        p += (bytes + 255) & ~size_t(255);
-        return r;
-    }
-};
+// temporaries of one call, carved (Carve) from the caller's workspace in front of the lattice KEM's workspace
 size_t tmp_bytes(const Desc &d, size_t n) {  // upper bound over the three operations: ek, dk, ctm + a dozen 32/64-byte rows per item
-    auto r = [](size_t b) { return (b + 255) & ~size_t(255); };
-    return r(n * d.EK) + r(n * d.DK) + r(n * d.CTM) + 10 * r(n * 64) + r(n);
+    return up256(n * d.EK) + up256(n * d.DK) + up256(n * d.CTM) + 10 * up256(n * 64) + up256(n);
 }
 
-int copy_rows(hipStream_t st, void *dst, size_t dst_row, const void *src, size_t src_row, size_t width, size_t n) {
+// strided copy of word-aligned rows by a kernel (the composite signatures' byte-granular copy_rows_2d goes through the copy engine)
+int copy_rows_w32(hipStream_t st, void *dst, size_t dst_row, const void *src, size_t src_row, size_t width, size_t n) {
     const size_t total = n * (width / 4);
     if (total == 0) return CIRCL_HIP_OK;
-    hipLaunchKernelGGL(hk::rows_copy_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, static_cast<uint32_t *>(dst), dst_row / 4,
+    hipLaunchKernelGGL(hk::rows_copy_kernel, lanes_grid(total, 256), dim3(256), 0, st, static_cast<uint32_t *>(dst), dst_row / 4,
                        static_cast<const uint32_t *>(src), src_row / 4, (unsigned)(width / 4), n);
     HIP_TRY(hipGetLastError());
     return CIRCL_HIP_OK;
 }
 int zero_failed(hipStream_t st, void *dst, size_t row, const uint8_t *status, size_t n) {
     const size_t total = n * (row / 4);
-    hipLaunchKernelGGL(hk::rows_zero_failed_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, static_cast<uint32_t *>(dst), row / 4,
+    hipLaunchKernelGGL(hk::rows_zero_failed_kernel, lanes_grid(total, 256), dim3(256), 0, st, static_cast<uint32_t *>(dst), row / 4,
                        (unsigned)(row / 4), status, n);
     HIP_TRY(hipGetLastError());
     return CIRCL_HIP_OK;
 }
-#define TRY(expr)                          \
-    do {                                   \
-        const int rc_ = (expr);            \
-        if (rc_ != CIRCL_HIP_OK) return rc_; \
-    } while (0)
 inline const uint32_t *w(const uint8_t *p) { return reinterpret_cast<const uint32_t *>(p); }
 inline uint32_t *w(uint8_t *p) { return reinterpret_cast<uint32_t *>(p); }
-inline dim3 g256(size_t n) { return dim3((unsigned)((n + 255) / 256)); }
 
 // The secret temporaries of a call, zeroed on the call's stream on EVERY path: finish() on the way out of a successful call
 // (its failures are reported), the destructor behind any early error return.
@@ -122,11 +108,6 @@ struct SecretWipe {
     }
 };
 
-bool args_ok(const void *a, const void *b, const void *c, const void *d, const void *ws) {
-    return !((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c) | reinterpret_cast<uintptr_t>(d) |
-              reinterpret_cast<uintptr_t>(ws)) & 15);
-}
-
 int misaligned() {  // (the header's code for a misaligned device pointer; the message tells it from a short workspace)
     g_err = "hybrid _dev entry point: device pointers must be 16-byte aligned";
     return CIRCL_HIP_EWORKSPACE;
@@ -146,6 +127,44 @@ int kem_decaps(const Desc &d, const uint8_t *dk, const uint8_t *ct, uint8_t *ss,
     if (!d.r3) return circl_hip_mlkem_decaps_dev(d.param, dk, ct, ss, status, n, ws, wsb, st);
     HIP_TRY(hipMemsetAsync(status, 0, n, st));
     return circl_hip_kyber_decaps_dev(d.param, dk, ct, ss, n, ws, wsb, st);
+}
+
+// a packed row (a key, a ciphertext, a shared secret) is the lattice half and the 32 bytes of the X25519 half, either of them first
+int split_rows(hipStream_t st, const Desc &d, const uint8_t *packed, size_t row, uint8_t *kem, size_t kem_bytes, uint8_t *x, size_t n) {
+    TRY(copy_rows_w32(st, kem, kem_bytes, packed + d.kem_off(32), row, kem_bytes, n));
+    return copy_rows_w32(st, x, 32, packed + d.x_off(kem_bytes), row, 32, n);
+}
+int join_rows(hipStream_t st, const Desc &d, uint8_t *packed, size_t row, const uint8_t *kem, size_t kem_bytes, const uint8_t *x, size_t n) {
+    TRY(copy_rows_w32(st, packed + d.kem_off(32), row, kem, kem_bytes, kem_bytes, n));
+    return copy_rows_w32(st, packed + d.x_off(kem_bytes), row, x, 32, 32, n);
+}
+// the ephemeral seed of an encapsulation -> the lattice KEM's m and the X25519 scalar
+int expand_eseed(hipStream_t st, const Desc &d, const uint8_t *d_eseed, uint8_t *m, uint8_t *ekx, size_t n) {
+    if (d.xwing) {  // xwing.go:247-248: seedm = seed[:32], ekx = seed[32:]
+        TRY(copy_rows_w32(st, m, 32, d_eseed, 64, 32, n));
+        return copy_rows_w32(st, ekx, 32, d_eseed + 32, 64, 32, n);
+    }
+    if (d.x_first)
+        hipLaunchKernelGGL((hk::hybrid_expand_kernel<4, 4, true>), lanes_grid(n, 256), dim3(256), 0, st, w(d_eseed), w(m), w(ekx), n);
+    else
+        hipLaunchKernelGGL((hk::hybrid_expand_kernel<4, 4, false>), lanes_grid(n, 256), dim3(256), 0, st, w(d_eseed), w(m), w(ekx), n);
+    HIP_TRY(hipGetLastError());
+    return CIRCL_HIP_OK;
+}
+// the shared secret from its two halves: X-Wing's combiner (it reads the status only where the lattice half can fail per item: `combine_status`
+// is NULL in a decapsulation, and a low-order pk_X is not an error in X-Wing, xwing.go:251-254), or kem/hybrid's concatenation, zeroed
+// where either half failed
+int shared_secret(hipStream_t st, const Desc &d, const uint8_t *ssm, const uint8_t *ssx, const uint8_t *ctx, const uint8_t *pkx, const uint8_t *okx,
+                  uint8_t *d_status, const uint8_t *combine_status, uint8_t *d_ss, size_t n) {
+    if (d.xwing) {
+        hipLaunchKernelGGL(hk::xwing_combine_kernel, lanes_grid(n, 256), dim3(256), 0, st, w(ssm), w(ssx), w(ctx), w(pkx), combine_status, w(d_ss), n);
+        HIP_TRY(hipGetLastError());
+        return CIRCL_HIP_OK;
+    }
+    hipLaunchKernelGGL(hk::hybrid_status_kernel, lanes_grid(n, 256), dim3(256), 0, st, d_status, okx, n);
+    HIP_TRY(hipGetLastError());
+    TRY(join_rows(st, d, d_ss, 64, ssm, 32, ssx, n));
+    return zero_failed(st, d_ss, 64, d_status, n);
 }
 }  // namespace
 
@@ -174,7 +193,7 @@ int circl_hip_hybrid_keygen_dev(int scheme, const uint8_t *d_seed, uint8_t *d_pk
     if (n == 0) return CIRCL_HIP_OK;
     if (!d_seed || !d_pk || !d_sk || !d_ws) return CIRCL_HIP_EPARAM;
     if (ws_bytes < hybrid_ws_min(d, n)) return CIRCL_HIP_EWORKSPACE;
-    if (!args_ok(d_seed, d_pk, d_sk, nullptr, d_ws)) return misaligned();
+    if (!aligned<16>(d_seed, d_pk, d_sk, d_ws)) return misaligned();
     hipStream_t st = static_cast<hipStream_t>(stream);
     Carve c{static_cast<uint8_t *>(d_ws)};
     uint8_t *seedm = c.take(n * 64), *skx = c.take(n * 32), *pkx = c.take(n * 32), *ek = c.take(n * d.EK), *dk = c.take(n * d.DK);
@@ -183,21 +202,19 @@ int circl_hip_hybrid_keygen_dev(int scheme, const uint8_t *d_seed, uint8_t *d_pk
     SecretWipe wipe{st};  // nothing key-equivalent stays behind in the caller's workspace
     wipe.add(seedm, n * 64); wipe.add(skx, n * 32); wipe.add(dk, n * d.DK);
     if (d.xwing)
-        hipLaunchKernelGGL(hk::xwing_expand_kernel, g256(n), dim3(256), 0, st, w(d_seed), w(seedm), w(skx), n);
+        hipLaunchKernelGGL(hk::xwing_expand_kernel, lanes_grid(n, 256), dim3(256), 0, st, w(d_seed), w(seedm), w(skx), n);
     else if (d.x_first)
-        hipLaunchKernelGGL((hk::hybrid_expand_kernel<8, 8, true>), g256(n), dim3(256), 0, st, w(d_seed), w(seedm), w(skx), n);
+        hipLaunchKernelGGL((hk::hybrid_expand_kernel<8, 8, true>), lanes_grid(n, 256), dim3(256), 0, st, w(d_seed), w(seedm), w(skx), n);
     else
-        hipLaunchKernelGGL((hk::hybrid_expand_kernel<8, 8, false>), g256(n), dim3(256), 0, st, w(d_seed), w(seedm), w(skx), n);
+        hipLaunchKernelGGL((hk::hybrid_expand_kernel<8, 8, false>), lanes_grid(n, 256), dim3(256), 0, st, w(d_seed), w(seedm), w(skx), n);
     HIP_TRY(hipGetLastError());
     TRY(kem_keygen(d, seedm, ek, dk, n, kws, kws_bytes, st));
     TRY(circl_hip_x25519_dev(skx, nullptr, pkx, nullptr, n, st));
-    TRY(copy_rows(st, d_pk + d.kem_off(32), d.pk, ek, d.EK, d.EK, n));
-    TRY(copy_rows(st, d_pk + d.x_off(d.EK), d.pk, pkx, 32, 32, n));
+    TRY(join_rows(st, d, d_pk, d.pk, ek, d.EK, pkx, n));
     if (d.xwing) {
-        TRY(copy_rows(st, d_sk, 32, d_seed, 32, 32, n));  // the packed private key is the seed (xwing.go:156-163)
+        TRY(copy_rows_w32(st, d_sk, 32, d_seed, 32, 32, n));  // the packed private key is the seed (xwing.go:156-163)
     } else {
-        TRY(copy_rows(st, d_sk + d.kem_off(32), d.sk, dk, d.DK, d.DK, n));
-        TRY(copy_rows(st, d_sk + d.x_off(d.DK), d.sk, skx, 32, 32, n));
+        TRY(join_rows(st, d, d_sk, d.sk, dk, d.DK, skx, n));
     }
     return wipe.finish();
 }
@@ -210,7 +227,7 @@ int circl_hip_hybrid_encaps_dev(int scheme, const uint8_t *d_pk, const uint8_t *
     if (n == 0) return CIRCL_HIP_OK;
     if (!d_status || !d_pk || !d_eseed || !d_ct || !d_ss || !d_ws) return CIRCL_HIP_EPARAM;
     if (ws_bytes < hybrid_ws_min(d, n)) return CIRCL_HIP_EWORKSPACE;
-    if (!args_ok(d_pk, d_eseed, d_ct, d_ss, d_ws)) return misaligned();
+    if (!aligned<16>(d_pk, d_eseed, d_ct, d_ss, d_ws)) return misaligned();
     hipStream_t st = static_cast<hipStream_t>(stream);
     Carve c{static_cast<uint8_t *>(d_ws)};
     uint8_t *ek = c.take(n * d.EK), *pkx = c.take(n * 32), *m = c.take(n * 32), *ekx = c.take(n * 32), *ctm = c.take(n * d.CTM), *ssm = c.take(n * 32),
@@ -219,32 +236,12 @@ int circl_hip_hybrid_encaps_dev(int scheme, const uint8_t *d_pk, const uint8_t *
     const size_t kws_bytes = ws_bytes - tmp_bytes(d, n);
     SecretWipe wipe{st};  // the ephemeral secrets and the two half shared secrets
     wipe.add(m, n * 32); wipe.add(ekx, n * 32); wipe.add(ssm, n * 32); wipe.add(ssx, n * 32);
-    TRY(copy_rows(st, ek, d.EK, d_pk + d.kem_off(32), d.pk, d.EK, n));
-    TRY(copy_rows(st, pkx, 32, d_pk + d.x_off(d.EK), d.pk, 32, n));
-    if (d.xwing) {  // xwing.go:247-248: seedm = seed[:32], ekx = seed[32:]
-        TRY(copy_rows(st, m, 32, d_eseed, 64, 32, n));
-        TRY(copy_rows(st, ekx, 32, d_eseed + 32, 64, 32, n));
-    } else {
-        if (d.x_first)
-            hipLaunchKernelGGL((hk::hybrid_expand_kernel<4, 4, true>), g256(n), dim3(256), 0, st, w(d_eseed), w(m), w(ekx), n);
-        else
-            hipLaunchKernelGGL((hk::hybrid_expand_kernel<4, 4, false>), g256(n), dim3(256), 0, st, w(d_eseed), w(m), w(ekx), n);
-        HIP_TRY(hipGetLastError());
-    }
+    TRY(split_rows(st, d, d_pk, d.pk, ek, d.EK, pkx, n));
+    TRY(expand_eseed(st, d, d_eseed, m, ekx, n));
     TRY(kem_encaps(d, ek, m, ctm, ssm, d_status, n, kws, kws_bytes, st));
     TRY(x25519_pair_dev(ekx, pkx, ctx, ssx, okx, n, st));  // ct_X = X25519(ekx, 9), ss_X = X25519(ekx, pk_X)
-    TRY(copy_rows(st, d_ct + d.kem_off(32), d.ct, ctm, d.CTM, d.CTM, n));
-    TRY(copy_rows(st, d_ct + d.x_off(d.CTM), d.ct, ctx, 32, 32, n));
-    if (d.xwing) {  // a low-order pk_X is not an error in X-Wing (xwing.go:251-254)
-        hipLaunchKernelGGL(hk::xwing_combine_kernel, g256(n), dim3(256), 0, st, w(ssm), w(ssx), w(ctx), w(pkx), d_status, w(d_ss), n);
-        HIP_TRY(hipGetLastError());
-    } else {
-        hipLaunchKernelGGL(hk::hybrid_status_kernel, g256(n), dim3(256), 0, st, d_status, okx, n);
-        HIP_TRY(hipGetLastError());
-        TRY(copy_rows(st, d_ss + d.kem_off(32), 64, ssm, 32, 32, n));
-        TRY(copy_rows(st, d_ss + d.x_off(32), 64, ssx, 32, 32, n));
-        TRY(zero_failed(st, d_ss, 64, d_status, n));
-    }
+    TRY(join_rows(st, d, d_ct, d.ct, ctm, d.CTM, ctx, n));
+    TRY(shared_secret(st, d, ssm, ssx, ctx, pkx, okx, d_status, d_status, d_ss, n));
     TRY(zero_failed(st, d_ct, d.ct, d_status, n));
     return wipe.finish();
 }
@@ -257,7 +254,7 @@ int circl_hip_hybrid_decaps_dev(int scheme, const uint8_t *d_sk, const uint8_t *
     if (n == 0) return CIRCL_HIP_OK;
     if (!d_status || !d_sk || !d_ct || !d_ss || !d_ws) return CIRCL_HIP_EPARAM;
     if (ws_bytes < hybrid_ws_min(d, n)) return CIRCL_HIP_EWORKSPACE;
-    if (!args_ok(d_sk, d_ct, d_ss, nullptr, d_ws)) return misaligned();
+    if (!aligned<16>(d_sk, d_ct, d_ss, d_ws)) return misaligned();
     hipStream_t st = static_cast<hipStream_t>(stream);
     Carve c{static_cast<uint8_t *>(d_ws)};
     uint8_t *dk = c.take(n * d.DK), *ek = c.take(n * d.EK), *skx = c.take(n * 32), *ctm = c.take(n * d.CTM), *ctx = c.take(n * 32), *ssm = c.take(n * 32),
@@ -266,30 +263,18 @@ int circl_hip_hybrid_decaps_dev(int scheme, const uint8_t *d_sk, const uint8_t *
     const size_t kws_bytes = ws_bytes - tmp_bytes(d, n);
     SecretWipe wipe{st};
     wipe.add(dk, n * d.DK); wipe.add(skx, n * 32); wipe.add(ssm, n * 32); wipe.add(ssx, n * 32); wipe.add(seedm, n * 64);
-    TRY(copy_rows(st, ctm, d.CTM, d_ct + d.kem_off(32), d.ct, d.CTM, n));
-    TRY(copy_rows(st, ctx, 32, d_ct + d.x_off(d.CTM), d.ct, 32, n));
+    TRY(split_rows(st, d, d_ct, d.ct, ctm, d.CTM, ctx, n));
     if (d.xwing) {  // the private key is the seed: re-derive (xwing.go:165-185 Unpack = deriveKeyPair)
-        hipLaunchKernelGGL(hk::xwing_expand_kernel, g256(n), dim3(256), 0, st, w(d_sk), w(seedm), w(skx), n);
+        hipLaunchKernelGGL(hk::xwing_expand_kernel, lanes_grid(n, 256), dim3(256), 0, st, w(d_sk), w(seedm), w(skx), n);
         HIP_TRY(hipGetLastError());
         TRY(kem_keygen(d, seedm, ek, dk, n, kws, kws_bytes, st));
         TRY(x25519_pair_dev(skx, ctx, pkx, ssx, okx, n, st));  // sk.xpk = X25519(sk_X, 9), ss_X = X25519(sk_X, ct_X)
     } else {
-        TRY(copy_rows(st, dk, d.DK, d_sk + d.kem_off(32), d.sk, d.DK, n));
-        TRY(copy_rows(st, skx, 32, d_sk + d.x_off(d.DK), d.sk, 32, n));
+        TRY(split_rows(st, d, d_sk, d.sk, dk, d.DK, skx, n));
         TRY(circl_hip_x25519_dev(skx, ctx, ssx, okx, n, st));
     }
     TRY(kem_decaps(d, dk, ctm, ssm, d_status, n, kws, kws_bytes, st));
-    if (d.xwing) {
-        hipLaunchKernelGGL(hk::xwing_combine_kernel, g256(n), dim3(256), 0, st, w(ssm), w(ssx), w(ctx), w(pkx), static_cast<const uint8_t *>(nullptr),
-                           w(d_ss), n);
-        HIP_TRY(hipGetLastError());
-    } else {
-        hipLaunchKernelGGL(hk::hybrid_status_kernel, g256(n), dim3(256), 0, st, d_status, okx, n);
-        HIP_TRY(hipGetLastError());
-        TRY(copy_rows(st, d_ss + d.kem_off(32), 64, ssm, 32, 32, n));
-        TRY(copy_rows(st, d_ss + d.x_off(32), 64, ssx, 32, 32, n));
-        TRY(zero_failed(st, d_ss, 64, d_status, n));
-    }
+    TRY(shared_secret(st, d, ssm, ssx, ctx, pkx, okx, d_status, nullptr, d_ss, n));
     return wipe.finish();
 }
 
@@ -299,7 +284,7 @@ int circl_hip_hybrid_decaps_dev(int scheme, const uint8_t *d_sk, const uint8_t *
 // (hybrid.go:101-114).  A hybrid table is that: an ML-KEM key table (A^T, H(ek), the private key's hash verdict) of the lattice
 // halves plus the X25519 rows, built once; a call then moves only seeds / ciphertexts and runs the shared-key ML-KEM work.
 static int gather_rows(hipStream_t st, uint8_t *dst, const uint8_t *table, size_t nkeys, const uint32_t *key_idx, size_t n) {
-    hipLaunchKernelGGL(hk::rows_gather_kernel, g256(n * 8), dim3(256), 0, st, w(dst), w(table), KeyIdx{key_idx, (uint32_t)(nkeys - 1)}, 8u, n);
+    hipLaunchKernelGGL(hk::rows_gather_kernel, lanes_grid(n * 8, 256), dim3(256), 0, st, w(dst), w(table), KeyIdx{key_idx, (uint32_t)(nkeys - 1)}, 8u, n);
     HIP_TRY(hipGetLastError());
     return CIRCL_HIP_OK;
 }
@@ -340,18 +325,17 @@ static int hybrid_keytable_new_one(int scheme, const Desc &d, int private_keys, 
     if (rc == CIRCL_HIP_OK && private_keys && d.xwing) {
         // the packed private key is the 32-byte seed: expand it on the device as every X-Wing decapsulation would (xwing.go:98-144)
         const size_t ws_bytes = circl_hip_mlkem_workspace_size(d.param, nkeys);
-        auto r = [](size_t b) { return (b + 255) & ~size_t(255); };
-        tmp.bytes = r(nkeys * 32) + r(nkeys * 64) + r(nkeys * d.EK) + r(nkeys * d.DK) + ws_bytes;
+        tmp.bytes = up256(nkeys * 32) + up256(nkeys * 64) + up256(nkeys * d.EK) + up256(nkeys * d.DK) + ws_bytes;
         if (hipMalloc(reinterpret_cast<void **>(&tmp.p), tmp.bytes) != hipSuccess) { (void)hipGetLastError(); rc = CIRCL_HIP_ENOMEM; }
         if (rc == CIRCL_HIP_OK) {
             Carve c{tmp.p};
-            uint8_t *seed = c.take(nkeys * 32), *seedm = c.take(nkeys * 64), *ek = c.take(nkeys * d.EK), *dk = c.take(nkeys * d.DK), *kws = c.p;
+            uint8_t *seed = c.take(nkeys * 32), *seedm = c.take(nkeys * 64), *ek = c.take(nkeys * d.EK), *dk = c.take(nkeys * d.DK), *kws = c.rest();
             uint8_t *skx = t->d_x, *pkx = t->d_x + nkeys * 32;
             kpin.bytes = nkeys * d.DK;
             if (hipHostMalloc(reinterpret_cast<void **>(&kpin.p), kpin.bytes, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); kpin.p = nullptr; rc = CIRCL_HIP_ENOMEM; }
             auto build = [&]() -> int {
                 TRY(upload_secret(seed, keys, nkeys * 32, st));  // (the seeds ARE the private keys)
-                hipLaunchKernelGGL(hk::xwing_expand_kernel, g256(nkeys), dim3(256), 0, st, w(seed), w(seedm), w(skx), nkeys);
+                hipLaunchKernelGGL(hk::xwing_expand_kernel, lanes_grid(nkeys, 256), dim3(256), 0, st, w(seed), w(seedm), w(skx), nkeys);
                 HIP_TRY(hipGetLastError());
                 TRY(kem_keygen(d, seedm, ek, dk, nkeys, kws, ws_bytes, st));
                 TRY(circl_hip_x25519_dev(skx, nullptr, pkx, nullptr, nkeys, st));
@@ -407,7 +391,7 @@ int circl_hip_hybrid_encaps_table_dev(const circl_hip_keytable *t, const uint32_
     if (n == 0) return CIRCL_HIP_OK;
     if (!d_status || !d_eseed || !d_ct || !d_ss || !d_ws) return CIRCL_HIP_EPARAM;
     if (ws_bytes < hybrid_ws_min(d, n)) return CIRCL_HIP_EWORKSPACE;
-    if (!args_ok(d_eseed, d_ct, d_ss, nullptr, d_ws) || (reinterpret_cast<uintptr_t>(d_key_idx) & 3)) return misaligned();
+    if (!aligned<16>(d_eseed, d_ct, d_ss, d_ws) || !aligned<4>(d_key_idx)) return misaligned();
     hipStream_t st = static_cast<hipStream_t>(stream);
     Carve c{static_cast<uint8_t *>(d_ws)};
     uint8_t *pkx = c.take(n * 32), *m = c.take(n * 32), *ekx = c.take(n * 32), *ctm = c.take(n * d.CTM), *ssm = c.take(n * 32), *ctx = c.take(n * 32),
@@ -417,27 +401,11 @@ int circl_hip_hybrid_encaps_table_dev(const circl_hip_keytable *t, const uint32_
     SecretWipe wipe{st};
     wipe.add(m, n * 32); wipe.add(ekx, n * 32); wipe.add(ssm, n * 32); wipe.add(ssx, n * 32);
     TRY(gather_rows(st, pkx, t->d_x, t->nkeys, d_key_idx, n));
-    if (d.xwing) {
-        TRY(copy_rows(st, m, 32, d_eseed, 64, 32, n));
-        TRY(copy_rows(st, ekx, 32, d_eseed + 32, 64, 32, n));
-    } else {
-        hipLaunchKernelGGL((hk::hybrid_expand_kernel<4, 4, false>), g256(n), dim3(256), 0, st, w(d_eseed), w(m), w(ekx), n);
-        HIP_TRY(hipGetLastError());
-    }
+    TRY(expand_eseed(st, d, d_eseed, m, ekx, n));  // (a table is never X25519-first: round-3 Kyber has none)
     TRY(circl_hip_mlkem_encaps_table_dev(t->inner, d_key_idx, m, ctm, ssm, d_status, n, kws, kws_bytes, st));
     TRY(x25519_pair_dev(ekx, pkx, ctx, ssx, okx, n, st));
-    TRY(copy_rows(st, d_ct + d.kem_off(32), d.ct, ctm, d.CTM, d.CTM, n));
-    TRY(copy_rows(st, d_ct + d.x_off(d.CTM), d.ct, ctx, 32, 32, n));
-    if (d.xwing) {
-        hipLaunchKernelGGL(hk::xwing_combine_kernel, g256(n), dim3(256), 0, st, w(ssm), w(ssx), w(ctx), w(pkx), d_status, w(d_ss), n);
-        HIP_TRY(hipGetLastError());
-    } else {
-        hipLaunchKernelGGL(hk::hybrid_status_kernel, g256(n), dim3(256), 0, st, d_status, okx, n);
-        HIP_TRY(hipGetLastError());
-        TRY(copy_rows(st, d_ss + d.kem_off(32), 64, ssm, 32, 32, n));
-        TRY(copy_rows(st, d_ss + d.x_off(32), 64, ssx, 32, 32, n));
-        TRY(zero_failed(st, d_ss, 64, d_status, n));
-    }
+    TRY(join_rows(st, d, d_ct, d.ct, ctm, d.CTM, ctx, n));
+    TRY(shared_secret(st, d, ssm, ssx, ctx, pkx, okx, d_status, d_status, d_ss, n));
     TRY(zero_failed(st, d_ct, d.ct, d_status, n));
     return wipe.finish();
 }
@@ -451,7 +419,7 @@ int circl_hip_hybrid_decaps_table_dev(const circl_hip_keytable *t, const uint32_
     if (n == 0) return CIRCL_HIP_OK;
     if (!d_status || !d_ct || !d_ss || !d_ws) return CIRCL_HIP_EPARAM;
     if (ws_bytes < hybrid_ws_min(d, n)) return CIRCL_HIP_EWORKSPACE;
-    if (!args_ok(d_ct, d_ss, nullptr, nullptr, d_ws) || (reinterpret_cast<uintptr_t>(d_key_idx) & 3)) return misaligned();
+    if (!aligned<16>(d_ct, d_ss, d_ws) || !aligned<4>(d_key_idx)) return misaligned();
     hipStream_t st = static_cast<hipStream_t>(stream);
     Carve c{static_cast<uint8_t *>(d_ws)};
     uint8_t *skx = c.take(n * 32), *pkx = c.take(n * 32), *ctm = c.take(n * d.CTM), *ctx = c.take(n * 32), *ssm = c.take(n * 32), *ssx = c.take(n * 32),
@@ -460,23 +428,12 @@ int circl_hip_hybrid_decaps_table_dev(const circl_hip_keytable *t, const uint32_
     const size_t kws_bytes = ws_bytes - tmp_bytes(d, n);
     SecretWipe wipe{st};
     wipe.add(skx, n * 32); wipe.add(ssm, n * 32); wipe.add(ssx, n * 32);
-    TRY(copy_rows(st, ctm, d.CTM, d_ct + d.kem_off(32), d.ct, d.CTM, n));
-    TRY(copy_rows(st, ctx, 32, d_ct + d.x_off(d.CTM), d.ct, 32, n));
+    TRY(split_rows(st, d, d_ct, d.ct, ctm, d.CTM, ctx, n));
     TRY(gather_rows(st, skx, t->d_x, t->nkeys, d_key_idx, n));
     if (d.xwing) TRY(gather_rows(st, pkx, t->d_x + t->nkeys * 32, t->nkeys, d_key_idx, n));  // sk.xpk, computed when the table was built
     TRY(circl_hip_x25519_dev(skx, ctx, ssx, okx, n, st));
     TRY(circl_hip_mlkem_decaps_table_dev(t->inner, d_key_idx, ctm, ssm, d_status, n, kws, kws_bytes, st));
-    if (d.xwing) {
-        hipLaunchKernelGGL(hk::xwing_combine_kernel, g256(n), dim3(256), 0, st, w(ssm), w(ssx), w(ctx), w(pkx), static_cast<const uint8_t *>(nullptr),
-                           w(d_ss), n);
-        HIP_TRY(hipGetLastError());
-    } else {
-        hipLaunchKernelGGL(hk::hybrid_status_kernel, g256(n), dim3(256), 0, st, d_status, okx, n);
-        HIP_TRY(hipGetLastError());
-        TRY(copy_rows(st, d_ss + d.kem_off(32), 64, ssm, 32, 32, n));
-        TRY(copy_rows(st, d_ss + d.x_off(32), 64, ssx, 32, 32, n));
-        TRY(zero_failed(st, d_ss, 64, d_status, n));
-    }
+    TRY(shared_secret(st, d, ssm, ssx, ctx, pkx, okx, d_status, nullptr, d_ss, n));
     return wipe.finish();
 }
 
@@ -504,6 +461,30 @@ static std::function<size_t(size_t)> hybrid_ws_fn(int scheme) {
     };
 }
 
+// The arrays and the launch of the host forms, each said once: the blocking call, its coalesced batch, the asynchronous queue of a table or
+// of the entry point itself all pass the same shapes.  In the table forms key_idx is the one OPTIONAL array (absent: entry 0 for every item).
+static std::vector<HIn> hyb_enc_ins(const uint8_t *pk, const uint8_t *eseed, const Desc &s) { return {{pk, s.pk}, {eseed, s.eseed, true}}; }
+static std::vector<HIn> hyb_dec_ins(const uint8_t *sk, const uint8_t *ct, const Desc &s) { return {{sk, s.sk, true}, {ct, s.ct}}; }
+static std::vector<HIn> hyb_enc_table_ins(const uint32_t *ki, const uint8_t *eseed, const Desc &s) {
+    return {{reinterpret_cast<const uint8_t *>(ki), size_t(4), false, false, true}, {eseed, s.eseed, true}};
+}
+static std::vector<HIn> hyb_dec_table_ins(const uint32_t *ki, const uint8_t *ct, const Desc &s) {
+    return {{reinterpret_cast<const uint8_t *>(ki), size_t(4), false, false, true}, {ct, s.ct}};
+}
+static std::vector<HOut> hyb_enc_outs(uint8_t *ct, uint8_t *ss, uint8_t *status, const Desc &s) { return {{ct, s.ct}, {ss, s.ss, true}, {status, 1}}; }
+static std::vector<HOut> hyb_dec_outs(uint8_t *ss, uint8_t *status, const Desc &s) { return {{ss, s.ss, true}, {status, 1}}; }
+static int hyb_enc_chunk(int scheme, Chunk &c) {
+    return circl_hip_hybrid_encaps_dev(scheme, c.in[0], c.in[1], c.out[0], c.out[1], c.out[2], c.cnt, c.ws, c.ws_bytes, c.st);
+}
+static int hyb_dec_chunk(int scheme, Chunk &c) { return circl_hip_hybrid_decaps_dev(scheme, c.in[0], c.in[1], c.out[0], c.out[1], c.cnt, c.ws, c.ws_bytes, c.st); }
+static int hyb_enc_table_chunk(const circl_hip_keytable *r, Chunk &c, const uint32_t *d_key_idx) {
+    return circl_hip_hybrid_encaps_table_dev(r, d_key_idx, c.in[1], c.out[0], c.out[1], c.out[2], c.cnt, c.ws, c.ws_bytes, c.st);
+}
+static int hyb_dec_table_chunk(const circl_hip_keytable *r, Chunk &c, const uint32_t *d_key_idx) {
+    return circl_hip_hybrid_decaps_table_dev(r, d_key_idx, c.in[1], c.out[0], c.out[1], c.cnt, c.ws, c.ws_bytes, c.st);
+}
+static const uint32_t *key_idx_of(const Chunk &c) { return reinterpret_cast<const uint32_t *>(c.in[0]); }
+
 int circl_hip_hybrid_keygen(int scheme, const uint8_t *seed, uint8_t *pk, uint8_t *sk, size_t n, int device) {
     Desc s;
     if (!desc_of(scheme, s)) return CIRCL_HIP_EPARAM;
@@ -515,21 +496,16 @@ int circl_hip_hybrid_keygen(int scheme, const uint8_t *seed, uint8_t *pk, uint8_
     }, kHeavyOneDeviceMax);
 }
 
+// circl_hip_set_coalesce: what a TLS 1.3 server does per X25519MLKEM768 handshake -- one encapsulation to the client's ephemeral
+// share -- from many connections at once (kem/hybrid/hybrid.go:271-300); a ladder costs ~0.8 ms however few items share it
 int circl_hip_hybrid_encaps(int scheme, const uint8_t *pk, const uint8_t *eseed, uint8_t *ct, uint8_t *ss, uint8_t *status, size_t n, int device) {
     Desc s;
     if (!desc_of(scheme, s)) return CIRCL_HIP_EPARAM;
     if (n && (!pk || !eseed || !ct || !ss)) return CIRCL_HIP_EPARAM;
     return shard(n, device, [&](int dev, size_t lo, size_t cnt) {
-        const std::vector<HIn> ins = {{pk + lo * s.pk, s.pk}, {eseed + lo * s.eseed, s.eseed, true}};
-        const std::vector<HOut> outs = {{ct + lo * s.ct, s.ct}, {ss + lo * s.ss, s.ss, true}, {status ? status + lo : nullptr, 1}};
-        auto launch = [&](Chunk &c) { return circl_hip_hybrid_encaps_dev(scheme, c.in[0], c.in[1], c.out[0], c.out[1], c.out[2], c.cnt, c.ws, c.ws_bytes, c.st); };
-        // circl_hip_set_coalesce: what a TLS 1.3 server does per X25519MLKEM768 handshake -- one encapsulation to the client's ephemeral
-        // share -- from many connections at once (kem/hybrid/hybrid.go:271-300); a ladder costs ~0.8 ms however few items share it
-        if (Coalescer *co = call_coalescer(kCoHybEncaps, scheme - 1, dev)) {
-            const int rc = coalesce_run(co, cnt, ins, {}, outs, hybrid_ws_fn(scheme), hybrid_opts(scheme), launch);
-            if (rc != kNotCoalesced) return rc;
-        }
-        return run_pipeline(dev, cnt, ins, {}, outs, hybrid_ws_fn(scheme), hybrid_opts(scheme), launch);
+        return coalesce_or_pipeline(call_coalescer(kCoHybEncaps, scheme - 1, dev), dev, cnt, hyb_enc_ins(pk + lo * s.pk, eseed + lo * s.eseed, s), {},
+                                    hyb_enc_outs(ct + lo * s.ct, ss + lo * s.ss, status ? status + lo : nullptr, s), hybrid_ws_fn(scheme), hybrid_opts(scheme),
+                                    [&](Chunk &c) { return hyb_enc_chunk(scheme, c); });
     }, kHeavyOneDeviceMax);
 }
 
@@ -538,32 +514,15 @@ int circl_hip_hybrid_decaps(int scheme, const uint8_t *sk, const uint8_t *ct, ui
     if (!desc_of(scheme, s)) return CIRCL_HIP_EPARAM;
     if (n && (!sk || !ct || !ss)) return CIRCL_HIP_EPARAM;
     return shard(n, device, [&](int dev, size_t lo, size_t cnt) {
-        const std::vector<HIn> ins = {{sk + lo * s.sk, s.sk, true}, {ct + lo * s.ct, s.ct}};
-        const std::vector<HOut> outs = {{ss + lo * s.ss, s.ss, true}, {status ? status + lo : nullptr, 1}};
-        auto launch = [&](Chunk &c) { return circl_hip_hybrid_decaps_dev(scheme, c.in[0], c.in[1], c.out[0], c.out[1], c.cnt, c.ws, c.ws_bytes, c.st); };
-        if (Coalescer *co = call_coalescer(kCoHybDecaps, scheme - 1, dev)) {
-            const int rc = coalesce_run(co, cnt, ins, {}, outs, hybrid_ws_fn(scheme), hybrid_opts(scheme), launch);
-            if (rc != kNotCoalesced) return rc;
-        }
-        return run_pipeline(dev, cnt, ins, {}, outs, hybrid_ws_fn(scheme), hybrid_opts(scheme), launch);
+        return coalesce_or_pipeline(call_coalescer(kCoHybDecaps, scheme - 1, dev), dev, cnt, hyb_dec_ins(sk + lo * s.sk, ct + lo * s.ct, s), {},
+                                    hyb_dec_outs(ss + lo * s.ss, status ? status + lo : nullptr, s), hybrid_ws_fn(scheme), hybrid_opts(scheme),
+                                    [&](Chunk &c) { return hyb_dec_chunk(scheme, c); });
     }, kHeavyOneDeviceMax);
 }
 
-static int check_idx(const uint32_t *key_idx, size_t n, size_t nkeys) {
-    if (key_idx)
-        for (size_t i = 0; i < n; i++)
-            if (key_idx[i] >= nkeys) return CIRCL_HIP_EPARAM;
-    return CIRCL_HIP_OK;
-}
-// host buffers through a resident hybrid table.  key_idx is the one OPTIONAL array (absent: entry 0 for every item).  A small call joins the
-// table's cross-caller batch (circl_hip_keytable_set_coalesce) or, submitted, its asynchronous queue (circl_hip_keytable_async_start) -- the
-// X25519 ladder makes ONE hybrid launch ~0.8 ms whatever it holds, so these are the calls that gain most from sharing it.
-static std::vector<HIn> hyb_enc_ins(const uint32_t *ki, const uint8_t *eseed, const Desc &s) {
-    return {{reinterpret_cast<const uint8_t *>(ki), size_t(4), false, false, true}, {eseed, s.eseed, true}};
-}
-static std::vector<HIn> hyb_dec_ins(const uint32_t *ki, const uint8_t *ct, const Desc &s) {
-    return {{reinterpret_cast<const uint8_t *>(ki), size_t(4), false, false, true}, {ct, s.ct}};
-}
+// host buffers through a resident hybrid table.  A small call joins the table's cross-caller batch (circl_hip_keytable_set_coalesce) or,
+// submitted, its asynchronous queue (circl_hip_keytable_async_start) -- the X25519 ladder makes ONE hybrid launch ~0.8 ms whatever it
+// holds, so these are the calls that gain most from sharing it.
 int circl_hip_hybrid_encaps_table(const circl_hip_keytable *t, const uint32_t *key_idx, const uint8_t *eseed, uint8_t *ct, uint8_t *ss, uint8_t *status,
                                   size_t n) {
     if (!t || t->magic != kKeytableMagic || t->family != 3 || t->private_keys) return CIRCL_HIP_EPARAM;
@@ -571,26 +530,13 @@ int circl_hip_hybrid_encaps_table(const circl_hip_keytable *t, const uint32_t *k
     if (!desc_of(t->scheme, s)) return CIRCL_HIP_EPARAM;
     if (n == 0) return CIRCL_HIP_OK;
     if (!eseed || !ct || !ss) return CIRCL_HIP_EPARAM;
-    TRY(check_idx(key_idx, n, t->nkeys));
+    if (key_idx) TRY(check_key_idx(key_idx, n, t->nkeys));
     const int scheme = t->scheme;
     return table_shard(t, n, [&](const circl_hip_keytable *r, size_t lo, size_t cnt) {
-        const uint32_t *ki = key_idx ? key_idx + lo : nullptr;
-        Coalescer *co = usable_coalescer(r);
-        if (co && cnt <= coalescer_call_max(co)) {
-            const int rc = coalesce_run(co, cnt, hyb_enc_ins(ki, eseed + lo * s.eseed, s), {},
-                                        {{ct + lo * s.ct, s.ct}, {ss + lo * s.ss, s.ss, true}, {status ? status + lo : nullptr, 1}}, hybrid_ws_fn(scheme), hybrid_opts(scheme),
-                                        [&](Chunk &c) {
-                                            return circl_hip_hybrid_encaps_table_dev(r, reinterpret_cast<const uint32_t *>(c.in[0]), c.in[1], c.out[0], c.out[1], c.out[2],
-                                                                                     c.cnt, c.ws, c.ws_bytes, c.st);
-                                        });
-            if (rc != kNotCoalesced) return rc;
-        }
-        return run_pipeline(r->device, cnt, {{reinterpret_cast<const uint8_t *>(ki), ki ? size_t(4) : size_t(0)}, {eseed + lo * s.eseed, s.eseed, true}}, {},
-                            {{ct + lo * s.ct, s.ct}, {ss + lo * s.ss, s.ss, true}, {status ? status + lo : nullptr, 1}},
-                            hybrid_ws_fn(scheme), hybrid_opts(scheme), [&](Chunk &c) {
-                                return circl_hip_hybrid_encaps_table_dev(r, ki ? reinterpret_cast<const uint32_t *>(c.in[0]) : nullptr, c.in[1], c.out[0], c.out[1],
-                                                                         c.out[2], c.cnt, c.ws, c.ws_bytes, c.st);
-                            });
+        return table_coalesce_or_pipeline(r, cnt, hyb_enc_table_ins(key_idx ? key_idx + lo : nullptr, eseed + lo * s.eseed, s), 0, {},
+                                          hyb_enc_outs(ct + lo * s.ct, ss + lo * s.ss, status ? status + lo : nullptr, s), hybrid_ws_fn(scheme),
+                                          hybrid_opts(scheme), hybrid_opts(scheme),
+                                          [&](Chunk &c, const uint32_t *d_key_idx) { return hyb_enc_table_chunk(r, c, d_key_idx); });
     }, kHeavyOneDeviceMax);
 }
 int circl_hip_hybrid_decaps_table(const circl_hip_keytable *t, const uint32_t *key_idx, const uint8_t *ct, uint8_t *ss, uint8_t *status, size_t n) {
@@ -599,25 +545,12 @@ int circl_hip_hybrid_decaps_table(const circl_hip_keytable *t, const uint32_t *k
     if (!desc_of(t->scheme, s)) return CIRCL_HIP_EPARAM;
     if (n == 0) return CIRCL_HIP_OK;
     if (!ct || !ss) return CIRCL_HIP_EPARAM;
-    TRY(check_idx(key_idx, n, t->nkeys));
+    if (key_idx) TRY(check_key_idx(key_idx, n, t->nkeys));
     const int scheme = t->scheme;
     return table_shard(t, n, [&](const circl_hip_keytable *r, size_t lo, size_t cnt) {
-        const uint32_t *ki = key_idx ? key_idx + lo : nullptr;
-        Coalescer *co = usable_coalescer(r);
-        if (co && cnt <= coalescer_call_max(co)) {
-            const int rc = coalesce_run(co, cnt, hyb_dec_ins(ki, ct + lo * s.ct, s), {}, {{ss + lo * s.ss, s.ss, true}, {status ? status + lo : nullptr, 1}},
-                                        hybrid_ws_fn(scheme), hybrid_opts(scheme), [&](Chunk &c) {
-                                            return circl_hip_hybrid_decaps_table_dev(r, reinterpret_cast<const uint32_t *>(c.in[0]), c.in[1], c.out[0], c.out[1], c.cnt,
-                                                                                     c.ws, c.ws_bytes, c.st);
-                                        });
-            if (rc != kNotCoalesced) return rc;
-        }
-        return run_pipeline(r->device, cnt, {{reinterpret_cast<const uint8_t *>(ki), ki ? size_t(4) : size_t(0)}, {ct + lo * s.ct, s.ct}}, {},
-                            {{ss + lo * s.ss, s.ss, true}, {status ? status + lo : nullptr, 1}},
-                            hybrid_ws_fn(scheme), hybrid_opts(scheme), [&](Chunk &c) {
-                                return circl_hip_hybrid_decaps_table_dev(r, ki ? reinterpret_cast<const uint32_t *>(c.in[0]) : nullptr, c.in[1], c.out[0], c.out[1],
-                                                                         c.cnt, c.ws, c.ws_bytes, c.st);
-                            });
+        return table_coalesce_or_pipeline(r, cnt, hyb_dec_table_ins(key_idx ? key_idx + lo : nullptr, ct + lo * s.ct, s), 0, {},
+                                          hyb_dec_outs(ss + lo * s.ss, status ? status + lo : nullptr, s), hybrid_ws_fn(scheme), hybrid_opts(scheme),
+                                          hybrid_opts(scheme), [&](Chunk &c, const uint32_t *d_key_idx) { return hyb_dec_table_chunk(r, c, d_key_idx); });
     }, kHeavyOneDeviceMax);
 }
 // ---- the asynchronous form (include/circl_hip.h: circl_hip_keytable_async_start) ----
@@ -629,9 +562,9 @@ int circl_hip_hybrid_encaps_table_submit(const circl_hip_keytable *t, const uint
     if (!desc_of(t->scheme, s)) return CIRCL_HIP_EPARAM;
     if (n == 0) return CIRCL_HIP_OK;
     if (!eseed || !ct || !ss) return CIRCL_HIP_EPARAM;
-    TRY(check_idx(key_idx, n, t->nkeys));
+    if (key_idx) TRY(check_key_idx(key_idx, n, t->nkeys));
     return table_submit(t, ticket, [&](const circl_hip_keytable *, Coalescer *co, uint64_t *seq) {
-        return coalesce_submit(co, n, hyb_enc_ins(key_idx, eseed, s), {}, {{ct, s.ct}, {ss, s.ss, true}, {status, 1}}, seq, false);
+        return coalesce_submit(co, n, hyb_enc_table_ins(key_idx, eseed, s), {}, hyb_enc_outs(ct, ss, status, s), seq, false);
     });
 }
 int circl_hip_hybrid_decaps_table_submit(const circl_hip_keytable *t, const uint32_t *key_idx, const uint8_t *ct, uint8_t *ss, uint8_t *status, size_t n,
@@ -642,9 +575,9 @@ int circl_hip_hybrid_decaps_table_submit(const circl_hip_keytable *t, const uint
     if (!desc_of(t->scheme, s)) return CIRCL_HIP_EPARAM;
     if (n == 0) return CIRCL_HIP_OK;
     if (!ct || !ss) return CIRCL_HIP_EPARAM;
-    TRY(check_idx(key_idx, n, t->nkeys));
+    if (key_idx) TRY(check_key_idx(key_idx, n, t->nkeys));
     return table_submit(t, ticket, [&](const circl_hip_keytable *, Coalescer *co, uint64_t *seq) {
-        return coalesce_submit(co, n, hyb_dec_ins(key_idx, ct, s), {}, {{ss, s.ss, true}, {status, 1}}, seq, false);
+        return coalesce_submit(co, n, hyb_dec_table_ins(key_idx, ct, s), {}, hyb_dec_outs(ss, status, s), seq, false);
     });
 }
 
@@ -658,15 +591,12 @@ int hyb_call_queue_start(bool decaps, int scheme, Coalescer *co, bool want_event
     if (!desc_of(scheme, s)) return CIRCL_HIP_EPARAM;
     if (!decaps) {
         *sh = QueueShape{s.pk, s.eseed, s.ct, s.ss, false, true};
-        return coalescer_async_start(co, {{nullptr, s.pk}, {nullptr, s.eseed, true}}, {}, {{nullptr, s.ct}, {nullptr, s.ss, true}, {nullptr, 1}}, hybrid_ws_fn(scheme),
-                                     hybrid_opts(scheme), [scheme](Chunk &c) {
-                                         return circl_hip_hybrid_encaps_dev(scheme, c.in[0], c.in[1], c.out[0], c.out[1], c.out[2], c.cnt, c.ws, c.ws_bytes, c.st);
-                                     }, want_eventfd);
+        return coalescer_async_start(co, hyb_enc_ins(nullptr, nullptr, s), {}, hyb_enc_outs(nullptr, nullptr, nullptr, s), hybrid_ws_fn(scheme), hybrid_opts(scheme),
+                                     [scheme](Chunk &c) { return hyb_enc_chunk(scheme, c); }, want_eventfd);
     }
     *sh = QueueShape{s.sk, s.ct, 0, s.ss, true, false};
-    return coalescer_async_start(co, {{nullptr, s.sk, true}, {nullptr, s.ct}}, {}, {{nullptr, s.ss, true}, {nullptr, 1}}, hybrid_ws_fn(scheme), hybrid_opts(scheme),
-                                 [scheme](Chunk &c) { return circl_hip_hybrid_decaps_dev(scheme, c.in[0], c.in[1], c.out[0], c.out[1], c.cnt, c.ws, c.ws_bytes, c.st); },
-                                 want_eventfd);
+    return coalescer_async_start(co, hyb_dec_ins(nullptr, nullptr, s), {}, hyb_dec_outs(nullptr, nullptr, s), hybrid_ws_fn(scheme), hybrid_opts(scheme),
+                                 [scheme](Chunk &c) { return hyb_dec_chunk(scheme, c); }, want_eventfd);
 }
 // the queue of one hybrid table (part): its arrays and its launch, fixed for the queue's life (`r` outlives the queue: the table owns it)
 int hyb_table_async_start(const circl_hip_keytable *r, Coalescer *co, bool want_eventfd) {
@@ -674,14 +604,10 @@ int hyb_table_async_start(const circl_hip_keytable *r, Coalescer *co, bool want_
     if (!desc_of(r->scheme, s)) return CIRCL_HIP_EPARAM;
     const int scheme = r->scheme;
     if (!r->private_keys)
-        return coalescer_async_start(co, hyb_enc_ins(nullptr, nullptr, s), {}, {{nullptr, s.ct}, {nullptr, s.ss, true}, {nullptr, 1}}, hybrid_ws_fn(scheme), hybrid_opts(scheme),
-                                     [r](Chunk &c) {
-                                         return circl_hip_hybrid_encaps_table_dev(r, reinterpret_cast<const uint32_t *>(c.in[0]), c.in[1], c.out[0], c.out[1], c.out[2], c.cnt,
-                                                                                  c.ws, c.ws_bytes, c.st);
-                                     }, want_eventfd);
-    return coalescer_async_start(co, hyb_dec_ins(nullptr, nullptr, s), {}, {{nullptr, s.ss, true}, {nullptr, 1}}, hybrid_ws_fn(scheme), hybrid_opts(scheme), [r](Chunk &c) {
-        return circl_hip_hybrid_decaps_table_dev(r, reinterpret_cast<const uint32_t *>(c.in[0]), c.in[1], c.out[0], c.out[1], c.cnt, c.ws, c.ws_bytes, c.st);
-    }, want_eventfd);
+        return coalescer_async_start(co, hyb_enc_table_ins(nullptr, nullptr, s), {}, hyb_enc_outs(nullptr, nullptr, nullptr, s), hybrid_ws_fn(scheme),
+                                     hybrid_opts(scheme), [r](Chunk &c) { return hyb_enc_table_chunk(r, c, key_idx_of(c)); }, want_eventfd);
+    return coalescer_async_start(co, hyb_dec_table_ins(nullptr, nullptr, s), {}, hyb_dec_outs(nullptr, nullptr, s), hybrid_ws_fn(scheme), hybrid_opts(scheme),
+                                 [r](Chunk &c) { return hyb_dec_table_chunk(r, c, key_idx_of(c)); }, want_eventfd);
 }
 }  // namespace host
 }  // namespace circl

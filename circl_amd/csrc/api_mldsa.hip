@@ -2,7 +2,7 @@
 //
 // No CPU path: every compute entry point launches the HIP kernels of mldsa_kernels.h / mldsa_sign_batched.h or fails
 // with CIRCL_HIP_ENODEV.
-#include "host_common.h"
+#include "host_compose.h"
 #include "keytable.h"
 #include "mldsa_kernels.h"
 #include "mldsa_sign_batched.h"
@@ -137,7 +137,7 @@ int mldsa_verify_dev_impl(const uint8_t *pk, size_t nkeys, const uint32_t *key_i
     if (KM == KM_KEYED && nkeys == 0) return CIRCL_HIP_EPARAM;
     if (cached) pk = cached->d_keys;
     const size_t need = mldsa_ws_bytes<MODE>(n) + (KM == KM_KEYED && !cached ? mldsa_table_bytes<MODE>(nkeys) : 0);
-    if (ws_bytes < need || !aligned16(ws) || !aligned16(pk) || (reinterpret_cast<uintptr_t>(key_idx) & 3)) return CIRCL_HIP_EWORKSPACE;
+    if (ws_bytes < need || !aligned<16>(ws, pk) || !aligned<4>(key_idx)) return CIRCL_HIP_EWORKSPACE;
     const KeyIdx kx{KM == KM_KEYED ? key_idx : nullptr, nkeys ? (uint32_t)(nkeys - 1) : 0u};  // a device index vector is bounded to the table on every read
     uint8_t *muw1 = static_cast<uint8_t *>(ws);
     uint8_t *ball = muw1 + up256(n * G::MUW1);
@@ -245,7 +245,7 @@ int mldsa_keygen_dev_impl(const uint8_t *seed32, uint8_t *pk, uint8_t *sk, size_
     using Kg = circl::mldsa::KG<MODE>;
     using namespace circl::mldsa;
     if (n == 0) return CIRCL_HIP_OK;
-    if (ws_bytes < mldsa_ws_bytes<MODE>(n) || !aligned16(ws) || !aligned16(seed32) || !aligned16(pk) || !aligned16(sk))
+    if (ws_bytes < mldsa_ws_bytes<MODE>(n) || !aligned<16>(ws, seed32, pk, sk))
         return CIRCL_HIP_EWORKSPACE;
     uint8_t *es = static_cast<uint8_t *>(ws);
     unsigned *work = reinterpret_cast<unsigned *>(es + mldsa_item_ws_bytes<MODE>(n));
@@ -288,7 +288,7 @@ int mldsa_public_dev_impl(const uint8_t *sk, uint8_t *pk, size_t n, void *ws, si
     using Kg = circl::mldsa::KG<MODE>;
     using namespace circl::mldsa;
     if (n == 0) return CIRCL_HIP_OK;
-    if (ws_bytes < mldsa_ws_bytes<MODE>(n) || !aligned16(ws) || !aligned16(sk) || !aligned16(pk)) return CIRCL_HIP_EWORKSPACE;
+    if (ws_bytes < mldsa_ws_bytes<MODE>(n) || !aligned<16>(ws, sk, pk)) return CIRCL_HIP_EWORKSPACE;
     unsigned *work = reinterpret_cast<unsigned *>(static_cast<uint8_t *>(ws) + mldsa_item_ws_bytes<MODE>(n));
     uint8_t *scratch = reinterpret_cast<uint8_t *>(work) + 256;
     HIP_TRY(hipMemsetAsync(work, 0, 256, st));
@@ -393,14 +393,12 @@ int mldsa_verify_host_one(int param, int dev, const uint8_t *pk, size_t nkeys, c
         return mldsa_verify_dev_any<KM>(param, c.in[0], nkeys, KM == KM_KEYED ? reinterpret_cast<const uint32_t *>(c.in[2]) : nullptr, c.in[1], c.blob[0], c.off[0],
                                         c.blob[1], c.off[1], internal, c.out[0], c.cnt, c.ws, c.ws_bytes, c.st);
     };
+    Coalescer *co = nullptr;
     if (KM == KM_ITEM && msg_blob && all_inputs_present(ins)) {  // circl_hip_set_coalesce: every item brings its own key, so calls of different callers mix freely
         const int slot = param == 44 ? 0 : param == 65 ? 1 : param == 87 ? 2 : -1;  // (round-3 Dilithium: no slot, never coalesced)
-        if (Coalescer *co = call_coalescer(internal ? kCoDsaVerifyInternal : kCoDsaVerify, slot, dev)) {
-            const int rc = coalesce_run(co, n, ins, blobs, outs, ws_fn, dsa_opts(size_t(1) << 13, false), launch);
-            if (rc != kNotCoalesced) return rc;
-        }
+        co = call_coalescer(internal ? kCoDsaVerifyInternal : kCoDsaVerify, slot, dev);
     }
-    return run_pipeline(dev, n, ins, blobs, outs, ws_fn, dsa_opts(size_t(1) << 13, false), launch);
+    return coalesce_or_pipeline(co, dev, n, ins, blobs, outs, ws_fn, dsa_opts(size_t(1) << 13, false), launch);
 }
 
 // ---- ML-DSA sign ------------------------------------------------------------------------------
@@ -735,7 +733,7 @@ int mldsa_sign_dev_impl(const uint8_t *sk, const uint8_t *msg_blob, const uint64
     using S = circl::mldsa::SG<MODE>;
     using namespace circl::mldsa;
     if (n == 0) return CIRCL_HIP_OK;
-    if (ws_bytes < mldsa_sign_ws_bytes<MODE>(n) || !aligned16(ws) || !aligned16(sk) || !aligned16(rnd) || rnd == nullptr)
+    if (ws_bytes < mldsa_sign_ws_bytes<MODE>(n) || !aligned<16>(ws, sk, rnd) || rnd == nullptr)
         return CIRCL_HIP_EWORKSPACE;
     if (n >= sign_batched_min()) return mldsa_sign_batched<MODE>(sk, msg_blob, msg_off, ctx_blob, ctx_off, rnd, internal, sig, n, ws, st, shared);
     const SignLayout<MODE> lay(n);
@@ -945,28 +943,17 @@ int circl_hip_mldsa_verify_table(const circl_hip_keytable *t, const uint32_t *ke
     const int param = t->param;
     const size_t SIG = circl_hip_mldsa_sig_size(param);
     if (n == 0) return CIRCL_HIP_OK;
-    if (key_idx)
-        for (size_t i = 0; i < n; i++)
-            if (key_idx[i] >= t->nkeys) return CIRCL_HIP_EPARAM;
+    if (key_idx) TRY(check_key_idx(key_idx, n, t->nkeys));
     if (check_contexts(param, ctx_blob, ctx_off, n) == CTX_UNSUPPORTED) return CIRCL_HIP_EPARAM;
     return table_shard(t, n, [&](const circl_hip_keytable *r, size_t lo, size_t cnt) {
-        const uint32_t *ki = key_idx ? key_idx + lo : nullptr;
-        Coalescer *co = usable_coalescer(r);
-        if (co && cnt <= coalescer_call_max(co)) {  // a small call joins the table's cross-caller batch (absent key_idx: zeros; absent contexts: empty rows)
-            const int rc = coalesce_run(co, cnt, {{sig ? sig + lo * SIG : nullptr, SIG}, {reinterpret_cast<const uint8_t *>(ki), size_t(4), false, false, true}},
-                                        {{msg_blob, msg_off + lo}, {ctx_blob, ctx_blob ? ctx_off + lo : nullptr}}, {{ok + lo, 1}},
-                                        [&](size_t c) { return mldsa_ws_any(param, c); }, dsa_verify_table_opts(), [&](Chunk &c) {
-                                            return circl_hip_mldsa_verify_table_dev(r, reinterpret_cast<const uint32_t *>(c.in[1]), c.in[0], c.blob[0], c.off[0], c.blob[1],
-                                                                                    c.off[1], c.out[0], c.cnt, c.ws, c.ws_bytes, c.st);
-                                        });
-            if (rc != kNotCoalesced) return rc;
-        }
-        return run_pipeline(r->device, cnt, {{sig ? sig + lo * SIG : nullptr, SIG}, {reinterpret_cast<const uint8_t *>(ki), ki ? size_t(4) : size_t(0)}},
-                            {{msg_blob, msg_off + lo}, {ctx_blob, ctx_blob ? ctx_off + lo : nullptr}}, {{ok + lo, 1}}, [&](size_t c) { return mldsa_ws_any(param, c); },
-                            dsa_opts(size_t(1) << 13, false), [&](Chunk &c) {
-                                return circl_hip_mldsa_verify_table_dev(r, ki ? reinterpret_cast<const uint32_t *>(c.in[1]) : nullptr, c.in[0], c.blob[0], c.off[0],
-                                                                        c.blob[1], c.off[1], c.out[0], c.cnt, c.ws, c.ws_bytes, c.st);
-                            });
+        // a small call joins the table's cross-caller batch (absent contexts: empty rows), whose ONE launch may raise the completion flag itself
+        return table_coalesce_or_pipeline(r, cnt, {{sig ? sig + lo * SIG : nullptr, SIG}, {reinterpret_cast<const uint8_t *>(key_idx ? key_idx + lo : nullptr), size_t(4), false, false, true}},
+                                          1, {{msg_blob, msg_off + lo}, {ctx_blob, ctx_blob ? ctx_off + lo : nullptr}}, {{ok + lo, 1}},
+                                          [&](size_t c) { return mldsa_ws_any(param, c); }, dsa_verify_table_opts(), dsa_opts(size_t(1) << 13, false),
+                                          [&](Chunk &c, const uint32_t *d_key_idx) {
+                                              return circl_hip_mldsa_verify_table_dev(r, d_key_idx, c.in[0], c.blob[0], c.off[0], c.blob[1], c.off[1], c.out[0], c.cnt, c.ws,
+                                                                                      c.ws_bytes, c.st);
+                                          });
     });
 }
 
@@ -979,9 +966,7 @@ int circl_hip_mldsa_verify_table_submit(const circl_hip_keytable *t, const uint3
     const int param = t->param;
     const size_t SIG = circl_hip_mldsa_sig_size(param);
     if (n == 0) return CIRCL_HIP_OK;
-    if (key_idx)
-        for (size_t i = 0; i < n; i++)
-            if (key_idx[i] >= t->nkeys) return CIRCL_HIP_EPARAM;
+    if (key_idx) TRY(check_key_idx(key_idx, n, t->nkeys));
     if (check_contexts(param, ctx_blob, ctx_off, n) == CTX_UNSUPPORTED) return CIRCL_HIP_EPARAM;
     return table_submit(t, ticket, [&](const circl_hip_keytable *, Coalescer *co, uint64_t *seq) {
         return coalesce_submit(co, n, {{sig, SIG}, {reinterpret_cast<const uint8_t *>(key_idx), size_t(4), false, false, true}},
@@ -1042,7 +1027,7 @@ int circl_hip_mldsa_sign_table_keyed_dev(const circl_hip_keytable *t, const uint
                                          const uint8_t *d_ctx_blob, const uint64_t *d_ctx_off, const uint8_t *d_rnd, int internal, uint8_t *d_sig, size_t n,
                                          void *d_ws, size_t ws_bytes, void *stream) {
     t = keytable_here(t);
-    if (!t || t->family != 2 || !t->private_keys || (reinterpret_cast<uintptr_t>(d_key_idx) & 3)) return CIRCL_HIP_EPARAM;
+    if (!t || t->family != 2 || !t->private_keys || !aligned<4>(d_key_idx)) return CIRCL_HIP_EPARAM;
     struct Park {  // (restored on every path)
         Park(const circl_hip_keytable *p, const uint32_t *k) { tl_sign_prepared = p; tl_sign_key_idx = k; }
         ~Park() { tl_sign_prepared = nullptr; tl_sign_key_idx = nullptr; }
@@ -1061,35 +1046,21 @@ int circl_hip_mldsa_sign_table_keyed(const circl_hip_keytable *t, const uint32_t
     const int param = t->param;
     const size_t SIG = circl_hip_mldsa_sig_size(param);
     if (n == 0) return CIRCL_HIP_OK;
-    if (key_idx)
-        for (size_t i = 0; i < n; i++)
-            if (key_idx[i] >= t->nkeys) return CIRCL_HIP_EPARAM;
+    if (key_idx) TRY(check_key_idx(key_idx, n, t->nkeys));
     if (check_contexts(param, ctx_blob, ctx_off, n) != CTX_OK) return CIRCL_HIP_EPARAM;  // sign.ErrContextTooLong / ErrContextNotSupported
     const PipeOpts opts = dsa_opts(size_t(1) << 13, true, /*depth=*/3);
     std::vector<uint8_t> zeros;
     if (!rnd) zeros.assign(32 * std::min(n, opts.chunk_items), 0);  // deterministic signing: 32 zero bytes per item
     return table_shard(t, n, [&](const circl_hip_keytable *r, size_t lo, size_t cnt) {
-        const uint32_t *ki = key_idx ? key_idx + lo : nullptr;
-        Coalescer *co = usable_coalescer(r);
-        if (co && cnt <= coalescer_call_max(co)) {  // a small call joins the table's cross-caller batch (absent rnd / key_idx: zeros)
-            const int rc = coalesce_run(co, cnt, {{rnd ? rnd + lo * 32 : nullptr, size_t(32), true, false, true}, {reinterpret_cast<const uint8_t *>(ki), size_t(4), false, false, true}},
-                                        {{msg_blob, msg_off + lo}, {ctx_blob, ctx_blob ? ctx_off + lo : nullptr}}, {{sig + lo * SIG, SIG}},
-                                        [&](size_t c) { return mldsa_sign_ws_any(param, c); }, opts, [&](Chunk &c) {
-                                            SignCtxOk checked;  // (every caller of the batch passed check_contexts)
-                                            return circl_hip_mldsa_sign_table_keyed_dev(r, reinterpret_cast<const uint32_t *>(c.in[1]), c.blob[0], c.off[0], c.blob[1],
-                                                                                        c.off[1], c.in[0], 0, c.out[0], c.cnt, c.ws, c.ws_bytes, c.st);
-                                        });
-            if (rc != kNotCoalesced) return rc;
-        }
-        std::vector<HIn> ins;
-        ins.push_back(rnd ? HIn{rnd + lo * 32, 32, true} : HIn{zeros.data(), zeros.size(), false, true});
-        ins.push_back(HIn{reinterpret_cast<const uint8_t *>(ki), ki ? size_t(4) : size_t(0)});
-        return run_pipeline(r->device, cnt, ins, {{msg_blob, msg_off + lo}, {ctx_blob, ctx_blob ? ctx_off + lo : nullptr}}, {{sig + lo * SIG, SIG}},
-                            [&](size_t c) { return mldsa_sign_ws_any(param, c); }, opts, [&](Chunk &c) {
-                                SignCtxOk checked;  // (check_contexts above)
-                                return circl_hip_mldsa_sign_table_keyed_dev(r, ki ? reinterpret_cast<const uint32_t *>(c.in[1]) : nullptr, c.blob[0], c.off[0], c.blob[1],
-                                                                            c.off[1], c.in[0], 0, c.out[0], c.cnt, c.ws, c.ws_bytes, c.st);
-                            });
+        // an absent rnd is rows of zeros in a cross-caller batch and ONE row of zeros for the whole call, re-staged with every chunk, in the pipeline
+        return table_coalesce_or_pipeline(r, cnt, {{rnd ? rnd + lo * 32 : nullptr, size_t(32), true, false, true}, {reinterpret_cast<const uint8_t *>(key_idx ? key_idx + lo : nullptr), size_t(4), false, false, true}},
+                                          1, {{msg_blob, msg_off + lo}, {ctx_blob, ctx_blob ? ctx_off + lo : nullptr}}, {{sig + lo * SIG, SIG}},
+                                          [&](size_t c) { return mldsa_sign_ws_any(param, c); }, opts, opts,
+                                          [&](Chunk &c, const uint32_t *d_key_idx) {
+                                              SignCtxOk checked;  // (check_contexts above, by every caller of a batch)
+                                              return circl_hip_mldsa_sign_table_keyed_dev(r, d_key_idx, c.blob[0], c.off[0], c.blob[1], c.off[1], c.in[0], 0, c.out[0], c.cnt,
+                                                                                          c.ws, c.ws_bytes, c.st);
+                                          }, {{size_t(0), HIn{zeros.data(), zeros.size(), false, true}}});
     }, kHeavyOneDeviceMax);
 }
 int circl_hip_mldsa_sign_table(const circl_hip_keytable *t, const uint8_t *msg_blob, const uint64_t *msg_off, const uint8_t *ctx_blob, const uint64_t *ctx_off,
@@ -1116,8 +1087,7 @@ int circl_hip_mldsa_verify_keyed(int param, const uint8_t *pk_table, size_t nkey
     if (!PK) return CIRCL_HIP_EPARAM;
     if (n == 0) return CIRCL_HIP_OK;
     if (nkeys == 0 || nkeys > 0xffffffffull) return CIRCL_HIP_EPARAM;
-    for (size_t i = 0; i < n; i++)
-        if (key_idx[i] >= nkeys) return CIRCL_HIP_EPARAM;
+    TRY(check_key_idx(key_idx, n, nkeys));
     if (check_contexts(param, ctx_blob, ctx_off, n) == CTX_UNSUPPORTED) return CIRCL_HIP_EPARAM;
     return shard(n, device, [&](int dev, size_t lo, size_t cnt) {
         return mldsa_verify_host_one<KM_KEYED>(param, dev, pk_table, nkeys, key_idx + lo, sig + lo * SIG, msg_blob, msg_off + lo, ctx_blob,
@@ -1136,7 +1106,7 @@ int circl_hip_mldsa_sample_in_ball(int param, const uint8_t *ctilde, uint32_t *p
     PipeOpts o;
     o.chunk_items = host_chunk_items(size_t(1) << 14);
     return shard(n, device, [&](int dev, size_t lo, size_t cnt) {
-        return run_pipeline(dev, cnt, {{ctilde + lo * CT, CT}}, {}, {{po + lo * 1024, 1024}}, [](size_t) { return size_t(0); }, o, [&](Chunk &c) {
+        return run_pipeline(dev, cnt, {{ctilde + lo * CT, CT}}, {}, {{po + lo * 1024, 1024}}, kNoWs, o, [&](Chunk &c) {
 #define CALL(M) hipLaunchKernelGGL(mldsa_sample_in_ball_kernel<M>, dim3((unsigned)c.cnt), dim3(64), 0, c.st, (const uint8_t *)c.in[0], \
                                    reinterpret_cast<uint32_t *>(c.out[0]), sequential)
             int rc = CIRCL_HIP_OK;

@@ -2,7 +2,7 @@
 //
 // There is deliberately no CPU path in this file: every compute entry point launches the HIP kernels of
 // mlkem_kernels.h or fails with CIRCL_HIP_ENODEV.
-#include "host_common.h"
+#include "host_compose.h"
 #include "keytable.h"
 #include "mlkem_kernels.h"
 
@@ -123,7 +123,7 @@ int encaps_dev_impl(const uint8_t *ek, const uint8_t *m, uint8_t *ct, uint8_t *s
     using Gm = circl::mlkem::Geom<K>;
     using namespace circl::mlkem;
     if (n == 0) return CIRCL_HIP_OK;
-    if (ws_bytes < kem_ws_min(n) || !aligned16(ws) || !aligned16(ek) || !aligned16(m) || !aligned16(ct) || !aligned16(ss))
+    if (ws_bytes < kem_ws_min(n) || !aligned<16>(ws, ek, m, ct, ss))
         return CIRCL_HIP_EWORKSPACE;
     KemWs w(ws, n);
     uint8_t *r_ws = w.slot0, *m_ws = w.slot1;
@@ -188,7 +188,7 @@ int encaps_shared_dev_impl(const uint8_t *ek, const uint8_t *m, uint8_t *ct, uin
     using Gm = circl::mlkem::Geom<K>;
     using namespace circl::mlkem;
     if (n == 0) return CIRCL_HIP_OK;
-    if (ws_bytes < kem_ws_min(n) || !aligned16(ws) || !aligned16(ek) || !aligned16(m) || !aligned16(ct) || !aligned16(ss))
+    if (ws_bytes < kem_ws_min(n) || !aligned<16>(ws, ek, m, ct, ss))
         return CIRCL_HIP_EWORKSPACE;
     KemWs w(ws, n);
     uint8_t *r_ws = w.slot0, *h_ws = w.slot1;
@@ -245,8 +245,7 @@ int encaps_keyed_dev_impl(const uint8_t *ek_table, size_t nkeys, const uint32_t 
     using namespace circl::mlkem;
     if (n == 0) return CIRCL_HIP_OK;
     if (nkeys == 0) return CIRCL_HIP_EPARAM;
-    if (ws_bytes < kem_ws_bytes(n) + kem_table_bytes<K>(nkeys) || !aligned16(ws) || !aligned16(ek_table) || !aligned16(m) || !aligned16(ct) ||
-        !aligned16(ss) || (reinterpret_cast<uintptr_t>(key_idx) & 3))
+    if (ws_bytes < kem_ws_bytes(n) + kem_table_bytes<K>(nkeys) || !aligned<16>(ws, ek_table, m, ct, ss) || !aligned<4>(key_idx))
         return CIRCL_HIP_EWORKSPACE;
     KemWs w(ws, n);
     const KeyIdx kx{key_idx, (uint32_t)(nkeys - 1)};  // a device index vector is bounded to the table on every read
@@ -285,7 +284,7 @@ int decaps_shared_dev_impl(const uint8_t *dk, const uint8_t *ct, uint8_t *ss, ui
     using Gm = circl::mlkem::Geom<K>;
     using namespace circl::mlkem;
     if (n == 0) return CIRCL_HIP_OK;
-    if (ws_bytes < kem_ws_min(n) || !aligned16(ws) || !aligned16(dk) || !aligned16(ct) || !aligned16(ss)) return CIRCL_HIP_EWORKSPACE;
+    if (ws_bytes < kem_ws_min(n) || !aligned<16>(ws, dk, ct, ss)) return CIRCL_HIP_EWORKSPACE;
     KemWs w(ws, n);
     uint8_t *mprime = w.slot0, *r_ws = w.slot1, *kbar = w.slot2, *ssrej = w.slot3;
     uint8_t *key_status = reinterpret_cast<uint8_t *>(w.work) + 128;  // second half of the ticket-counter slot
@@ -353,8 +352,8 @@ int decaps_keyed_dev_impl(const uint8_t *dk_table, size_t nkeys, const uint32_t 
     using namespace circl::mlkem;
     if (n == 0) return CIRCL_HIP_OK;
     if (nkeys == 0) return CIRCL_HIP_EPARAM;
-    if (ws_bytes < kem_ws_bytes(n) + kem_table_bytes<K>(nkeys) || !aligned16(ws) || !aligned16(dk_table) || !aligned16(ct) || !aligned16(ss) ||
-        (reinterpret_cast<uintptr_t>(key_idx) & 3))
+    if (ws_bytes < kem_ws_bytes(n) + kem_table_bytes<K>(nkeys) || !aligned<16>(ws, dk_table, ct, ss) ||
+        !aligned<4>(key_idx))
         return CIRCL_HIP_EWORKSPACE;
     KemWs w(ws, n);
     const KeyIdx kx{key_idx, (uint32_t)(nkeys - 1)};
@@ -401,7 +400,7 @@ int decaps_dev_impl(const uint8_t *dk, const uint8_t *ct, uint8_t *ss, uint8_t *
     using Gm = circl::mlkem::Geom<K>;
     using namespace circl::mlkem;
     if (n == 0) return CIRCL_HIP_OK;
-    if (ws_bytes < kem_ws_min(n) || !aligned16(ws) || !aligned16(dk) || !aligned16(ct) || !aligned16(ss)) return CIRCL_HIP_EWORKSPACE;
+    if (ws_bytes < kem_ws_min(n) || !aligned<16>(ws, dk, ct, ss)) return CIRCL_HIP_EWORKSPACE;
     KemWs w(ws, n);
     uint8_t *mprime = w.slot0, *r_ws = w.slot1, *kbar = w.slot2, *ssrej = w.slot3;
     if (R3) status = w.status_slot;
@@ -469,7 +468,7 @@ int keygen_dev_impl(const uint8_t *seed64, uint8_t *ek, uint8_t *dk, size_t n, v
     using Gm = circl::mlkem::Geom<K>;
     using namespace circl::mlkem;
     if (n == 0) return CIRCL_HIP_OK;
-    if (ws_bytes < kem_ws_min(n) || !aligned16(ws) || !aligned16(seed64) || !aligned16(ek) || !aligned16(dk)) return CIRCL_HIP_EWORKSPACE;
+    if (ws_bytes < kem_ws_min(n) || !aligned<16>(ws, seed64, ek, dk)) return CIRCL_HIP_EWORKSPACE;
     KemWs w(ws, n);
     uint8_t *rs = w.slot0;
     if (n <= kem_chain_item_batch()) {  // one launch, two wavefronts per key: G -> [PRF, NTT(s)] beside A, then t-hat, packing, H(ek) || z
@@ -520,14 +519,6 @@ std::function<size_t(size_t)> kem_ws_fn() {
     return [](size_t cnt) { return cnt <= (size_t(1) << 13) ? kem_ws_bytes(cnt) : kem_ws_min(cnt); };
 }
 
-// host-side check of a key-index vector (the device path trusts its caller: an out-of-range index would read past the table)
-int check_key_idx(const uint32_t *key_idx, size_t n, size_t nkeys) {
-    if (nkeys == 0 || nkeys > 0xffffffffull) return CIRCL_HIP_EPARAM;
-    for (size_t i = 0; i < n; i++)
-        if (key_idx[i] >= nkeys) return CIRCL_HIP_EPARAM;
-    return CIRCL_HIP_OK;
-}
-
 // ---- key tables that live across calls (keytable.h) ------------------------------------------------------------------------------
 // The table memory has the layout of the per-call key tables' workspace tail (kem_table_bytes): A^T rows of whole groups, H(ek)
 // per entry, a status byte per entry.  key_idx == nullptr: every item uses entry 0 (the kernels see key stride 0).
@@ -552,7 +543,7 @@ int encaps_table_dev_impl(const circl_hip_keytable *t, const uint32_t *key_idx, 
     using Gm = circl::mlkem::Geom<K>;
     using namespace circl::mlkem;
     if (n == 0) return CIRCL_HIP_OK;
-    if (ws_bytes < kem_ws_min(n) || !aligned16(ws) || !aligned16(m) || !aligned16(ct) || !aligned16(ss) || (reinterpret_cast<uintptr_t>(key_idx) & 3))
+    if (ws_bytes < kem_ws_min(n) || !aligned<16>(ws, m, ct, ss) || !aligned<4>(key_idx))
         return CIRCL_HIP_EWORKSPACE;
     KemWs w(ws, n);
     const KeyIdx kx{key_idx, (uint32_t)(t->nkeys - 1)};
@@ -593,7 +584,7 @@ int decaps_table_dev_impl(const circl_hip_keytable *t, const uint32_t *key_idx, 
     using Gm = circl::mlkem::Geom<K>;
     using namespace circl::mlkem;
     if (n == 0) return CIRCL_HIP_OK;
-    if (ws_bytes < kem_ws_min(n) || !aligned16(ws) || !aligned16(ct) || !aligned16(ss) || (reinterpret_cast<uintptr_t>(key_idx) & 3)) return CIRCL_HIP_EWORKSPACE;
+    if (ws_bytes < kem_ws_min(n) || !aligned<16>(ws, ct, ss) || !aligned<4>(key_idx)) return CIRCL_HIP_EWORKSPACE;
     KemWs w(ws, n);
     const KeyIdx kx{key_idx, (uint32_t)(t->nkeys - 1)};
     uint8_t *mprime = w.slot0, *r_ws = w.slot1, *kbar = w.slot2, *ssrej = w.slot3;
@@ -745,11 +736,7 @@ int circl_hip_mlkem_encaps(int param, const uint8_t *ek, const uint8_t *m, uint8
         // circl_hip_set_coalesce: the small calls of concurrent callers share launches -- a TLS server's shape: every handshake
         // encapsulates once, to a key of its own (kem/hybrid/hybrid.go:95-99 -> kem/mlkem/mlkem768/kyber.go:359-370)
         Coalescer *co = all_inputs_present(ins) ? call_coalescer(kCoKemEncaps, kem_k(param) - 2, dev) : nullptr;
-        if (co) {
-            const int rc = coalesce_run(co, cnt, ins, {}, outs, kem_ws_fn(), kem_opts(), launch);
-            if (rc != kNotCoalesced) return rc;
-        }
-        return run_pipeline(dev, cnt, ins, {}, outs, kem_ws_fn(), kem_opts(), launch);
+        return coalesce_or_pipeline(co, dev, cnt, ins, {}, outs, kem_ws_fn(), kem_opts(), launch);
     });
 }
 
@@ -760,12 +747,8 @@ int circl_hip_mlkem_decaps(int param, const uint8_t *dk, const uint8_t *ct, uint
         const std::vector<HIn> ins = {{dk + lo * DK, DK, true}, {ct + lo * CT, CT}};
         const std::vector<HOut> outs = {{ss + lo * 32, 32, true}, {status ? status + lo : nullptr, 1}};
         auto launch = [&](Chunk &c) { return circl_hip_mlkem_decaps_dev(param, c.in[0], c.in[1], c.out[0], c.out[1], c.cnt, c.ws, c.ws_bytes, c.st); };
-        Coalescer *co = all_inputs_present(ins) ? call_coalescer(kCoKemDecaps, kem_k(param) - 2, dev) : nullptr;
-        if (co) {  // circl_hip_set_coalesce: the small calls of concurrent callers share launches
-            const int rc = coalesce_run(co, cnt, ins, {}, outs, kem_ws_fn(), kem_opts(), launch);
-            if (rc != kNotCoalesced) return rc;
-        }
-        return run_pipeline(dev, cnt, ins, {}, outs, kem_ws_fn(), kem_opts(), launch);
+        Coalescer *co = all_inputs_present(ins) ? call_coalescer(kCoKemDecaps, kem_k(param) - 2, dev) : nullptr;  // (circl_hip_set_coalesce, as above)
+        return coalesce_or_pipeline(co, dev, cnt, ins, {}, outs, kem_ws_fn(), kem_opts(), launch);
     });
 }
 
@@ -807,7 +790,8 @@ int circl_hip_mlkem_encaps_keyed(int param, const uint8_t *ek_table, size_t nkey
     const size_t EK = circl_hip_mlkem_ek_size(param), CT = circl_hip_mlkem_ct_size(param);
     if (!EK) return CIRCL_HIP_EPARAM;
     if (n == 0) return CIRCL_HIP_OK;
-    if (int rc = check_key_idx(key_idx, n, nkeys)) return rc;
+    if (nkeys == 0 || nkeys > 0xffffffffull) return CIRCL_HIP_EPARAM;
+    TRY(check_key_idx(key_idx, n, nkeys));
     return shard(n, device, [&](int dev, size_t lo, size_t cnt) {
         return run_pipeline(dev, cnt, {{ek_table, EK * nkeys, false, true}, {reinterpret_cast<const uint8_t *>(key_idx + lo), 4}, {m + lo * 32, 32, true}}, {},
                             {{ct + lo * CT, CT}, {ss + lo * 32, 32, true}, {status ? status + lo : nullptr, 1}},
@@ -822,7 +806,8 @@ int circl_hip_mlkem_decaps_keyed(int param, const uint8_t *dk_table, size_t nkey
     const size_t DK = circl_hip_mlkem_dk_size(param), CT = circl_hip_mlkem_ct_size(param);
     if (!DK) return CIRCL_HIP_EPARAM;
     if (n == 0) return CIRCL_HIP_OK;
-    if (int rc = check_key_idx(key_idx, n, nkeys)) return rc;
+    if (nkeys == 0 || nkeys > 0xffffffffull) return CIRCL_HIP_EPARAM;
+    TRY(check_key_idx(key_idx, n, nkeys));
     return shard(n, device, [&](int dev, size_t lo, size_t cnt) {
         return run_pipeline(dev, cnt, {{dk_table, DK * nkeys, true, true}, {reinterpret_cast<const uint8_t *>(key_idx + lo), 4}, {ct + lo * CT, CT}}, {},
                             {{ss + lo * 32, 32, true}, {status ? status + lo : nullptr, 1}},
@@ -910,48 +895,26 @@ int circl_hip_mlkem_encaps_table(const circl_hip_keytable *t, const uint32_t *ke
     if (!kem_table_ok(t, 0)) return CIRCL_HIP_EPARAM;
     const size_t CT = circl_hip_mlkem_ct_size(t->param);
     if (n == 0) return CIRCL_HIP_OK;
-    if (key_idx)
-        if (int rc = check_key_idx(key_idx, n, t->nkeys)) return rc;
-    return table_shard(t, n, [&](const circl_hip_keytable *r, size_t lo, size_t cnt) {
-        const uint32_t *ki = key_idx ? key_idx + lo : nullptr;
-        Coalescer *co = usable_coalescer(r);
-        if (co && cnt <= coalescer_call_max(co)) {  // a small call joins the table's cross-caller batch (an absent key_idx: zeros)
-            const int rc = coalesce_run(co, cnt, kem_enc_ins(ki, m ? m + lo * 32 : nullptr), {},
-                                        {{ct + lo * CT, CT}, {ss + lo * 32, 32, true}, {status ? status + lo : nullptr, 1}}, kem_ws_fn(), kem_opts(), [&](Chunk &c) {
-                                            return circl_hip_mlkem_encaps_table_dev(r, reinterpret_cast<const uint32_t *>(c.in[0]), c.in[1], c.out[0], c.out[1], c.out[2],
-                                                                                    c.cnt, c.ws, c.ws_bytes, c.st);
-                                        });
-            if (rc != kNotCoalesced) return rc;
-        }
-        return run_pipeline(r->device, cnt, {{reinterpret_cast<const uint8_t *>(ki), ki ? size_t(4) : size_t(0)}, {m ? m + lo * 32 : nullptr, 32, true}}, {},
-                            {{ct + lo * CT, CT}, {ss + lo * 32, 32, true}, {status ? status + lo : nullptr, 1}}, kem_ws_fn(), kem_opts(), [&](Chunk &c) {
-                                return circl_hip_mlkem_encaps_table_dev(r, ki ? reinterpret_cast<const uint32_t *>(c.in[0]) : nullptr, c.in[1], c.out[0], c.out[1],
-                                                                        c.out[2], c.cnt, c.ws, c.ws_bytes, c.st);
-                            });
+    if (key_idx) TRY(check_key_idx(key_idx, n, t->nkeys));
+    return table_shard(t, n, [&](const circl_hip_keytable *r, size_t lo, size_t cnt) {  // (a small call joins the table's cross-caller batch)
+        return table_coalesce_or_pipeline(r, cnt, kem_enc_ins(key_idx ? key_idx + lo : nullptr, m ? m + lo * 32 : nullptr), 0, {},
+                                          {{ct + lo * CT, CT}, {ss + lo * 32, 32, true}, {status ? status + lo : nullptr, 1}}, kem_ws_fn(), kem_opts(), kem_opts(),
+                                          [&](Chunk &c, const uint32_t *d_key_idx) {
+                                              return circl_hip_mlkem_encaps_table_dev(r, d_key_idx, c.in[1], c.out[0], c.out[1], c.out[2], c.cnt, c.ws, c.ws_bytes, c.st);
+                                          });
     });
 }
 int circl_hip_mlkem_decaps_table(const circl_hip_keytable *t, const uint32_t *key_idx, const uint8_t *ct, uint8_t *ss, uint8_t *status, size_t n) {
     if (!kem_table_ok(t, 1)) return CIRCL_HIP_EPARAM;
     const size_t CT = circl_hip_mlkem_ct_size(t->param);
     if (n == 0) return CIRCL_HIP_OK;
-    if (key_idx)
-        if (int rc = check_key_idx(key_idx, n, t->nkeys)) return rc;
+    if (key_idx) TRY(check_key_idx(key_idx, n, t->nkeys));
     return table_shard(t, n, [&](const circl_hip_keytable *r, size_t lo, size_t cnt) {
-        const uint32_t *ki = key_idx ? key_idx + lo : nullptr;
-        Coalescer *co = usable_coalescer(r);
-        if (co && cnt <= coalescer_call_max(co)) {
-            const int rc = coalesce_run(co, cnt, kem_dec_ins(ki, ct ? ct + lo * CT : nullptr, CT), {},
-                                        {{ss + lo * 32, 32, true}, {status ? status + lo : nullptr, 1}}, kem_ws_fn(), kem_opts(), [&](Chunk &c) {
-                                            return circl_hip_mlkem_decaps_table_dev(r, reinterpret_cast<const uint32_t *>(c.in[0]), c.in[1], c.out[0], c.out[1], c.cnt,
-                                                                                    c.ws, c.ws_bytes, c.st);
-                                        });
-            if (rc != kNotCoalesced) return rc;
-        }
-        return run_pipeline(r->device, cnt, {{reinterpret_cast<const uint8_t *>(ki), ki ? size_t(4) : size_t(0)}, {ct ? ct + lo * CT : nullptr, CT}}, {},
-                            {{ss + lo * 32, 32, true}, {status ? status + lo : nullptr, 1}}, kem_ws_fn(), kem_opts(), [&](Chunk &c) {
-                                return circl_hip_mlkem_decaps_table_dev(r, ki ? reinterpret_cast<const uint32_t *>(c.in[0]) : nullptr, c.in[1], c.out[0], c.out[1],
-                                                                        c.cnt, c.ws, c.ws_bytes, c.st);
-                            });
+        return table_coalesce_or_pipeline(r, cnt, kem_dec_ins(key_idx ? key_idx + lo : nullptr, ct ? ct + lo * CT : nullptr, CT), 0, {},
+                                          {{ss + lo * 32, 32, true}, {status ? status + lo : nullptr, 1}}, kem_ws_fn(), kem_opts(), kem_opts(),
+                                          [&](Chunk &c, const uint32_t *d_key_idx) {
+                                              return circl_hip_mlkem_decaps_table_dev(r, d_key_idx, c.in[1], c.out[0], c.out[1], c.cnt, c.ws, c.ws_bytes, c.st);
+                                          });
     });
 }
 // ---- the asynchronous form (include/circl_hip.h: circl_hip_keytable_async_start) ----
@@ -961,8 +924,7 @@ int circl_hip_mlkem_encaps_table_submit(const circl_hip_keytable *t, const uint3
     if (!kem_table_ok(t, 0) || !ticket || (n && (!m || !ct || !ss))) return CIRCL_HIP_EPARAM;
     const size_t CT = circl_hip_mlkem_ct_size(t->param);
     if (n == 0) return CIRCL_HIP_OK;
-    if (key_idx)
-        if (int rc = check_key_idx(key_idx, n, t->nkeys)) return rc;
+    if (key_idx) TRY(check_key_idx(key_idx, n, t->nkeys));
     return table_submit(t, ticket, [&](const circl_hip_keytable *, Coalescer *co, uint64_t *seq) {
         return coalesce_submit(co, n, kem_enc_ins(key_idx, m), {}, {{ct, CT}, {ss, 32, true}, {status, 1}}, seq, false);
     });
@@ -973,8 +935,7 @@ int circl_hip_mlkem_decaps_table_submit(const circl_hip_keytable *t, const uint3
     if (!kem_table_ok(t, 1) || !ticket || (n && (!ct || !ss))) return CIRCL_HIP_EPARAM;
     const size_t CT = circl_hip_mlkem_ct_size(t->param);
     if (n == 0) return CIRCL_HIP_OK;
-    if (key_idx)
-        if (int rc = check_key_idx(key_idx, n, t->nkeys)) return rc;
+    if (key_idx) TRY(check_key_idx(key_idx, n, t->nkeys));
     return table_submit(t, ticket, [&](const circl_hip_keytable *, Coalescer *co, uint64_t *seq) {
         return coalesce_submit(co, n, kem_dec_ins(key_idx, ct, CT), {}, {{ss, 32, true}, {status, 1}}, seq, false);
     });

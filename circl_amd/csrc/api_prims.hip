@@ -1,7 +1,7 @@
 // api_prims.hip -- the unit-level primitives (Keccak-f, ring transforms, sponges) and the batched XOF / KangarooTwelve
 // service of the C ABI (include/circl_hip.h).  No CPU compute path: the KangarooTwelve host code only lays out the tree's
 // nodes; every permutation runs on the device.
-#include "host_common.h"
+#include "host_compose.h"
 #include "prim_kernels.h"
 #include "sampler_prims.h"
 
@@ -13,7 +13,6 @@ PipeOpts prim_opts(size_t row_bytes) {
     o.chunk_items = host_chunk_items(std::max<size_t>(size_t(1) << 10, (size_t(32) << 20) / std::max<size_t>(row_bytes, 1)));  // ~32 MB per chunk
     return o;
 }
-const std::function<size_t(size_t)> no_ws = [](size_t) { return size_t(0); };
 }  // namespace
 
 extern "C" {
@@ -22,7 +21,7 @@ int circl_hip_keccak_f1600(uint64_t *states, size_t n, int rounds, int device) {
     if (rounds != 24 && rounds != 12) return CIRCL_HIP_EPARAM;
     uint8_t *p = reinterpret_cast<uint8_t *>(states);
     return shard(n, device, [&](int dev, size_t lo, size_t cnt) {
-        return run_pipeline(dev, cnt, {{p + lo * 200, 200}}, {}, {{p + lo * 200, 200}}, no_ws, prim_opts(200), [&](Chunk &c) {
+        return run_pipeline(dev, cnt, {{p + lo * 200, 200}}, {}, {{p + lo * 200, 200}}, kNoWs, prim_opts(200), [&](Chunk &c) {
             HIP_TRY(hipMemcpyAsync(c.out[0], c.in[0], c.cnt * 200, hipMemcpyDeviceToDevice, c.st));
             hipLaunchKernelGGL(circl::prim::keccak_f1600_kernel, dim3((unsigned)((c.cnt + 255) / 256)), dim3(256), 0, c.st,
                                reinterpret_cast<uint64_t *>(c.out[0]), c.cnt, 24 - rounds);
@@ -79,7 +78,7 @@ int circl_hip_profile_valu_probe(int device, int waves_per_simd, double *keccak_
 int circl_hip_keccak_f1600_coop(uint64_t *states, size_t n, int device) {
     uint8_t *p = reinterpret_cast<uint8_t *>(states);
     return shard(n, device, [&](int dev, size_t lo, size_t cnt) {
-        return run_pipeline(dev, cnt, {{p + lo * 200, 200}}, {}, {{p + lo * 200, 200}}, no_ws, prim_opts(200), [&](Chunk &c) {
+        return run_pipeline(dev, cnt, {{p + lo * 200, 200}}, {}, {{p + lo * 200, 200}}, kNoWs, prim_opts(200), [&](Chunk &c) {
             HIP_TRY(hipMemcpyAsync(c.out[0], c.in[0], c.cnt * 200, hipMemcpyDeviceToDevice, c.st));
             hipLaunchKernelGGL(circl::prim::keccak_f1600_coop_kernel, dim3((unsigned)c.cnt), dim3(64), 0, c.st, reinterpret_cast<uint64_t *>(c.out[0]));
             HIP_TRY(hipGetLastError());
@@ -91,7 +90,7 @@ int circl_hip_keccak_f1600_coop(uint64_t *states, size_t n, int device) {
 int circl_hip_keccak_f1600_split(uint64_t *states, size_t n, int device) {
     uint8_t *p = reinterpret_cast<uint8_t *>(states);
     return shard(n, device, [&](int dev, size_t lo, size_t cnt) {
-        return run_pipeline(dev, cnt, {{p + lo * 200, 200}}, {}, {{p + lo * 200, 200}}, no_ws, prim_opts(200), [&](Chunk &c) {
+        return run_pipeline(dev, cnt, {{p + lo * 200, 200}}, {}, {{p + lo * 200, 200}}, kNoWs, prim_opts(200), [&](Chunk &c) {
             HIP_TRY(hipMemcpyAsync(c.out[0], c.in[0], c.cnt * 200, hipMemcpyDeviceToDevice, c.st));
             hipLaunchKernelGGL(circl::prim::keccak_f1600_split_kernel, dim3((unsigned)((2 * c.cnt + 255) / 256)), dim3(256), 0, c.st,
                                reinterpret_cast<uint64_t *>(c.out[0]), c.cnt);
@@ -111,7 +110,7 @@ int circl_hip_kyber_ntt(int16_t *polys, size_t n, int inverse, int device) {
                  : xch == circl::kyber::XCH_LANES  ? circl::prim::kyber_ntt_kernel<circl::kyber::XCH_LANES>
                                                    : circl::prim::kyber_ntt_kernel<circl::kyber::XCH_LANES_TOP>;
     return shard(n, device, [&](int dev, size_t lo, size_t cnt) {
-        return run_pipeline(dev, cnt, {{p + lo * 512, 512}}, {}, {{p + lo * 512, 512}}, no_ws, prim_opts(512), [&](Chunk &c) {
+        return run_pipeline(dev, cnt, {{p + lo * 512, 512}}, {}, {{p + lo * 512, 512}}, kNoWs, prim_opts(512), [&](Chunk &c) {
             HIP_TRY(hipMemcpyAsync(c.out[0], c.in[0], c.cnt * 512, hipMemcpyDeviceToDevice, c.st));
             hipLaunchKernelGGL(kern, dim3((unsigned)c.cnt), dim3(64), 0, c.st, reinterpret_cast<int16_t *>(c.out[0]), inverse);
             HIP_TRY(hipGetLastError());
@@ -123,7 +122,7 @@ int circl_hip_kyber_ntt(int16_t *polys, size_t n, int inverse, int device) {
 int circl_hip_dilithium_ntt(uint32_t *polys, size_t n, int inverse, int device) {
     uint8_t *p = reinterpret_cast<uint8_t *>(polys);
     return shard(n, device, [&](int dev, size_t lo, size_t cnt) {
-        return run_pipeline(dev, cnt, {{p + lo * 1024, 1024}}, {}, {{p + lo * 1024, 1024}}, no_ws, prim_opts(1024), [&](Chunk &c) {
+        return run_pipeline(dev, cnt, {{p + lo * 1024, 1024}}, {}, {{p + lo * 1024, 1024}}, kNoWs, prim_opts(1024), [&](Chunk &c) {
             HIP_TRY(hipMemcpyAsync(c.out[0], c.in[0], c.cnt * 1024, hipMemcpyDeviceToDevice, c.st));
             hipLaunchKernelGGL(circl::prim::dilithium_ntt_kernel, dim3((unsigned)c.cnt), dim3(64), 0, c.st, reinterpret_cast<uint32_t *>(c.out[0]), inverse);
             HIP_TRY(hipGetLastError());
@@ -136,7 +135,7 @@ int circl_hip_kyber_mulhat(int16_t *out, const int16_t *a, const int16_t *b, siz
     uint8_t *po = reinterpret_cast<uint8_t *>(out);
     const uint8_t *pa = reinterpret_cast<const uint8_t *>(a), *pb = reinterpret_cast<const uint8_t *>(b);
     return shard(n, device, [&](int dev, size_t lo, size_t cnt) {
-        return run_pipeline(dev, cnt, {{pa + lo * 512, 512}, {pb + lo * 512, 512}}, {}, {{po + lo * 512, 512}}, no_ws, prim_opts(512), [&](Chunk &c) {
+        return run_pipeline(dev, cnt, {{pa + lo * 512, 512}, {pb + lo * 512, 512}}, {}, {{po + lo * 512, 512}}, kNoWs, prim_opts(512), [&](Chunk &c) {
             hipLaunchKernelGGL(circl::prim::kyber_mulhat_kernel, dim3((unsigned)c.cnt), dim3(64), 0, c.st, reinterpret_cast<int16_t *>(c.out[0]),
                                reinterpret_cast<const int16_t *>(c.in[0]), reinterpret_cast<const int16_t *>(c.in[1]));
             HIP_TRY(hipGetLastError());
@@ -152,7 +151,7 @@ int circl_hip_shake(int rate, int ds, const uint8_t *in, size_t inlen, uint8_t *
     const uint8_t *src = in;
     if (!inlen) { pad.assign(n, 0); src = pad.data(); }
     return shard(n, device, [&](int dev, size_t lo, size_t cnt) {
-        return run_pipeline(dev, cnt, {{src + lo * il, il}}, {}, {{out + lo * outlen, outlen}}, no_ws, prim_opts(il + outlen), [&](Chunk &c) {
+        return run_pipeline(dev, cnt, {{src + lo * il, il}}, {}, {{out + lo * outlen, outlen}}, kNoWs, prim_opts(il + outlen), [&](Chunk &c) {
             // the kernel strides inputs by `inlen`; empty inputs never dereference
             hipLaunchKernelGGL(circl::prim::sponge_kernel, dim3((unsigned)((c.cnt + 255) / 256)), dim3(256), 0, c.st, rate / 8, (uint32_t)ds, 0,
                                (const uint8_t *)c.in[0], inlen, (const uint64_t *)nullptr, c.out[0], outlen, c.cnt);
@@ -170,7 +169,7 @@ int circl_hip_lane_op(int op, int arg, const uint32_t *a, const uint32_t *b, uin
     return shard(n, device, [&](int dev, size_t lo, size_t cnt) {
         std::vector<HIn> ins = {{pa + lo * 4, 4}};
         if (pb) ins.push_back({pb + lo * 4, 4});
-        return run_pipeline(dev, cnt, ins, {}, {{p0 + lo * 4, 4}, {p1 ? p1 + lo * 4 : nullptr, 4}}, no_ws, prim_opts(16), [&](Chunk &c) {
+        return run_pipeline(dev, cnt, ins, {}, {{p0 + lo * 4, 4}, {p1 ? p1 + lo * 4 : nullptr, 4}}, kNoWs, prim_opts(16), [&](Chunk &c) {
             hipLaunchKernelGGL(circl::prim::lane_op_kernel, dim3((unsigned)((c.cnt + 255) / 256)), dim3(256), 0, c.st, op, arg,
                                reinterpret_cast<const uint32_t *>(c.in[0]), pb ? reinterpret_cast<const uint32_t *>(c.in[1]) : nullptr,
                                reinterpret_cast<uint32_t *>(c.out[0]), p1 ? reinterpret_cast<uint32_t *>(c.out[1]) : nullptr, c.cnt);
@@ -185,7 +184,7 @@ int circl_hip_kyber_sample_uniform(const uint8_t *seed32, const uint8_t *xy, int
     PipeOpts o = prim_opts(512);
     o.chunk_items = (o.chunk_items + 63) & ~size_t(63);
     return shard(n, device, [&](int dev, size_t lo, size_t cnt) {
-        return run_pipeline(dev, cnt, {{seed32 + lo * 32, 32}, {xy + lo * 2, 2}}, {}, {{po + lo * 512, 512}}, no_ws, o, [&](Chunk &c) {
+        return run_pipeline(dev, cnt, {{seed32 + lo * 32, 32}, {xy + lo * 2, 2}}, {}, {{po + lo * 512, 512}}, kNoWs, o, [&](Chunk &c) {
             hipLaunchKernelGGL(circl::prim::kyber_uniform_prim_kernel, dim3((unsigned)((c.cnt + 63) / 64)), dim3(64), circl::mlkem::Geom<3>::LDS_FIFO, c.st,
                                (const uint8_t *)c.in[0], (const uint8_t *)c.in[1], reinterpret_cast<int16_t *>(c.out[0]), c.cnt);
             HIP_TRY(hipGetLastError());
@@ -199,7 +198,7 @@ int circl_hip_kyber_sample_cbd(int eta, const uint8_t *seed32, int16_t *polys, s
     constexpr size_t ROW = 64 * 512;  // 64 nonces x 256 int16
     uint8_t *po = reinterpret_cast<uint8_t *>(polys);
     return shard(n, device, [&](int dev, size_t lo, size_t cnt) {
-        return run_pipeline(dev, cnt, {{seed32 + lo * 32, 32}}, {}, {{po + lo * ROW, ROW}}, no_ws, prim_opts(ROW), [&](Chunk &c) {
+        return run_pipeline(dev, cnt, {{seed32 + lo * 32, 32}}, {}, {{po + lo * ROW, ROW}}, kNoWs, prim_opts(ROW), [&](Chunk &c) {
             if (eta == 2)
                 hipLaunchKernelGGL(circl::prim::kyber_cbd_prim_kernel<3>, dim3((unsigned)c.cnt), dim3(64), 0, c.st, (const uint8_t *)c.in[0],
                                    reinterpret_cast<int16_t *>(c.out[0]), c.cnt);
@@ -242,7 +241,7 @@ int circl_hip_xof(int rate, int ds, int rounds, const uint8_t *in_blob, const ui
     // messages are ragged: bound a chunk by its item count only (blob bytes of a chunk are whatever its offsets span)
     o.chunk_items = host_chunk_items(size_t(1) << 16);
     return shard(n, device, [&](int dev, size_t lo, size_t cnt) {
-        return run_pipeline(dev, cnt, {}, {{in_blob, in_off + lo}}, {{out + lo * outlen, outlen}}, no_ws, o, [&](Chunk &c) {
+        return run_pipeline(dev, cnt, {}, {{in_blob, in_off + lo}}, {{out + lo * outlen, outlen}}, kNoWs, o, [&](Chunk &c) {
             hipLaunchKernelGGL(circl::prim::sponge_kernel, dim3((unsigned)((c.cnt + 255) / 256)), dim3(256), 0, c.st, rate / 8, (uint32_t)ds, 24 - rounds,
                                c.blob[0], (size_t)0, c.off[0], c.out[0], outlen, c.cnt);
             HIP_TRY(hipGetLastError());

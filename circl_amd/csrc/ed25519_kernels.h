@@ -177,12 +177,5 @@ static __global__ __launch_bounds__(64) void eddilithium2_seed_kernel(const uint
     }
 }
 
-// ok[i] = a[i] & b[i] (Ed25519-Dilithium2 verification: both halves must hold)
-static __global__ __launch_bounds__(64) void and_verdicts_kernel(const uint8_t *__restrict__ a, const uint8_t *__restrict__ b, uint8_t *__restrict__ ok,
-                                                                 size_t n) {
-    const size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
-    if (i < n) ok[i] = (uint8_t)((a[i] != 0) & (b[i] != 0));
-}
-
 }  // namespace ed25519
 }  // namespace circl

@@ -195,11 +195,5 @@ static __global__ __launch_bounds__(64) void eddilithium3_seed_kernel(const uint
     store_row(seed_e + i * 57, e, 57);
 }
 
-// ok[i] = a[i] & b[i] (Ed448-Dilithium3 verification: both halves must hold)
-static __global__ __launch_bounds__(64) void and_verdicts448_kernel(const uint8_t *__restrict__ a, const uint8_t *__restrict__ b, uint8_t *__restrict__ ok, size_t n) {
-    const size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
-    if (i < n) ok[i] = (uint8_t)((a[i] != 0) & (b[i] != 0));
-}
-
 }  // namespace ed448
 }  // namespace circl

@@ -43,7 +43,6 @@ extern thread_local std::string g_err;
     } while (0)
 
 inline size_t up256(size_t x) { return (x + 255) & ~size_t(255); }
-inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // ---- devices ----------------------------------------------------------------------------------
 int ndev();                      // LOGICAL devices (0 if none), fixed at first call: the HIP devices of the process unless
@@ -258,6 +257,16 @@ inline bool all_inputs_present(const std::vector<HIn> &ins) {
     for (auto &in : ins)
         if (!in.p) return false;
     return true;
+}
+// One call of such an entry point on device `dev`: it joins a batch of `co` (what call_coalescer gave: nullptr = none) or, where it cannot,
+// goes through the pipeline -- the same arrays, workspace rule, options and launch either way.
+static inline int coalesce_or_pipeline(Coalescer *co, int dev, size_t n, const std::vector<HIn> &ins, const std::vector<HBlob> &blobs, const std::vector<HOut> &outs,
+                                const std::function<size_t(size_t)> &ws_bytes, const PipeOpts &opts, const std::function<int(Chunk &)> &launch) {
+    if (co) {
+        const int rc = coalesce_run(co, n, ins, blobs, outs, ws_bytes, opts, launch);
+        if (rc != kNotCoalesced) return rc;
+    }
+    return run_pipeline(dev, n, ins, blobs, outs, ws_bytes, opts, launch);
 }
 
 // Contiguous split of [0,n) over the visible devices, one host thread each (pinned to the device's NUMA node), no collective.

@@ -14,6 +14,9 @@
 
 #include <atomic>
 #include <functional>
+#include <initializer_list>
+#include <utility>
+#include <vector>
 
 namespace circl {
 namespace host {
@@ -107,6 +110,28 @@ template <class F> int table_shard(const circl_hip_keytable *t, size_t n, F one,
     auto part = [&](const circl_hip_keytable *r, size_t lo, size_t cnt) { TableUse use(r); return one(r, lo, cnt); };
     if (n <= one_replica_max && t->nreplica > 0) return part(t->replica[next_replica(t->nreplica)], size_t(0), n);
     return shard(n, CIRCL_HIP_ALL_DEVICES, [&](int dev, size_t lo, size_t cnt) { return part(t->replica[dev], lo, cnt); });
+}
+// The host-buffer call of n items through `r` (one part of a table, TableUse held): a small call joins the cross-caller batch of the table's
+// coalescer, any other -- or one the coalescer turns away -- goes through the pipeline.  The arrays are said once, in the coalescer's form:
+// ins[ki_slot] is the OPTIONAL key_idx vector (rows of 4 bytes).  Absent (p == nullptr: entry 0 for every item) it is rows of zeros in a batch,
+// whose shape is fixed, and nothing at all in the pipeline, where the launch then gets nullptr; launch(chunk, d_key_idx) is written once.
+// `piped_absent`: (slot, replacement) of further optional inputs that the pipeline stages differently when they are absent.
+template <class Launch>
+int table_coalesce_or_pipeline(const circl_hip_keytable *r, size_t n, std::vector<HIn> ins, size_t ki_slot, const std::vector<HBlob> &blobs,
+                               const std::vector<HOut> &outs, const std::function<size_t(size_t)> &ws_bytes, const PipeOpts &coalesced_opts,
+                               const PipeOpts &piped_opts, Launch launch, std::initializer_list<std::pair<size_t, HIn>> piped_absent = {}) {
+    Coalescer *co = usable_coalescer(r);
+    if (co && n <= coalescer_call_max(co)) {
+        const int rc = coalesce_run(co, n, ins, blobs, outs, ws_bytes, coalesced_opts,
+                                    [&](Chunk &c) { return launch(c, reinterpret_cast<const uint32_t *>(c.in[ki_slot])); });
+        if (rc != kNotCoalesced) return rc;
+    }
+    const bool keyed = ins[ki_slot].p != nullptr;
+    if (!keyed) ins[ki_slot].row = 0;
+    for (auto &a : piped_absent)
+        if (!ins[a.first].p) ins[a.first] = a.second;
+    return run_pipeline(r->device, n, ins, blobs, outs, ws_bytes, piped_opts,
+                        [&](Chunk &c) { return launch(c, keyed ? reinterpret_cast<const uint32_t *>(c.in[ki_slot]) : nullptr); });
 }
 // the asynchronous queues of the two families (api_mlkem.hip, api_mldsa.hip): fix the queue's arrays and launch on `co`, start its dispatcher
 int kem_table_async_start(const circl_hip_keytable *r, Coalescer *co, bool want_eventfd);

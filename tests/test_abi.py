@@ -162,3 +162,142 @@ def test_route_check_knows_the_librarys_defaults():
             assert compiled == -1 and re.search(r"k <= 6 \? 9 : 8", src) and dflt == (8 if case.endswith("87") else 9)
         else:
             assert compiled == dflt, (knob, compiled, dflt)
+
+
+# The argument contract of the host entry points around the composite schemes: what they answer BEFORE they look for a device (so the
+# same codes hold with and without one).  "B" = a valid buffer, "K" = the key indices [5, 0], "C" = the context offsets [0, 256] (one
+# context of 256 bytes: over ed448.ContextMaxSize), None = NULL.  The codes are what the library answered before the composite schemes'
+# host glue was folded into shared helpers: 0 = CIRCL_HIP_OK, -1 = CIRCL_HIP_EPARAM.
+_NO_DEVICE_NEEDED = [
+    # n == 0 comes first, then NULL arguments
+    ("circl_hip_eddilithium2_keygen", (None, None, None, 0, 0), 0),
+    ("circl_hip_eddilithium2_keygen", (None, "B", "B", 1, 0), -1),
+    ("circl_hip_eddilithium2_keygen", ("B", None, "B", 1, 0), -1),
+    ("circl_hip_eddilithium2_keygen", ("B", "B", None, 1, 0), -1),
+    ("circl_hip_eddilithium2_sign", (None, None, None, None, 0, 0), 0),
+    ("circl_hip_eddilithium2_sign", (None, "B", "B", "B", 1, 0), -1),
+    ("circl_hip_eddilithium2_sign", ("B", "B", None, "B", 1, 0), -1),
+    ("circl_hip_eddilithium2_sign", ("B", "B", "B", None, 1, 0), -1),
+    ("circl_hip_eddilithium2_verify", (None, None, None, None, None, 0, 0), 0),
+    ("circl_hip_eddilithium2_verify", (None, "B", "B", "B", "B", 1, 0), -1),
+    ("circl_hip_eddilithium2_verify", ("B", None, "B", "B", "B", 1, 0), -1),
+    ("circl_hip_eddilithium2_verify", ("B", "B", "B", None, "B", 1, 0), -1),
+    ("circl_hip_eddilithium2_verify", ("B", "B", "B", "B", None, 1, 0), -1),
+    ("circl_hip_eddilithium3_keygen", (None, None, None, 0, 0), 0),
+    ("circl_hip_eddilithium3_keygen", (None, "B", "B", 1, 0), -1),
+    ("circl_hip_eddilithium3_keygen", ("B", None, "B", 1, 0), -1),
+    ("circl_hip_eddilithium3_keygen", ("B", "B", None, 1, 0), -1),
+    ("circl_hip_eddilithium3_sign", (None, None, None, None, 0, 0), 0),
+    ("circl_hip_eddilithium3_sign", (None, "B", "B", "B", 1, 0), -1),
+    ("circl_hip_eddilithium3_sign", ("B", "B", None, "B", 1, 0), -1),
+    ("circl_hip_eddilithium3_sign", ("B", "B", "B", None, 1, 0), -1),
+    ("circl_hip_eddilithium3_verify", (None, None, None, None, None, 0, 0), 0),
+    ("circl_hip_eddilithium3_verify", (None, "B", "B", "B", "B", 1, 0), -1),
+    ("circl_hip_eddilithium3_verify", ("B", None, "B", "B", "B", 1, 0), -1),
+    ("circl_hip_eddilithium3_verify", ("B", "B", "B", None, "B", 1, 0), -1),
+    ("circl_hip_eddilithium3_verify", ("B", "B", "B", "B", None, 1, 0), -1),
+    # the classical halves on their own
+    ("circl_hip_ed25519_keygen", (None, None, None, 0, 0), 0),
+    ("circl_hip_ed25519_keygen", (None, "B", "B", 1, 0), -1),
+    ("circl_hip_ed25519_keygen", ("B", None, None, 1, 0), -1),
+    ("circl_hip_ed25519_sign", (None, None, None, None, 0, 0), 0),
+    ("circl_hip_ed25519_sign", (None, "B", "B", "B", 1, 0), -1),
+    ("circl_hip_ed25519_sign", ("B", "B", None, "B", 1, 0), -1),
+    ("circl_hip_ed25519_sign", ("B", "B", "B", None, 1, 0), -1),
+    ("circl_hip_ed25519_verify", (None, None, None, None, None, 0, 0), 0),
+    ("circl_hip_ed25519_verify", (None, "B", "B", "B", "B", 1, 0), -1),
+    ("circl_hip_ed25519_verify", ("B", None, "B", "B", "B", 1, 0), -1),
+    ("circl_hip_ed25519_verify", ("B", "B", "B", None, "B", 1, 0), -1),
+    ("circl_hip_ed25519_verify", ("B", "B", "B", "B", None, 1, 0), -1),
+    ("circl_hip_sha512", (None, None, None, 0, 0), 0),
+    ("circl_hip_sha512", ("B", None, "B", 1, 0), -1),
+    ("circl_hip_sha512", ("B", "B", None, 1, 0), -1),
+    ("circl_hip_ed448_keygen", (None, None, None, 0, 0), 0),
+    ("circl_hip_ed448_keygen", (None, "B", "B", 1, 0), -1),
+    ("circl_hip_ed448_keygen", ("B", None, None, 1, 0), -1),
+    ("circl_hip_ed448_sign", (None, None, None, None, None, None, 0, 0), 0),
+    ("circl_hip_ed448_sign", (None, "B", "B", None, None, "B", 1, 0), -1),
+    ("circl_hip_ed448_sign", ("B", "B", None, None, None, "B", 1, 0), -1),
+    ("circl_hip_ed448_sign", ("B", "B", "B", None, None, None, 1, 0), -1),
+    ("circl_hip_ed448_sign", ("B", "B", "B", "B", None, "B", 1, 0), -1),   # a context blob without offsets
+    ("circl_hip_ed448_sign", ("B", "B", "B", "B", "C", "B", 1, 0), -1),    # a context of 256 bytes
+    ("circl_hip_ed448_verify", (None, None, None, None, None, None, None, 0, 0), 0),
+    ("circl_hip_ed448_verify", (None, "B", "B", "B", None, None, "B", 1, 0), -1),
+    ("circl_hip_ed448_verify", ("B", None, "B", "B", None, None, "B", 1, 0), -1),
+    ("circl_hip_ed448_verify", ("B", "B", "B", None, None, None, "B", 1, 0), -1),
+    ("circl_hip_ed448_verify", ("B", "B", "B", "B", None, None, None, 1, 0), -1),
+    ("circl_hip_ed448_verify", ("B", "B", "B", "B", "B", None, "B", 1, 0), -1),
+    ("circl_hip_x448", (None, "B", "B", "B", 0, 0), 0),
+    ("circl_hip_x448", ("B", "B", None, "B", 0, 0), 0),
+    ("circl_hip_x448", (None, "B", "B", "B", 1, 0), -1),
+    ("circl_hip_x448", ("B", "B", None, "B", 1, 0), -1),
+    ("circl_hip_x25519", (None, "B", "B", "B", 0, 0), 0),
+    ("circl_hip_x25519", (None, "B", "B", "B", 1, 0), -1),
+    ("circl_hip_x25519", ("B", "B", None, "B", 1, 0), -1),
+    # the hybrids: an unknown scheme is refused whatever else is passed, then NULL arrays
+    ("circl_hip_hybrid_keygen", (99, "B", "B", "B", 0, 0), -1),
+    ("circl_hip_hybrid_keygen", (0, "B", "B", "B", 1, 0), -1),
+    ("circl_hip_hybrid_keygen", (1, None, "B", "B", 1, 0), -1),
+    ("circl_hip_hybrid_keygen", (2, "B", None, "B", 1, 0), -1),
+    ("circl_hip_hybrid_keygen", (3, "B", "B", None, 1, 0), -1),
+    ("circl_hip_hybrid_encaps", (99, "B", "B", "B", "B", "B", 0, 0), -1),
+    ("circl_hip_hybrid_encaps", (1, None, "B", "B", "B", "B", 1, 0), -1),
+    ("circl_hip_hybrid_encaps", (2, "B", None, "B", "B", "B", 1, 0), -1),
+    ("circl_hip_hybrid_encaps", (3, "B", "B", None, "B", "B", 1, 0), -1),
+    ("circl_hip_hybrid_encaps", (4, "B", "B", "B", None, "B", 1, 0), -1),
+    ("circl_hip_hybrid_decaps", (99, "B", "B", "B", "B", 0, 0), -1),
+    ("circl_hip_hybrid_decaps", (1, None, "B", "B", "B", 1, 0), -1),
+    ("circl_hip_hybrid_decaps", (2, "B", None, "B", "B", 1, 0), -1),
+    ("circl_hip_hybrid_decaps", (4, "B", "B", None, "B", 1, 0), -1),
+    ("circl_hip_hybrid_keygen_dev", (99, "B", "B", "B", 1, "B", 1 << 30, None), -1),
+    ("circl_hip_hybrid_encaps_dev", (99, "B", "B", "B", "B", "B", 1, "B", 1 << 30, None), -1),
+    ("circl_hip_hybrid_decaps_dev", (99, "B", "B", "B", "B", 1, "B", 1 << 30, None), -1),
+    # a NULL table is refused, not dereferenced
+    ("circl_hip_hybrid_encaps_table", (None, None, "B", "B", "B", "B", 1), -1),
+    ("circl_hip_hybrid_decaps_table", (None, None, "B", "B", "B", 1), -1),
+    ("circl_hip_hybrid_encaps_table_submit", (None, None, "B", "B", "B", "B", 1, "B"), -1),
+    ("circl_hip_hybrid_decaps_table_submit", (None, None, "B", "B", "B", 1, "B"), -1),
+    ("circl_hip_hybrid_encaps_table_dev", (None, None, "B", "B", "B", "B", 1, "B", 1 << 30, None), -1),
+    ("circl_hip_hybrid_decaps_table_dev", (None, None, "B", "B", "B", 1, "B", 1 << 30, None), -1),
+    ("circl_hip_mlkem_encaps_table", (None, "K", "B", "B", "B", "B", 2), -1),
+    ("circl_hip_mlkem_decaps_table", (None, "K", "B", "B", "B", 2), -1),
+    ("circl_hip_mlkem_encaps_table_submit", (None, None, "B", "B", "B", "B", 1, "B"), -1),
+    ("circl_hip_mlkem_decaps_table_submit", (None, None, "B", "B", "B", 1, "B"), -1),
+    ("circl_hip_mldsa_verify_table", (None, "K", "B", "B", "B", None, None, "B", 2), -1),
+    ("circl_hip_mldsa_verify_table_submit", (None, None, "B", "B", "B", None, None, "B", 1, "B"), -1),
+    ("circl_hip_mldsa_sign_table_keyed", (None, "K", "B", "B", None, None, None, "B", 2), -1),
+    ("circl_hip_mldsa_sign_table", (None, "B", "B", None, None, None, "B", 1), -1),
+    # key tables that come with the call: the parameter set, n == 0, then the table size and every index
+    ("circl_hip_mlkem_encaps_keyed", (999, "B", 8, "K", "B", "B", "B", "B", 2, 0), -1),
+    ("circl_hip_mlkem_encaps_keyed", (768, "B", 0, "K", "B", "B", "B", "B", 0, 0), 0),
+    ("circl_hip_mlkem_encaps_keyed", (768, "B", 0, "K", "B", "B", "B", "B", 2, 0), -1),
+    ("circl_hip_mlkem_encaps_keyed", (768, "B", 1 << 32, "K", "B", "B", "B", "B", 2, 0), -1),
+    ("circl_hip_mlkem_encaps_keyed", (768, "B", 5, "K", "B", "B", "B", "B", 2, 0), -1),
+    ("circl_hip_mlkem_decaps_keyed", (999, "B", 8, "K", "B", "B", "B", 2, 0), -1),
+    ("circl_hip_mlkem_decaps_keyed", (512, "B", 0, "K", "B", "B", "B", 0, 0), 0),
+    ("circl_hip_mlkem_decaps_keyed", (512, "B", 0, "K", "B", "B", "B", 2, 0), -1),
+    ("circl_hip_mlkem_decaps_keyed", (512, "B", 1 << 32, "K", "B", "B", "B", 2, 0), -1),
+    ("circl_hip_mlkem_decaps_keyed", (512, "B", 5, "K", "B", "B", "B", 2, 0), -1),
+    ("circl_hip_mldsa_verify_keyed", (999, "B", 8, "K", "B", "B", "B", None, None, "B", 2, 0), -1),
+    ("circl_hip_mldsa_verify_keyed", (65, "B", 0, "K", "B", "B", "B", None, None, "B", 0, 0), 0),
+    ("circl_hip_mldsa_verify_keyed", (65, "B", 0, "K", "B", "B", "B", None, None, "B", 2, 0), -1),
+    ("circl_hip_mldsa_verify_keyed", (65, "B", 1 << 32, "K", "B", "B", "B", None, None, "B", 2, 0), -1),
+    ("circl_hip_mldsa_verify_keyed", (65, "B", 5, "K", "B", "B", "B", None, None, "B", 2, 0), -1),
+]
+
+
+def test_argument_contract_before_any_device(L):
+    import ctypes as C
+    buf = np.zeros(1 << 16, np.uint8)
+    kidx = np.array([5, 0], np.uint32)
+    coff = np.array([0, 256], np.uint64)
+    ptr = {"B": buf.ctypes.data, "K": kidx.ctypes.data, "C": coff.ctypes.data}
+    got = []
+    for name, args, want in _NO_DEVICE_NEEDED:
+        rc = getattr(L, name)(*[ptr[a] if isinstance(a, str) else a for a in args])
+        print(name, args, rc)
+        got.append((name, args, rc))
+    assert got == _NO_DEVICE_NEEDED
+    # a *_submit call zeroes the ticket before it refuses
+    ticket = C.c_uint64(7)
+    assert L.circl_hip_hybrid_encaps_table_submit(None, None, ptr["B"], ptr["B"], ptr["B"], ptr["B"], 1, C.byref(ticket)) == -1 and ticket.value == 0

@@ -1,6 +1,9 @@
 """Batch Ed448-Dilithium3 (sign/eddilithium3) on the GPU: key generation, signing and verification against the oracle's
 round-3 Dilithium3 (mode3) and the RFC 8032 5.2 checker of tests/curve448.py, composed as sign/eddilithium3/eddilithium.go does."""
 import hashlib
+import os
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -9,6 +12,7 @@ import curve448 as ref
 
 pytestmark = pytest.mark.gpu
 DPK, DSK, DSIG = 1952, 4000, 3293
+HERE = os.path.dirname(os.path.abspath(__file__))
 
 
 @pytest.fixture(scope="module")
@@ -34,9 +38,7 @@ def batch(api):
     return seeds, msgs, pk, sk, sig
 
 
-def test_keygen_sign_against_oracle_and_checker(batch, orc, api):
-    seeds, msgs, pk, sk, sig = batch
-    assert api.EDDILITHIUM3_SIZES == dict(seed=57, pk=2009, sk=4057, sig=3407)
+def _check_against_oracle_and_checker(orc, seeds, msgs, pk, sk, sig):
     assert pk.shape == (len(seeds), 2009) and sk.shape == (len(seeds), 4057) and sig.shape == (len(seeds), 3407)
     split = [hashlib.shake_256(bytes(s)).digest(32 + 57) for s in seeds]  # NewKeyFromSeed: 32 bytes for mode3, then 57 for Ed448
     sd = np.frombuffer(b"".join(x[:32] for x in split), np.uint8).reshape(-1, 32).copy()
@@ -53,6 +55,53 @@ def test_keygen_sign_against_oracle_and_checker(batch, orc, api):
         esk = split[i][32:] + bytes(pk[i, DPK:])
         assert bytes(sig[i, DSIG:]) == ref.sign(esk, msgs[i], b"")  # the empty context
     assert orc.mldsa_verify(3, dpk, dsig, msgs).all()
+
+
+def test_keygen_sign_against_oracle_and_checker(batch, orc, api):
+    assert api.EDDILITHIUM3_SIZES == dict(seed=57, pk=2009, sk=4057, sig=3407)
+    _check_against_oracle_and_checker(orc, *batch)
+
+
+def _chunked(mode, seeds, msgs, tmp_path):
+    """keygen, sign and verify in a child process whose pipeline chunks are 2^8 items (the smallest CIRCL_HIP_HOST_CHUNK allows)"""
+    src, dst = str(tmp_path / "in.npz"), str(tmp_path / "out.npz")
+    off = np.cumsum([0] + [len(m) for m in msgs]).astype(np.uint64)
+    np.savez(src, seeds=seeds, blob=np.frombuffer(b"".join(msgs), np.uint8), off=off)
+    env = dict(os.environ, CIRCL_HIP_HOST_CHUNK="8")
+    r = subprocess.run([sys.executable, os.path.join(HERE, "eddilithium_worker.py"), str(mode), src, dst], env=env, capture_output=True, text=True, timeout=240)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    d = np.load(dst)
+    return d["pk"], d["sk"], d["sig"], d["ok"]
+
+
+def test_second_chunk_of_the_composition(batch, orc, tmp_path):
+    """300 items in chunks of 256: the second chunk has rebased message offsets, the workspace of the first and a wipe in between"""
+    seeds70, _, pk70, sk70, _ = batch
+    rng = np.random.default_rng(32)
+    n = 300
+    seeds = np.concatenate([seeds70, rng.integers(0, 256, (n - len(seeds70), 57), dtype=np.uint8)])
+    lens = rng.permutation(n)  # every length 0..299 once
+    lens[[3, 255, 256, 299]] = 0  # ... and empty messages on both sides of the chunk boundary
+    msgs = [rng.bytes(int(l)) for l in lens]
+    pk, sk, sig, ok = _chunked(3, seeds, msgs, tmp_path)
+    _check_against_oracle_and_checker(orc, seeds, msgs, pk, sk, sig)
+    assert ok.shape == (n,) and ok.all()
+    assert (pk[:70] == pk70).all() and (sk[:70] == sk70).all()
+
+
+@pytest.mark.parametrize("n", [1, 65])
+def test_round_trip_at_boundary_sizes(api, n):
+    """one row (the pitch arithmetic of the strided copies is degenerate) and a second, nearly empty wavefront"""
+    rng = np.random.default_rng(33 + n)
+    msgs = [rng.bytes(int(l)) for l in rng.integers(0, 100, n)]
+    pk, sk = api.eddilithium3_keygen(rng.integers(0, 256, (n, 57), dtype=np.uint8))
+    sig = api.eddilithium3_sign(sk, msgs)
+    ok = api.eddilithium3_verify(pk, sig, msgs)
+    assert ok.shape == (n,) and ok.all()
+    for col in (100, DSIG + 70):  # a bit of the Dilithium3 half, a bit of the Ed448 half
+        bad = sig.copy()
+        bad[:, col] ^= 1
+        assert not api.eddilithium3_verify(pk, bad, msgs).any()
 
 
 def test_verify_both_halves(batch, api):
