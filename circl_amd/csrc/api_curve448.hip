@@ -16,7 +16,33 @@ bool context_too_long(const uint8_t *ctx_blob, const uint64_t *ctx_off, size_t n
     return false;
 }
 
+// X448 KeyGen by the Ed448 comb (x448_dev.h base_mult_comb), the default, or by the ladder from u = 5: CIRCL_HIP_X448_KEYGEN = comb |
+// ladder.  The comb is 2.1x the ladder at 2^14 items and 2.2x at 2^18 (profiles/curve448_bench.txt); the ladder stays
+// reachable for the comparison.  Like CIRCL_HIP_FRODO_WAVES it is read at every call, so that one process can compare the routes;
+// anything but "ladder" is the default.
+bool x448_keygen_comb() {
+    const char *e = getenv("CIRCL_HIP_X448_KEYGEN");
+    return !e || strcmp(e, "ladder") != 0;
+}
+
 }  // namespace
+
+namespace circl {
+namespace host {
+// internal (api_hybrid.hip): out_base[i] = X448(scalar_i, 5) and out_shared[i] = X448(scalar_i, point_i) in one launch
+int x448_pair_dev(const uint8_t *d_scalar, const uint8_t *d_point, uint8_t *d_out_base, uint8_t *d_out_shared, uint8_t *d_ok, size_t n,
+                  hipStream_t st) {
+    if (n == 0) return CIRCL_HIP_OK;
+    const unsigned nb = (unsigned)((n + 63) / 64);
+    ProfScope ps(CIRCL_HIP_KERNEL_X448, st);
+    auto kernel = x448_keygen_comb() ? circl::x448::x448_pair_kernel<true> : circl::x448::x448_pair_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(2 * nb), dim3(64), 0, st, reinterpret_cast<const uint32_t *>(d_scalar), reinterpret_cast<const uint32_t *>(d_point),
+                       reinterpret_cast<uint32_t *>(d_out_base), reinterpret_cast<uint32_t *>(d_out_shared), d_ok, n, nb);
+    HIP_TRY(hipGetLastError());
+    return CIRCL_HIP_OK;
+}
+}  // namespace host
+}  // namespace circl
 
 extern "C" {
 
@@ -29,10 +55,13 @@ int circl_hip_x448_dev(const uint8_t *d_scalar, const uint8_t *d_point, uint8_t 
     hipStream_t st = static_cast<hipStream_t>(stream);
     ProfScope ps(CIRCL_HIP_KERNEL_X448, st);
     if (d_point)
-        hipLaunchKernelGGL(circl::x448::x448_kernel<false>, lanes_grid(n), dim3(64), 0, st, reinterpret_cast<const uint32_t *>(d_scalar),
+        hipLaunchKernelGGL((circl::x448::x448_kernel<false, false>), lanes_grid(n), dim3(64), 0, st, reinterpret_cast<const uint32_t *>(d_scalar),
                            reinterpret_cast<const uint32_t *>(d_point), reinterpret_cast<uint32_t *>(d_out), d_ok, n);
+    else if (x448_keygen_comb())
+        hipLaunchKernelGGL((circl::x448::x448_kernel<true, true>), lanes_grid(n), dim3(64), 0, st, reinterpret_cast<const uint32_t *>(d_scalar),
+                           static_cast<const uint32_t *>(nullptr), reinterpret_cast<uint32_t *>(d_out), d_ok, n);
     else
-        hipLaunchKernelGGL(circl::x448::x448_kernel<true>, lanes_grid(n), dim3(64), 0, st, reinterpret_cast<const uint32_t *>(d_scalar),
+        hipLaunchKernelGGL((circl::x448::x448_kernel<true, false>), lanes_grid(n), dim3(64), 0, st, reinterpret_cast<const uint32_t *>(d_scalar),
                            static_cast<const uint32_t *>(nullptr), reinterpret_cast<uint32_t *>(d_out), d_ok, n);
     HIP_TRY(hipGetLastError());
     return CIRCL_HIP_OK;

@@ -3,6 +3,7 @@
 //   CIRCL_HIP_HYBRID_XWING            kem/xwing/xwing.go      (X25519 + ML-KEM-768, SHA3-256 combiner)
 //   CIRCL_HIP_HYBRID_X25519MLKEM768   kem/hybrid/hybrid.go    (ct_M || ct_X, ss_M || ss_X; X25519 as a KEM: xkem.go)
 //   CIRCL_HIP_HYBRID_KYBER768_X25519, _KYBER512_X25519   the same scheme type with X25519 first and round-3 Kyber second
+//   CIRCL_HIP_HYBRID_KYBER768_X448, _KYBER1024_X448      the same with X448 (56-byte rows, x448_dev.h) in place of X25519
 // A call is a handful of launches per chunk over HBM-resident arrays: strided splits of the packed keys / ciphertexts,
 // seed expansion (SHAKE256, lane = item), the ML-KEM-768 batch kernels, two X25519 ladders per item (lane = item), the
 // combiner, strided joins.  Nothing is computed on the host.
@@ -15,16 +16,17 @@ using circl::KeyIdx;
 namespace hk = circl::hybridk;
 
 namespace {
-// one hybrid = one lattice KEM (ML-KEM or round-3 Kyber) + X25519, either of them first in every packed array
+// one hybrid = one lattice KEM (ML-KEM or round-3 Kyber) + X25519 or X448, either of them first in every packed array
 struct Desc {
     bool xwing;     // X-Wing: seed expansion, combiner and private-key format of kem/xwing; otherwise kem/hybrid's concatenation scheme
-    int param;      // 768 | 512
+    int param;      // 512 | 768 | 1024
     bool r3;        // round-3 Kyber (kem/kyber) instead of ML-KEM
-    bool x_first;   // X25519 is the `first` component of hybrid.go's scheme{name, first, second}
+    bool x_first;   // the DH half is the `first` component of hybrid.go's scheme{name, first, second}
+    size_t x_bytes;  // width of the DH half's scalars, points and shared secrets: 32 (X25519) | 56 (X448)
     size_t EK, DK, CTM;
     size_t seed, eseed, pk, sk, ct, ss;
     // byte offsets of the two halves inside a packed row
-    size_t kem_off(size_t x_bytes) const { return x_first ? x_bytes : 0; }
+    size_t kem_off() const { return x_first ? x_bytes : 0; }
     size_t x_off(size_t kem_bytes) const { return x_first ? 0 : kem_bytes; }
 };
 bool desc_of(int scheme, Desc &d) {
@@ -33,9 +35,10 @@ bool desc_of(int scheme, Desc &d) {
         d.EK = circl_hip_mlkem_ek_size(param);
         d.DK = circl_hip_mlkem_dk_size(param);
         d.CTM = circl_hip_mlkem_ct_size(param);
-        d.pk = d.EK + 32;
-        d.ct = d.CTM + 32;
+        d.pk = d.EK + d.x_bytes;
+        d.ct = d.CTM + d.x_bytes;
     };
+    d.x_bytes = scheme == CIRCL_HIP_HYBRID_KYBER768_X448 || scheme == CIRCL_HIP_HYBRID_KYBER1024_X448 ? 56 : 32;
     switch (scheme) {
     case CIRCL_HIP_HYBRID_XWING:
         d.xwing = true; d.r3 = false; d.x_first = false;
@@ -54,18 +57,26 @@ bool desc_of(int scheme, Desc &d) {
         d.xwing = false; d.r3 = true; d.x_first = true;
         lattice(512);
         break;
+    case CIRCL_HIP_HYBRID_KYBER768_X448:  // scheme{"Kyber768-X448", x448Kem, kyber768}: hybrid.go:83-87
+        d.xwing = false; d.r3 = true; d.x_first = true;
+        lattice(768);
+        break;
+    case CIRCL_HIP_HYBRID_KYBER1024_X448:  // scheme{"Kyber1024-X448", x448Kem, kyber1024}: hybrid.go:89-93
+        d.xwing = false; d.r3 = true; d.x_first = true;
+        lattice(1024);
+        break;
     default:
         return false;
     }
-    d.seed = 64;   // max of the components' seed sizes (hybrid.go:128-138): 64 for the lattice KEM, 32 for X25519
-    d.eseed = 32;  // hybrid.go:148-157
-    d.sk = d.DK + 32;
-    d.ss = 64;
+    d.seed = 64;         // max of the components' seed sizes (hybrid.go:128-138): 64 for the lattice KEM, 32 / 56 for the DH half
+    d.eseed = d.x_bytes;  // hybrid.go:148-157: max(32, 32 | 56)
+    d.sk = d.DK + d.x_bytes;
+    d.ss = 32 + d.x_bytes;
     return true;
 }
 
 // temporaries of one call, carved (Carve) from the caller's workspace in front of the lattice KEM's workspace
-size_t tmp_bytes(const Desc &d, size_t n) {  // upper bound over the three operations: ek, dk, ctm + a dozen 32/64-byte rows per item
+size_t tmp_bytes(const Desc &d, size_t n) {  // upper bound over the three operations: ek, dk, ctm + a dozen rows of 32, x_bytes (<= 64) or 64 bytes per item
     return up256(n * d.EK) + up256(n * d.DK) + up256(n * d.CTM) + 10 * up256(n * 64) + up256(n);
 }
 
@@ -129,22 +140,32 @@ int kem_decaps(const Desc &d, const uint8_t *dk, const uint8_t *ct, uint8_t *ss,
     return circl_hip_kyber_decaps_dev(d.param, dk, ct, ss, n, ws, wsb, st);
 }
 
-// a packed row (a key, a ciphertext, a shared secret) is the lattice half and the 32 bytes of the X25519 half, either of them first
+// a packed row (a key, a ciphertext, a shared secret) is the lattice half and the x_bytes of the DH half, either of them first
 int split_rows(hipStream_t st, const Desc &d, const uint8_t *packed, size_t row, uint8_t *kem, size_t kem_bytes, uint8_t *x, size_t n) {
-    TRY(copy_rows_w32(st, kem, kem_bytes, packed + d.kem_off(32), row, kem_bytes, n));
-    return copy_rows_w32(st, x, 32, packed + d.x_off(kem_bytes), row, 32, n);
+    TRY(copy_rows_w32(st, kem, kem_bytes, packed + d.kem_off(), row, kem_bytes, n));
+    return copy_rows_w32(st, x, d.x_bytes, packed + d.x_off(kem_bytes), row, d.x_bytes, n);
 }
 int join_rows(hipStream_t st, const Desc &d, uint8_t *packed, size_t row, const uint8_t *kem, size_t kem_bytes, const uint8_t *x, size_t n) {
-    TRY(copy_rows_w32(st, packed + d.kem_off(32), row, kem, kem_bytes, kem_bytes, n));
-    return copy_rows_w32(st, packed + d.x_off(kem_bytes), row, x, 32, 32, n);
+    TRY(copy_rows_w32(st, packed + d.kem_off(), row, kem, kem_bytes, kem_bytes, n));
+    return copy_rows_w32(st, packed + d.x_off(kem_bytes), row, x, d.x_bytes, d.x_bytes, n);
 }
-// the ephemeral seed of an encapsulation -> the lattice KEM's m and the X25519 scalar
+// the DH half: X25519 or X448 on rows of x_bytes.  dh: out = DH(scalar, point) (+ ok), or DH(scalar, base point) without a point;
+// dh_pair: both in one launch
+int dh(const Desc &d, const uint8_t *scalar, const uint8_t *point, uint8_t *out, uint8_t *ok, size_t n, hipStream_t st) {
+    return d.x_bytes == 56 ? circl_hip_x448_dev(scalar, point, out, ok, n, st) : circl_hip_x25519_dev(scalar, point, out, ok, n, st);
+}
+int dh_pair(const Desc &d, const uint8_t *scalar, const uint8_t *point, uint8_t *out_base, uint8_t *out_shared, uint8_t *ok, size_t n, hipStream_t st) {
+    return d.x_bytes == 56 ? x448_pair_dev(scalar, point, out_base, out_shared, ok, n, st) : x25519_pair_dev(scalar, point, out_base, out_shared, ok, n, st);
+}
+// the ephemeral seed of an encapsulation -> the lattice KEM's m and the DH scalar
 int expand_eseed(hipStream_t st, const Desc &d, const uint8_t *d_eseed, uint8_t *m, uint8_t *ekx, size_t n) {
     if (d.xwing) {  // xwing.go:247-248: seedm = seed[:32], ekx = seed[32:]
         TRY(copy_rows_w32(st, m, 32, d_eseed, 64, 32, n));
         return copy_rows_w32(st, ekx, 32, d_eseed + 32, 64, 32, n);
     }
-    if (d.x_first)
+    if (d.x_bytes == 56)  // (X448 is always the first component)
+        hipLaunchKernelGGL((hk::hybrid_expand_kernel<7, 4, true, 7>), lanes_grid(n, 256), dim3(256), 0, st, w(d_eseed), w(m), w(ekx), n);
+    else if (d.x_first)
         hipLaunchKernelGGL((hk::hybrid_expand_kernel<4, 4, true>), lanes_grid(n, 256), dim3(256), 0, st, w(d_eseed), w(m), w(ekx), n);
     else
         hipLaunchKernelGGL((hk::hybrid_expand_kernel<4, 4, false>), lanes_grid(n, 256), dim3(256), 0, st, w(d_eseed), w(m), w(ekx), n);
@@ -163,8 +184,8 @@ int shared_secret(hipStream_t st, const Desc &d, const uint8_t *ssm, const uint8
     }
     hipLaunchKernelGGL(hk::hybrid_status_kernel, lanes_grid(n, 256), dim3(256), 0, st, d_status, okx, n);
     HIP_TRY(hipGetLastError());
-    TRY(join_rows(st, d, d_ss, 64, ssm, 32, ssx, n));
-    return zero_failed(st, d_ss, 64, d_status, n);
+    TRY(join_rows(st, d, d_ss, d.ss, ssm, 32, ssx, n));
+    return zero_failed(st, d_ss, d.ss, d_status, n);
 }
 }  // namespace
 
@@ -196,20 +217,23 @@ int circl_hip_hybrid_keygen_dev(int scheme, const uint8_t *d_seed, uint8_t *d_pk
     if (!aligned<16>(d_seed, d_pk, d_sk, d_ws)) return misaligned();
     hipStream_t st = static_cast<hipStream_t>(stream);
     Carve c{static_cast<uint8_t *>(d_ws)};
-    uint8_t *seedm = c.take(n * 64), *skx = c.take(n * 32), *pkx = c.take(n * 32), *ek = c.take(n * d.EK), *dk = c.take(n * d.DK);
+    const size_t XB = d.x_bytes;
+    uint8_t *seedm = c.take(n * 64), *skx = c.take(n * XB), *pkx = c.take(n * XB), *ek = c.take(n * d.EK), *dk = c.take(n * d.DK);
     uint8_t *kws = static_cast<uint8_t *>(d_ws) + tmp_bytes(d, n);
     const size_t kws_bytes = ws_bytes - tmp_bytes(d, n);
     SecretWipe wipe{st};  // nothing key-equivalent stays behind in the caller's workspace
-    wipe.add(seedm, n * 64); wipe.add(skx, n * 32); wipe.add(dk, n * d.DK);
+    wipe.add(seedm, n * 64); wipe.add(skx, n * XB); wipe.add(dk, n * d.DK);
     if (d.xwing)
         hipLaunchKernelGGL(hk::xwing_expand_kernel, lanes_grid(n, 256), dim3(256), 0, st, w(d_seed), w(seedm), w(skx), n);
+    else if (XB == 56)
+        hipLaunchKernelGGL((hk::hybrid_expand_kernel<8, 8, true, 7>), lanes_grid(n, 256), dim3(256), 0, st, w(d_seed), w(seedm), w(skx), n);
     else if (d.x_first)
         hipLaunchKernelGGL((hk::hybrid_expand_kernel<8, 8, true>), lanes_grid(n, 256), dim3(256), 0, st, w(d_seed), w(seedm), w(skx), n);
     else
         hipLaunchKernelGGL((hk::hybrid_expand_kernel<8, 8, false>), lanes_grid(n, 256), dim3(256), 0, st, w(d_seed), w(seedm), w(skx), n);
     HIP_TRY(hipGetLastError());
     TRY(kem_keygen(d, seedm, ek, dk, n, kws, kws_bytes, st));
-    TRY(circl_hip_x25519_dev(skx, nullptr, pkx, nullptr, n, st));
+    TRY(dh(d, skx, nullptr, pkx, nullptr, n, st));
     TRY(join_rows(st, d, d_pk, d.pk, ek, d.EK, pkx, n));
     if (d.xwing) {
         TRY(copy_rows_w32(st, d_sk, 32, d_seed, 32, 32, n));  // the packed private key is the seed (xwing.go:156-163)
@@ -230,16 +254,17 @@ int circl_hip_hybrid_encaps_dev(int scheme, const uint8_t *d_pk, const uint8_t *
     if (!aligned<16>(d_pk, d_eseed, d_ct, d_ss, d_ws)) return misaligned();
     hipStream_t st = static_cast<hipStream_t>(stream);
     Carve c{static_cast<uint8_t *>(d_ws)};
-    uint8_t *ek = c.take(n * d.EK), *pkx = c.take(n * 32), *m = c.take(n * 32), *ekx = c.take(n * 32), *ctm = c.take(n * d.CTM), *ssm = c.take(n * 32),
-            *ctx = c.take(n * 32), *ssx = c.take(n * 32), *okx = c.take(n);
+    const size_t XB = d.x_bytes;
+    uint8_t *ek = c.take(n * d.EK), *pkx = c.take(n * XB), *m = c.take(n * 32), *ekx = c.take(n * XB), *ctm = c.take(n * d.CTM), *ssm = c.take(n * 32),
+            *ctx = c.take(n * XB), *ssx = c.take(n * XB), *okx = c.take(n);
     uint8_t *kws = static_cast<uint8_t *>(d_ws) + tmp_bytes(d, n);
     const size_t kws_bytes = ws_bytes - tmp_bytes(d, n);
     SecretWipe wipe{st};  // the ephemeral secrets and the two half shared secrets
-    wipe.add(m, n * 32); wipe.add(ekx, n * 32); wipe.add(ssm, n * 32); wipe.add(ssx, n * 32);
+    wipe.add(m, n * 32); wipe.add(ekx, n * XB); wipe.add(ssm, n * 32); wipe.add(ssx, n * XB);
     TRY(split_rows(st, d, d_pk, d.pk, ek, d.EK, pkx, n));
     TRY(expand_eseed(st, d, d_eseed, m, ekx, n));
     TRY(kem_encaps(d, ek, m, ctm, ssm, d_status, n, kws, kws_bytes, st));
-    TRY(x25519_pair_dev(ekx, pkx, ctx, ssx, okx, n, st));  // ct_X = X25519(ekx, 9), ss_X = X25519(ekx, pk_X)
+    TRY(dh_pair(d, ekx, pkx, ctx, ssx, okx, n, st));  // ct_X = X25519(ekx, 9), ss_X = X25519(ekx, pk_X); X448: base point 5
     TRY(join_rows(st, d, d_ct, d.ct, ctm, d.CTM, ctx, n));
     TRY(shared_secret(st, d, ssm, ssx, ctx, pkx, okx, d_status, d_status, d_ss, n));
     TRY(zero_failed(st, d_ct, d.ct, d_status, n));
@@ -257,12 +282,13 @@ int circl_hip_hybrid_decaps_dev(int scheme, const uint8_t *d_sk, const uint8_t *
     if (!aligned<16>(d_sk, d_ct, d_ss, d_ws)) return misaligned();
     hipStream_t st = static_cast<hipStream_t>(stream);
     Carve c{static_cast<uint8_t *>(d_ws)};
-    uint8_t *dk = c.take(n * d.DK), *ek = c.take(n * d.EK), *skx = c.take(n * 32), *ctm = c.take(n * d.CTM), *ctx = c.take(n * 32), *ssm = c.take(n * 32),
-            *ssx = c.take(n * 32), *pkx = c.take(n * 32), *seedm = c.take(n * 64), *okx = c.take(n);
+    const size_t XB = d.x_bytes;
+    uint8_t *dk = c.take(n * d.DK), *ek = c.take(n * d.EK), *skx = c.take(n * XB), *ctm = c.take(n * d.CTM), *ctx = c.take(n * XB), *ssm = c.take(n * 32),
+            *ssx = c.take(n * XB), *pkx = c.take(n * XB), *seedm = c.take(n * 64), *okx = c.take(n);
     uint8_t *kws = static_cast<uint8_t *>(d_ws) + tmp_bytes(d, n);
     const size_t kws_bytes = ws_bytes - tmp_bytes(d, n);
     SecretWipe wipe{st};
-    wipe.add(dk, n * d.DK); wipe.add(skx, n * 32); wipe.add(ssm, n * 32); wipe.add(ssx, n * 32); wipe.add(seedm, n * 64);
+    wipe.add(dk, n * d.DK); wipe.add(skx, n * XB); wipe.add(ssm, n * 32); wipe.add(ssx, n * XB); wipe.add(seedm, n * 64);
     TRY(split_rows(st, d, d_ct, d.ct, ctm, d.CTM, ctx, n));
     if (d.xwing) {  // the private key is the seed: re-derive (xwing.go:165-185 Unpack = deriveKeyPair)
         hipLaunchKernelGGL(hk::xwing_expand_kernel, lanes_grid(n, 256), dim3(256), 0, st, w(d_sk), w(seedm), w(skx), n);
@@ -271,7 +297,7 @@ int circl_hip_hybrid_decaps_dev(int scheme, const uint8_t *d_sk, const uint8_t *
         TRY(x25519_pair_dev(skx, ctx, pkx, ssx, okx, n, st));  // sk.xpk = X25519(sk_X, 9), ss_X = X25519(sk_X, ct_X)
     } else {
         TRY(split_rows(st, d, d_sk, d.sk, dk, d.DK, skx, n));
-        TRY(circl_hip_x25519_dev(skx, ctx, ssx, okx, n, st));
+        TRY(dh(d, skx, ctx, ssx, okx, n, st));
     }
     TRY(kem_decaps(d, dk, ctm, ssm, d_status, n, kws, kws_bytes, st));
     TRY(shared_secret(st, d, ssm, ssx, ctx, pkx, okx, d_status, nullptr, d_ss, n));
@@ -349,7 +375,7 @@ static int hybrid_keytable_new_one(int scheme, const Desc &d, int private_keys, 
         krows.resize(nkeys * KROW);
         for (size_t i = 0; i < nkeys; i++) {
             const uint8_t *row = keys + i * t->row;
-            memcpy(krows.data() + i * KROW, row + d.kem_off(32), KROW);
+            memcpy(krows.data() + i * KROW, row + d.kem_off(), KROW);
             memcpy(xrows.data() + i * 32, row + d.x_off(KROW), 32);
         }
         // public: pk_X rows; private (kem/hybrid): sk_X rows (the decapsulation never needs pk_X there)
@@ -588,7 +614,7 @@ namespace host {
 // the arrays and the launch of circl_hip_hybrid_encaps / _decaps
 int hyb_call_queue_start(bool decaps, int scheme, Coalescer *co, bool want_eventfd, QueueShape *sh) {
     Desc s;
-    if (!desc_of(scheme, s)) return CIRCL_HIP_EPARAM;
+    if (!desc_of(scheme, s) || s.x_bytes != 32) return CIRCL_HIP_EPARAM;  // (the X448 hybrids have no queue: circl_hip.h)
     if (!decaps) {
         *sh = QueueShape{s.pk, s.eseed, s.ct, s.ss, false, true};
         return coalescer_async_start(co, hyb_enc_ins(nullptr, nullptr, s), {}, hyb_enc_outs(nullptr, nullptr, nullptr, s), hybrid_ws_fn(scheme), hybrid_opts(scheme),

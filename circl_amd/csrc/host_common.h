@@ -290,6 +290,9 @@ size_t mlkem_ws_secret_bytes(size_t n);
 // api_x25519.hip: both X25519 ladders of a hybrid KEM operation (base point and peer point, same scalar) in one launch
 int x25519_pair_dev(const uint8_t *d_scalar, const uint8_t *d_point, uint8_t *d_out_base, uint8_t *d_out_shared, uint8_t *d_ok, size_t n,
                     hipStream_t st);
+// api_curve448.hip: the same for X448 (rows of 56 bytes): X448(scalar, 5) by the default KeyGen route and X448(scalar, point) by the ladder
+int x448_pair_dev(const uint8_t *d_scalar, const uint8_t *d_point, uint8_t *d_out_base, uint8_t *d_out_shared, uint8_t *d_ok, size_t n,
+                  hipStream_t st);
 
 }  // namespace host
 }  // namespace circl

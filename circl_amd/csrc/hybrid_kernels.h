@@ -76,16 +76,16 @@ static __global__ __launch_bounds__(256) void xwing_expand_kernel(const uint32_t
     }
 }
 
-// kem/hybrid seed expansion (hybrid.go:236-250, :271-300; the X25519 half is a KEM of its own: xkem.go:112-123, :160-178).
-// ex = SHAKE256(seed) is cut into the first component's seed, then the second's; the X25519 component turns its 32 bytes into
-// the scalar sk_X = SHAKE256(xseed)[:32].  IN = seed words (8 for DeriveKeyPair, 4 for EncapsulateDeterministically), KEMW =
-// words of the lattice KEM's seed (8: d || z; 4: m), XFIRST = X25519 is the first component (Kyber768-X25519) or the second
-// (X25519MLKEM768).
-template <int IN, int KEMW, bool XFIRST>
+// kem/hybrid seed expansion (hybrid.go:236-250, :271-300; the DH half is a KEM of its own: xkem.go:112-123, :160-178).
+// ex = SHAKE256(seed) is cut into the first component's seed, then the second's; the DH component turns its XW words into
+// the scalar sk_X = SHAKE256(xseed)[:8 XW].  IN = seed words (8 for DeriveKeyPair; EncapsulateDeterministically: 4 with X25519,
+// 7 with X448), KEMW = words of the lattice KEM's seed (8: d || z; 4: m), XFIRST = the DH half is the first component
+// (Kyber768-X25519, Kyber768-X448) or the second (X25519MLKEM768), XW = words of the DH half (4: X25519, 7: X448).
+template <int IN, int KEMW, bool XFIRST, int XW = 4>
 static __global__ __launch_bounds__(256) void hybrid_expand_kernel(const uint32_t *__restrict__ seed, uint32_t *__restrict__ kem_seed,
                                                                    uint32_t *__restrict__ skx, size_t n) {
-    constexpr int KEM_AT = XFIRST ? 4 : 0, X_AT = XFIRST ? 0 : KEMW;
-    static_assert(KEMW + 4 <= 17, "one squeeze block");
+    constexpr int KEM_AT = XFIRST ? XW : 0, X_AT = XFIRST ? 0 : KEMW;
+    static_assert(KEMW + XW <= 17 && IN < 16, "one absorbed block, one squeeze block");
     size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     const bool live = i < n;
     if (!live) i = n - 1;
@@ -98,13 +98,13 @@ static __global__ __launch_bounds__(256) void hybrid_expand_kernel(const uint32_
     KeccakState x;
     state_zero(x);
 #pragma unroll
-    for (int j = 0; j < 4; j++) {
+    for (int j = 0; j < XW; j++) {
         x.lo[j] = s.lo[X_AT + j];
         x.hi[j] = s.hi[X_AT + j];
     }
-    shake256_pad<4>(x);
+    shake256_pad<XW>(x);
     keccak_f1600(x);
-    if (live) state_store<0, 4>(skx + i * 8, x);
+    if (live) state_store<0, XW>(skx + i * 2 * XW, x);
 }
 
 // X-Wing combiner (xwing.go:53-71): SHA3-256(ss_M || ss_X || ct_X || pk_X || "\.//^\") -- 134 bytes, one permutation.

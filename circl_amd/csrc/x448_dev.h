@@ -6,14 +6,15 @@
 // C = x3 + z3 are sums of two carried values, B = x2 - z2 and D = x3 - z3 differences (as good as carried), every product
 // has at most sums of two on both sides (fp448_dev.h's bound).
 //
-// KeyGen is the same ladder from u = 5 (the product by x1 becomes a product by the constant).  The reference uses a
-// right-to-left Joye ladder over a table of multiples (ladderJoye, table.go); the Ed448 comb of ed448_dev.h cannot stand in for
-// it the way the Ed25519 comb does for X25519, because Ed448's curve is 4-ISOGENOUS to Curve448, not birationally
-// equivalent: the image of [k]B under the isogeny is [4k] times the X448 base point, and undoing the 4 needs a scalar division
-// mod the group order on a secret.  The plain ladder gives the reference's bytes with nothing of that.
+// KeyGen has two routes.  The ladder from u = 5 (the product by x1 becomes a product by the constant), and the fixed-base comb of
+// Ed448 (base_mult_comb): RFC 7748's 4-isogeny (x, y) -> u = y^2 / x^2 from edwards448 to curve448 is a group homomorphism that
+// sends the Ed448 base point B to the point with u = 5, so u([k]B) = X448(k, 5) for every k, with no factor to undo
+// (tests/test_x448_comb_hostsim.py checks the identity on integers).  The reference uses a right-to-left Joye ladder over a
+// table of multiples (ladderJoye, table.go).  Both routes give the reference's bytes.
 #pragma once
 #include <stdint.h>
 
+#include "ed448_dev.h"
 #include "fp448_dev.h"
 
 namespace circl {
@@ -88,6 +89,21 @@ CIRCL_HD void scalar_mult(uint32_t out[14], const uint32_t k_in[14], const uint3
     fe_cswap(x2, x3, swap);
     fe_cswap(z2, z3, swap);
     fp448::fe_to_words(out, fe_mul(x2, fp448::fe_inv(z2)));
+}
+
+// X448(k, 5) on the fixed-base comb of ed448_dev.h: 112 mixed additions and 52 doublings against 448 ladder steps.  k is clamped
+// as in scalar_mult, then reduced mod l (ge_base wants k below 2^446; B has order l, so [k]B depends on k mod l only).  A clamped
+// k is a multiple of 4 in [2^447, 2^448), which holds 3 l (not a multiple of 4) and 4 l: k = 4 l is the one clamped scalar with
+// [k]B the identity (0, 1).  Then X = 0, fe_inv sends 0 to 0 and u = 0, which is what the ladder's x / z gives at the point at
+// infinity.  Everywhere else X != 0 and u = Y^2 / X^2 (Z cancels).  No branch and no address depends on k (base_select).
+CIRCL_HD void base_mult_comb(uint32_t out[14], const uint32_t k_in[14]) {
+    uint32_t k[14], r[14];
+#pragma unroll
+    for (int i = 0; i < 14; i++) k[i] = k_in[i];
+    ed448::clamp(k);
+    ed448::sc_reduce_small(r, k);
+    const ed448::Ge p = ed448::ge_base(r);
+    fp448::fe_to_words(out, fe_mul(fe_sqr(p.Y), fp448::fe_inv(fe_sqr(p.X))));
 }
 
 }  // namespace x448

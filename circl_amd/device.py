@@ -241,10 +241,12 @@ def valu_probe(device=0, waves_per_simd=4):
 
 
 XWING, X25519MLKEM768, KYBER768_X25519, KYBER512_X25519 = 1, 2, 3, 4
+KYBER768_X448, KYBER1024_X448 = 5, 6
 
 
 class HybridDevice:
-    """X-Wing / X25519MLKEM768 on resident tensors (circl_hip_hybrid_*_dev); x25519() is the bare ladder batch."""
+    """The hybrid KEMs (X-Wing, X25519MLKEM768, Kyber*-X25519, Kyber*-X448) on resident tensors (circl_hip_hybrid_*_dev); every size
+    comes from the library.  x25519() / x448() are the bare ladder batches."""
 
     def __init__(self, scheme, n, device="cuda"):
         self.scheme, self.n = scheme, n
@@ -281,6 +283,16 @@ def x25519(scalar, point=None, out=None, ok=None):
     ok = torch.empty(n, dtype=torch.uint8, device=scalar.device) if ok is None else ok
     nat.check(nat.lib().circl_hip_x25519_dev(_chk(scalar, 32), None if point is None else _chk(point, 32), _chk(out, 32), _chk(ok), n, _stream()),
               "x25519_dev")
+    return out, ok
+
+
+def x448(scalar, point=None, out=None, ok=None):
+    """circl_hip_x448_dev on (n, 56) tensors: Shared(scalar_i, point_i), or KeyGen(scalar_i) when point is None -> (out, ok)"""
+    n = scalar.shape[0]
+    out = torch.empty_like(scalar) if out is None else out
+    ok = torch.empty(n, dtype=torch.uint8, device=scalar.device) if ok is None else ok
+    nat.check(nat.lib().circl_hip_x448_dev(_chk(scalar, 56), None if point is None else _chk(point, 56), _chk(out, 56), _chk(ok), n, _stream()),
+              "x448_dev")
     return out, ok
 
 

@@ -618,13 +618,16 @@ def x25519(scalar, point=None, device=0):
 
 
 XWING, X25519MLKEM768, KYBER768_X25519, KYBER512_X25519 = 1, 2, 3, 4
+KYBER768_X448, KYBER1024_X448 = 5, 6  # hybrid.Kyber768X448() / Kyber1024X448(): X448 (56-byte rows) first, round-3 Kyber second
 HYBRID_SIZES = {XWING: dict(seed=32, eseed=64, pk=1216, sk=32, ct=1120, ss=32), X25519MLKEM768: dict(seed=64, eseed=32, pk=1216, sk=2432, ct=1120, ss=64),
                 KYBER768_X25519: dict(seed=64, eseed=32, pk=1216, sk=2432, ct=1120, ss=64),
-                KYBER512_X25519: dict(seed=64, eseed=32, pk=832, sk=1664, ct=800, ss=64)}
+                KYBER512_X25519: dict(seed=64, eseed=32, pk=832, sk=1664, ct=800, ss=64),
+                KYBER768_X448: dict(seed=64, eseed=56, pk=1240, sk=2456, ct=1144, ss=88),
+                KYBER1024_X448: dict(seed=64, eseed=56, pk=1624, sk=3224, ct=1624, ss=88)}
 
 
 def hybrid_keygen(scheme, seeds, device=0):
-    """X-Wing DeriveKeyPairPacked / X25519MLKEM768 DeriveKeyPair for every seed -> (pk, sk)"""
+    """X-Wing DeriveKeyPairPacked / kem/hybrid DeriveKeyPair (X25519MLKEM768, Kyber*-X25519, Kyber*-X448) for every seed -> (pk, sk)"""
     S = HYBRID_SIZES[scheme]
     seeds = _u8(seeds, S["seed"])
     n = seeds.shape[0]

@@ -615,8 +615,9 @@ int circl_hip_eddilithium2_verify(const uint8_t *pk, const uint8_t *sig, const u
  * Shared(shared, secret, public) (key.go:41-46) with point != NULL, KeyGen(public, secret) (key.go:33-35) with point == NULL
  * (base point u = 5).  scalar, point, out are n rows of 56 bytes; the scalar is clamped (k[0] &= 252, k[55] |= 128,
  * key.go:15-20).  ok[i] = 0 where Shared returns false: the point, reduced mod p = 2^448 - 2^224 - 1, is 0, 1 or p - 1
- * (lowOrderPoints, curve.go:76; out[i] is then all zero), 1 otherwise; ok may be NULL.  One Montgomery ladder per lane for both
- * (the reference's KeyGen is a Joye ladder over table.go; same bytes); device pointers 4-byte aligned. */
+ * (lowOrderPoints, curve.go:76; out[i] is then all zero), 1 otherwise; ok may be NULL.  One Montgomery ladder per lane for Shared;
+ * KeyGen is the fixed-base comb of Ed448 followed by RFC 7748's isogeny u = y^2 / x^2 or, with CIRCL_HIP_X448_KEYGEN=ladder in
+ * the environment, the same ladder from u = 5 (the reference's KeyGen is a Joye ladder over table.go); the same bytes either way.  Device pointers 4-byte aligned. */
 int circl_hip_x448(const uint8_t *scalar, const uint8_t *point, uint8_t *out, uint8_t *ok, size_t n, int device);
 int circl_hip_x448_dev(const uint8_t *d_scalar, const uint8_t *d_point, uint8_t *d_out, uint8_t *d_ok, size_t n, void *stream);
 
@@ -724,8 +725,14 @@ int circl_hip_frodo640shake_decaps_dev(const uint8_t *d_sk, const uint8_t *d_ct,
  *   and round-3 Kyber (kem/kyber) as the second: pk = pk_X || ek (1216 / 832), sk = sk_X || dk (2432 / 1664), ct = ct_X ||
  *   ct_K (1120 / 800), ss = ss_X || ss_K (64); seed 64 (SHAKE256 -> 32 for X25519, then 64 for Kyber), eseed 32.  Round-3
  *   Kyber has no per-item failure, so status is 1 only for a low-order X25519 point.
+ * scheme = CIRCL_HIP_HYBRID_KYBER768_X448 / _KYBER1024_X448: the same with X448 as a KEM (xkem.go, 56-byte rows) as the first
+ *   component and round-3 Kyber768 / Kyber1024 as the second: pk = pk_X || ek (1240 / 1624), sk = sk_X || dk (2456 / 3224),
+ *   ct = ct_X || ct_K (1144 / 1624), ss = ss_X || ss_K (88); seed 64 (SHAKE256 -> 56 for X448, then 64 for Kyber), eseed 56
+ *   (SHAKE256 -> 56 for X448, then 32 for Kyber).  status is 1 only where the X448 point, reduced mod p, is 0, 1 or p - 1
+ *   (dh/x448/key.go:22-30).  These two have no key tables, no coalescing and no asynchronous queue: circl_hip_hybrid_keytable_new
+ *   and circl_hip_queue_open return CIRCL_HIP_EPARAM for them.
  * The deterministic forms only (EncapsulateDeterministically / DeriveKeyPair): randomness stays with the caller.
- * The _dev forms zero the secret temporaries in the workspace (seeds, X25519 scalars, private keys, half secrets) before
+ * The _dev forms zero the secret temporaries in the workspace (seeds, X25519 / X448 scalars, private keys, half secrets) before
  * they return control of the stream; the ML-KEM workspace behind them follows the rules of the ML-KEM entry points.
  * status may be NULL on the host forms.  The _dev forms need circl_hip_hybrid_workspace_size(scheme, n) bytes, 16-byte
  * aligned arrays, and a non-NULL d_status. */
@@ -733,6 +740,8 @@ int circl_hip_frodo640shake_decaps_dev(const uint8_t *d_sk, const uint8_t *d_ct,
 #define CIRCL_HIP_HYBRID_X25519MLKEM768 2
 #define CIRCL_HIP_HYBRID_KYBER768_X25519 3 /* hybrid.Kyber768X25519(): X25519 first, round-3 Kyber768 second (hybrid.go:77-81) */
 #define CIRCL_HIP_HYBRID_KYBER512_X25519 4 /* hybrid.Kyber512X25519() (hybrid.go:71-75) */
+#define CIRCL_HIP_HYBRID_KYBER768_X448 5   /* hybrid.Kyber768X448():  X448 first, round-3 Kyber768 second  (hybrid.go:83-87) */
+#define CIRCL_HIP_HYBRID_KYBER1024_X448 6  /* hybrid.Kyber1024X448(): X448 first, round-3 Kyber1024 second (hybrid.go:89-93) */
 size_t circl_hip_hybrid_seed_size(int scheme);
 size_t circl_hip_hybrid_eseed_size(int scheme);
 size_t circl_hip_hybrid_pk_size(int scheme);

@@ -1,13 +1,18 @@
 #!/usr/bin/env python3
 """Batch X448 / Ed448 rates on one GPU: prints ONE JSON record.
 
-    python tools/curve448_bench.py [--sizes 10,14,18,20] [--reps 3] [--host-sizes 10,14,18]
+    python tools/curve448_bench.py [--sizes 10,14,18,20] [--reps 3] [--host-sizes 10,14,18] [--route-sizes 14,18] [--hybrid-size 16]
 
 device-resident: the _dev entry points on torch buffers, one key per item, 64-byte messages, empty contexts, timed with CUDA
 events around `reps` launches after a warm-up; x25519_shared / x25519_keygen: circl_hip_x25519_dev at the same sizes in the same
 process, so that the X448 : X25519 ratio is on file; host: the host-buffer entry points on numpy arrays (wall clock, including
 the Python binding's per-item list building, so they understate the C ABI); n = 1 latency of the host forms; parity: a sample of
-every device batch checked against the checker of tests/curve448.py."""
+every device batch checked against the checker of tests/curve448.py.
+x448_keygen_routes: circl_hip_x448_dev KeyGen by the ladder and by the Ed448 comb (CIRCL_HIP_X448_KEYGEN, read at every call),
+alternated twice in this one process at each of --route-sizes, every figure from device events around at least 300 ms of
+back-to-back calls on inputs resident in HBM; "comb_faster" is true for a size when the comb's slowest pass beats the ladder's
+fastest.  hybrids: KeyGen / Encaps / Decaps of Kyber768-X448, Kyber1024-X448 and, for scale, Kyber768-X25519 through the _dev entry
+points at 2^--hybrid-size, timed the same way (with the default KeyGen route)."""
 import argparse
 import ctypes as C
 import json
@@ -39,11 +44,69 @@ def _timed(fn, name, reps):
     return e0.elapsed_time(e1) / reps
 
 
+def _timed_for(fn, name, min_ms=300.0):
+    """ms per call from device events around at least `min_ms` of back-to-back calls"""
+    once = _timed(fn, name, 2)
+    reps = max(3, int(min_ms / max(once, 1e-3)) + 1)
+    return _timed(fn, name, reps), reps
+
+
+def keygen_routes(L, dev, lgs, rng):
+    vp = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+    rec = {}
+    for lg in lgs:
+        n = 1 << lg
+        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        kh = rng.integers(0, 256, (n, 56), dtype=np.uint8)
+        k = torch.from_numpy(kh).to(dev)
+        pubs = {r: torch.empty((n, 56), dtype=torch.uint8, device=dev) for r in ("ladder", "comb")}
+        row = {"ladder_per_s": [], "comb_per_s": [], "ladder_ms": [], "comb_ms": [], "reps": []}
+        for _ in range(2):
+            for route in ("ladder", "comb"):
+                os.environ["CIRCL_HIP_X448_KEYGEN"] = route
+                ms, reps = _timed_for(lambda: L.circl_hip_x448_dev(vp(k), None, vp(pubs[route]), None, n, st), "x448_keygen " + route)
+                row[route + "_per_s"].append(n / (ms / 1e3))
+                row[route + "_ms"].append(ms)
+                row["reps"].append(reps)
+        os.environ.pop("CIRCL_HIP_X448_KEYGEN", None)
+        row["same_bytes"] = bool((pubs["ladder"] == pubs["comb"]).all().item())
+        ph = pubs["comb"].cpu().numpy()
+        row["parity_vs_checker"] = all(bytes(ph[i]) == ref.x448(bytes(kh[i]))[0] for i in rng.choice(n, 8, replace=False))
+        row["comb_to_ladder"] = min(row["comb_per_s"]) / max(row["ladder_per_s"])
+        row["comb_faster"] = row["comb_to_ladder"] > 1.0
+        rec["2^%d" % lg] = row
+        del k, pubs
+    rec["comb_faster_at_every_size"] = bool(rec) and all(r["comb_faster"] for r in rec.values())
+    return rec
+
+
+def hybrids(dev, lg, rng):
+    from circl_amd import device as dv
+    n = 1 << lg
+    rec = {"n": n}
+    for name, scheme in (("Kyber768-X448", dv.KYBER768_X448), ("Kyber1024-X448", dv.KYBER1024_X448), ("Kyber768-X25519", dv.KYBER768_X25519)):
+        H = dv.HybridDevice(scheme, n)
+        seeds = torch.from_numpy(rng.integers(0, 256, (n, H.S["seed"]), dtype=np.uint8)).to(dev)
+        es = torch.from_numpy(rng.integers(0, 256, (n, H.S["eseed"]), dtype=np.uint8)).to(dev)
+        row = {}
+        for op, fn in (("keygen", lambda: (H.keygen(seeds), 0)[1]), ("encaps", lambda: (H.encaps(H.pk, es), 0)[1]),
+                       ("decaps", lambda: (H.decaps(H.sk, H.ct), 0)[1])):
+            ms, reps = _timed_for(fn, name + " " + op)
+            row[op + "_per_s"], row[op + "_ms"], row[op + "_reps"] = n / (ms / 1e3), ms, reps
+        row["round_trip_ok"] = bool((H.ss == H.ss2).all().item()) and not bool(H.status.any().item())
+        rec[name] = row
+        del H, seeds, es
+        torch.cuda.empty_cache()
+    return rec
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="10,14,18,20")
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--host-sizes", default="10,14,18")
+    ap.add_argument("--route-sizes", default="14,18")
+    ap.add_argument("--hybrid-size", type=int, default=16)
     a = ap.parse_args()
     L = nat.lib()
     dev = torch.device("cuda:0")
@@ -125,6 +188,9 @@ def main():
         hostapi.x448(k1, u1); t4 = time.perf_counter()
         lat = {"ed448_keygen_ms": (t1 - t) * 1e3, "ed448_sign_ms": (t2 - t1) * 1e3, "ed448_verify_ms": (t3 - t2) * 1e3, "x448_shared_ms": (t4 - t3) * 1e3}
     rec["n1_latency"] = lat
+    rec["x448_keygen_routes"] = keygen_routes(L, dev, [int(x) for x in a.route_sizes.split(",") if x], rng)
+    if a.hybrid_size > 0:
+        rec["hybrids"] = hybrids(dev, a.hybrid_size, rng)
     rec["parity_vs_checker"] = bool(parity)
     print(json.dumps(rec))
 
