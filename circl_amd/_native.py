@@ -52,6 +52,10 @@ SYMBOLS = [
     "circl_hip_eddilithium3_keygen", "circl_hip_eddilithium3_sign", "circl_hip_eddilithium3_verify",
     "circl_hip_frodo640shake_workspace_size", "circl_hip_frodo640shake_keygen", "circl_hip_frodo640shake_encaps", "circl_hip_frodo640shake_decaps",
     "circl_hip_frodo640shake_keygen_dev", "circl_hip_frodo640shake_encaps_dev", "circl_hip_frodo640shake_decaps_dev",
+    "circl_hip_hpke_dhkem_key_size", "circl_hip_hpke_dhkem_ss_size", "circl_hip_hpke_dhkem_derive_keypair", "circl_hip_hpke_dhkem_encap",
+    "circl_hip_hpke_dhkem_decap", "circl_hip_hpke_dhkem_auth_encap", "circl_hip_hpke_dhkem_auth_decap",
+    "circl_hip_hpke_dhkem_derive_keypair_dev", "circl_hip_hpke_dhkem_encap_dev", "circl_hip_hpke_dhkem_decap_dev",
+    "circl_hip_hpke_dhkem_auth_encap_dev", "circl_hip_hpke_dhkem_auth_decap_dev", "circl_hip_sha256",
 ]
 
 OK, EPARAM, ENODEV, EHIP, ENOMEM, EWORKSPACE, EBUSY, EAGAIN = 0, -1, -2, -3, -4, -5, -6, -7
@@ -230,6 +234,20 @@ def lib():
         L.circl_hip_frodo640shake_keygen_dev.argtypes = [vp, vp, vp, sz, vp, sz, vp]
         L.circl_hip_frodo640shake_encaps_dev.argtypes = [vp, vp, vp, vp, sz, vp, sz, vp]
         L.circl_hip_frodo640shake_decaps_dev.argtypes = [vp, vp, vp, sz, vp, sz, vp]
+        for f in ("key", "ss"):
+            fn = getattr(L, "circl_hip_hpke_dhkem_%s_size" % f)
+            fn.restype, fn.argtypes = sz, [i]
+        L.circl_hip_hpke_dhkem_derive_keypair.argtypes = [i, vp, vp, vp, sz, i]
+        L.circl_hip_hpke_dhkem_encap.argtypes = [i, vp, vp, vp, vp, vp, sz, i]
+        L.circl_hip_hpke_dhkem_decap.argtypes = [i, vp, vp, vp, vp, vp, sz, i]
+        L.circl_hip_hpke_dhkem_auth_encap.argtypes = [i, vp, vp, vp, vp, vp, vp, vp, sz, i]
+        L.circl_hip_hpke_dhkem_auth_decap.argtypes = [i, vp, vp, vp, vp, vp, vp, sz, i]
+        L.circl_hip_hpke_dhkem_derive_keypair_dev.argtypes = [i, vp, vp, vp, sz, vp]
+        L.circl_hip_hpke_dhkem_encap_dev.argtypes = [i, vp, vp, vp, vp, vp, sz, vp]
+        L.circl_hip_hpke_dhkem_decap_dev.argtypes = [i, vp, vp, vp, vp, vp, sz, vp]
+        L.circl_hip_hpke_dhkem_auth_encap_dev.argtypes = [i, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+        L.circl_hip_hpke_dhkem_auth_decap_dev.argtypes = [i, vp, vp, vp, vp, vp, vp, sz, vp]
+        L.circl_hip_sha256.argtypes = [vp, vp, vp, sz, i]
         for f in ("seed", "eseed", "pk", "sk", "ct", "ss"):
             fn = getattr(L, "circl_hip_hybrid_%s_size" % f)
             fn.restype, fn.argtypes = sz, [i]

@@ -16,7 +16,8 @@ KERNELS = {"mlkem_hash": 0, "mlkem_encrypt": 1, "mlkem_decrypt": 2, "mlkem_keyge
            "mldsa_hash": 5, "mldsa_verify": 6, "mldsa_keygen": 7, "mldsa_sign": 8, "mlkem_keytable": 9, "mldsa_keytable": 10, "x25519": 11,
            "ed25519_keygen": 12, "ed25519_sign": 13, "ed25519_verify": 14, "sha512": 15,
            "x448": 16, "ed448_keygen": 17, "ed448_sign": 18, "ed448_verify": 19,
-           "frodo_keygen": 20, "frodo_encaps": 21, "frodo_decaps": 22}
+           "frodo_keygen": 20, "frodo_encaps": 21, "frodo_decaps": 22,
+           "hpke_x25519": 23, "hpke_x448": 24, "sha256": 25}
 
 
 def _stream():
@@ -325,3 +326,60 @@ class FrodoDevice:
         nat.check(self.L.circl_hip_frodo640shake_decaps_dev(_chk(sk, self.SK), _chk(ct, self.CT), _chk(self.ss2), self.n, self.ws.data_ptr(), self.wsb,
                                                             _stream()), "frodo640shake_decaps_dev")
         return self.ss2
+
+
+HPKE_KEM_X25519_HKDF_SHA256, HPKE_KEM_X448_HKDF_SHA512 = 0x20, 0x21
+
+
+class HpkeDhkemDevice:
+    """HPKE DHKEM over X25519 (kem = 0x20) or X448 (0x21) on resident tensors (circl_hip_hpke_dhkem_*_dev), on torch's current stream.
+    Key rows are (n, N) with N = 32 / 56, shared secrets (n, S) with S = 32 / 64; every call returns new tensors unless given."""
+
+    def __init__(self, kem, device="cuda"):
+        self.kem, self.device = kem, device
+        self.L = nat.lib()
+        self.N, self.S = self.L.circl_hip_hpke_dhkem_key_size(kem), self.L.circl_hip_hpke_dhkem_ss_size(kem)
+        if not self.N:
+            raise ValueError("unknown HPKE KEM id 0x%x" % kem)
+
+    def _out(self, n, cols=None):
+        return torch.empty(n if cols is None else (n, cols), dtype=torch.uint8, device=self.device)
+
+    def _opt(self, t):
+        return None if t is None else _chk(t, self.N)
+
+    def derive_keypair(self, ikm, sk=None, pk=None):
+        n = ikm.shape[0]
+        sk = self._out(n, self.N) if sk is None else sk
+        pk = self._out(n, self.N) if pk is None else pk
+        nat.check(self.L.circl_hip_hpke_dhkem_derive_keypair_dev(self.kem, _chk(ikm, self.N), _chk(sk, self.N), _chk(pk, self.N), n, _stream()),
+                  "hpke_dhkem_derive_keypair_dev")
+        return sk, pk
+
+    def encap(self, pkR, ikmE, enc=None, ss=None, ok=None):
+        n = pkR.shape[0]
+        enc, ss, ok = (self._out(n, self.N) if enc is None else enc, self._out(n, self.S) if ss is None else ss, self._out(n) if ok is None else ok)
+        nat.check(self.L.circl_hip_hpke_dhkem_encap_dev(self.kem, _chk(pkR, self.N), _chk(ikmE, self.N), _chk(enc, self.N), _chk(ss, self.S), _chk(ok), n,
+                                                        _stream()), "hpke_dhkem_encap_dev")
+        return enc, ss, ok
+
+    def decap(self, skR, enc, pkR=None, ss=None, ok=None):
+        n = skR.shape[0]
+        ss, ok = self._out(n, self.S) if ss is None else ss, self._out(n) if ok is None else ok
+        nat.check(self.L.circl_hip_hpke_dhkem_decap_dev(self.kem, _chk(skR, self.N), self._opt(pkR), _chk(enc, self.N), _chk(ss, self.S), _chk(ok), n,
+                                                        _stream()), "hpke_dhkem_decap_dev")
+        return ss, ok
+
+    def auth_encap(self, pkR, skS, ikmE, pkS=None, enc=None, ss=None, ok=None):
+        n = pkR.shape[0]
+        enc, ss, ok = (self._out(n, self.N) if enc is None else enc, self._out(n, self.S) if ss is None else ss, self._out(n) if ok is None else ok)
+        nat.check(self.L.circl_hip_hpke_dhkem_auth_encap_dev(self.kem, _chk(pkR, self.N), _chk(skS, self.N), self._opt(pkS), _chk(ikmE, self.N),
+                                                             _chk(enc, self.N), _chk(ss, self.S), _chk(ok), n, _stream()), "hpke_dhkem_auth_encap_dev")
+        return enc, ss, ok
+
+    def auth_decap(self, skR, enc, pkS, pkR=None, ss=None, ok=None):
+        n = skR.shape[0]
+        ss, ok = self._out(n, self.S) if ss is None else ss, self._out(n) if ok is None else ok
+        nat.check(self.L.circl_hip_hpke_dhkem_auth_decap_dev(self.kem, _chk(skR, self.N), self._opt(pkR), _chk(enc, self.N), _chk(pkS, self.N),
+                                                             _chk(ss, self.S), _chk(ok), n, _stream()), "hpke_dhkem_auth_decap_dev")
+        return ss, ok

@@ -932,3 +932,74 @@ def frodo640shake_decaps(sk, ct, device=0):
     ss = np.empty((n, 16), np.uint8)
     nat.check(nat.lib().circl_hip_frodo640shake_decaps(_p(sk), _p(ct), _p(ss), n, device), "frodo640shake_decaps")
     return ss
+
+
+def sha256(msgs, device=0):
+    """SHA-256 of every message -> (n, 32)"""
+    n = len(msgs)
+    mb, mo = _blob(msgs)
+    out = np.empty((n, 32), np.uint8)
+    nat.check(nat.lib().circl_hip_sha256(_p(mb), _p(mo), _p(out), n, device), "sha256")
+    return out
+
+
+# ---- HPKE DHKEM over X25519 / HKDF-SHA256 (0x20) and X448 / HKDF-SHA512 (0x21): hpke/kembase.go, hpke/xkem.go ----
+HPKE_KEM_X25519_HKDF_SHA256, HPKE_KEM_X448_HKDF_SHA512 = 0x20, 0x21
+HPKE_DHKEM_SIZES = {0x20: dict(key=32, ss=32), 0x21: dict(key=56, ss=64)}
+
+
+def _hpke_rows(kem, *rows):
+    if kem not in HPKE_DHKEM_SIZES:
+        raise ValueError("unknown HPKE KEM id 0x%x (0x20 = X25519/HKDF-SHA256, 0x21 = X448/HKDF-SHA512)" % kem)
+    N = HPKE_DHKEM_SIZES[kem]["key"]
+    out = [None if r is None else _u8(r, N) for r in rows]
+    n = out[0].shape[0]
+    if any(r is not None and r.shape[0] != n for r in out):
+        raise ValueError("hpke_dhkem: the inputs differ in their number of rows")
+    return N, HPKE_DHKEM_SIZES[kem]["ss"], n, out
+
+
+def _po(a):
+    return None if a is None else _p(a)
+
+
+def hpke_dhkem_derive_keypair(kem, ikm, device=0):
+    """xKEM.DeriveKeyPair(ikm_i) -> (sk (n, N), pk (n, N)); sk is the raw LabeledExpand output (unclamped), as the reference stores it.
+    GenerateKeyPair is x25519() / x448() with point=None on sk rows drawn by the caller."""
+    N, _, n, (ikm,) = _hpke_rows(kem, ikm)
+    sk, pk = np.empty((n, N), np.uint8), np.empty((n, N), np.uint8)
+    nat.check(nat.lib().circl_hip_hpke_dhkem_derive_keypair(kem, _p(ikm), _p(sk), _p(pk), n, device), "hpke_dhkem_derive_keypair")
+    return sk, pk
+
+
+def hpke_dhkem_encap(kem, pkR, ikmE, device=0):
+    """EncapsulateDeterministically(pkR_i, ikmE_i) -> (enc (n, N), ss (n, S), ok (n,)); ok = 0 (and zero rows) for a low-order pkR"""
+    N, S, n, (pkR, ikmE) = _hpke_rows(kem, pkR, ikmE)
+    enc, ss, ok = np.empty((n, N), np.uint8), np.empty((n, S), np.uint8), np.empty(n, np.uint8)
+    nat.check(nat.lib().circl_hip_hpke_dhkem_encap(kem, _p(pkR), _p(ikmE), _p(enc), _p(ss), _p(ok), n, device), "hpke_dhkem_encap")
+    return enc, ss, ok
+
+
+def hpke_dhkem_decap(kem, skR, enc, pkR=None, device=0):
+    """Decapsulate(skR_i, enc_i) -> (ss (n, S), ok (n,)); pkR = skR's public key if the caller has it (else it is computed)"""
+    N, S, n, (skR, enc, pkR) = _hpke_rows(kem, skR, enc, pkR)
+    ss, ok = np.empty((n, S), np.uint8), np.empty(n, np.uint8)
+    nat.check(nat.lib().circl_hip_hpke_dhkem_decap(kem, _p(skR), _po(pkR), _p(enc), _p(ss), _p(ok), n, device), "hpke_dhkem_decap")
+    return ss, ok
+
+
+def hpke_dhkem_auth_encap(kem, pkR, skS, ikmE, pkS=None, device=0):
+    """AuthEncapsulateDeterministically(pkR_i, skS_i, ikmE_i) -> (enc, ss, ok); pkS = skS's public key if the caller has it"""
+    N, S, n, (pkR, skS, ikmE, pkS) = _hpke_rows(kem, pkR, skS, ikmE, pkS)
+    enc, ss, ok = np.empty((n, N), np.uint8), np.empty((n, S), np.uint8), np.empty(n, np.uint8)
+    nat.check(nat.lib().circl_hip_hpke_dhkem_auth_encap(kem, _p(pkR), _p(skS), _po(pkS), _p(ikmE), _p(enc), _p(ss), _p(ok), n, device),
+              "hpke_dhkem_auth_encap")
+    return enc, ss, ok
+
+
+def hpke_dhkem_auth_decap(kem, skR, enc, pkS, pkR=None, device=0):
+    """AuthDecapsulate(skR_i, enc_i, pkS_i) -> (ss, ok); pkR = skR's public key if the caller has it"""
+    N, S, n, (skR, enc, pkS, pkR) = _hpke_rows(kem, skR, enc, pkS, pkR)
+    ss, ok = np.empty((n, S), np.uint8), np.empty(n, np.uint8)
+    nat.check(nat.lib().circl_hip_hpke_dhkem_auth_decap(kem, _p(skR), _po(pkR), _p(enc), _p(pkS), _p(ss), _p(ok), n, device), "hpke_dhkem_auth_decap")
+    return ss, ok

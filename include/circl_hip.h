@@ -776,6 +776,52 @@ int circl_hip_hybrid_encaps_table_dev(const circl_hip_keytable *table, const uin
 int circl_hip_hybrid_decaps_table_dev(const circl_hip_keytable *table, const uint32_t *d_key_idx, const uint8_t *d_ct, uint8_t *d_ss,
                                       uint8_t *d_status, size_t n, void *d_ws, size_t ws_bytes, void *stream);
 
+/* ---- HPKE DHKEM over X25519 and X448 (hpke/kembase.go, hpke/xkem.go; RFC 9180 section 4.1) ------------------------------
+ * kem = CIRCL_HIP_HPKE_KEM_X25519_HKDF_SHA256 (0x20) or CIRCL_HIP_HPKE_KEM_X448_HKDF_SHA512 (0x21); any other value is
+ * CIRCL_HIP_EPARAM.  Every key row (ikm, sk, pk, enc) is circl_hip_hpke_dhkem_key_size(kem) = 32 / 56 bytes, a shared secret
+ * circl_hip_hpke_dhkem_ss_size(kem) = 32 / 64 bytes (kemBase.SharedKeySize = the hash size); both return 0 for an unknown kem.
+ * One fused kernel per call and one item per lane: the scalar multiplications (the fixed-base comb for a public key, the
+ * Montgomery ladder for a Diffie-Hellman output) and the HKDF between them run in one launch, without a workspace; the ephemeral
+ * private key, the Diffie-Hellman outputs and the HKDF pseudorandom keys stay in the lane.
+ *   derive_keypair: xKEM.DeriveKeyPair(ikm): sk = LabeledExpand(LabeledExtract("", "dkp_prk", ikm), "sk", "", Nsk), the raw Expand
+ *     output (unclamped, as the reference stores it); pk = KeyGen(sk).
+ *   encap:      EncapsulateDeterministically(pkR, ikmE) -> enc, ss.
+ *   decap:      Decapsulate(skR, enc) -> ss.
+ *   auth_encap: AuthEncapsulateDeterministically(pkR, skS, ikmE) -> enc, ss.
+ *   auth_decap: AuthDecapsulate(skR, enc, pkS) -> ss.
+ * The private key's own public key (pkR of decap / auth_decap, pkS of auth_encap) may be NULL: the kernel then computes it with
+ * the comb (the reference caches Public()).  kemCtx is built from the public-key bytes exactly as given: X25519 ignores bit 255 of
+ * a point in the ladder, but the bit still enters kemCtx (MarshalBinary returns the stored bytes).
+ * ok[i] = 0 where a Shared of item i returns false (the low-order points circl_hip_x25519 / circl_hip_x448 flag); ss[i], and
+ * enc[i] for the encapsulations, are then all zero (the reference returns nil, err).  ok may be NULL.
+ * GenerateKeyPair (a random sk, pk = KeyGen(sk)) is circl_hip_x25519 / circl_hip_x448 with point == NULL on sk rows the caller
+ * drew: there is no call of its own for it.
+ * The host forms stage through the pipeline and zero the device staging of every chunk; the _dev forms want 4-byte aligned
+ * pointers (CIRCL_HIP_EWORKSPACE otherwise).  n == 0 is CIRCL_HIP_OK. */
+#define CIRCL_HIP_HPKE_KEM_X25519_HKDF_SHA256 0x20
+#define CIRCL_HIP_HPKE_KEM_X448_HKDF_SHA512 0x21
+size_t circl_hip_hpke_dhkem_key_size(int kem);
+size_t circl_hip_hpke_dhkem_ss_size(int kem);
+int circl_hip_hpke_dhkem_derive_keypair(int kem, const uint8_t *ikm, uint8_t *sk, uint8_t *pk, size_t n, int device);
+int circl_hip_hpke_dhkem_encap(int kem, const uint8_t *pkR, const uint8_t *ikmE, uint8_t *enc, uint8_t *ss, uint8_t *ok, size_t n, int device);
+int circl_hip_hpke_dhkem_decap(int kem, const uint8_t *skR, const uint8_t *pkR, const uint8_t *enc, uint8_t *ss, uint8_t *ok, size_t n, int device);
+int circl_hip_hpke_dhkem_auth_encap(int kem, const uint8_t *pkR, const uint8_t *skS, const uint8_t *pkS, const uint8_t *ikmE, uint8_t *enc, uint8_t *ss,
+                                    uint8_t *ok, size_t n, int device);
+int circl_hip_hpke_dhkem_auth_decap(int kem, const uint8_t *skR, const uint8_t *pkR, const uint8_t *enc, const uint8_t *pkS, uint8_t *ss, uint8_t *ok,
+                                    size_t n, int device);
+int circl_hip_hpke_dhkem_derive_keypair_dev(int kem, const uint8_t *d_ikm, uint8_t *d_sk, uint8_t *d_pk, size_t n, void *stream);
+int circl_hip_hpke_dhkem_encap_dev(int kem, const uint8_t *d_pkR, const uint8_t *d_ikmE, uint8_t *d_enc, uint8_t *d_ss, uint8_t *d_ok, size_t n,
+                                   void *stream);
+int circl_hip_hpke_dhkem_decap_dev(int kem, const uint8_t *d_skR, const uint8_t *d_pkR, const uint8_t *d_enc, uint8_t *d_ss, uint8_t *d_ok, size_t n,
+                                   void *stream);
+int circl_hip_hpke_dhkem_auth_encap_dev(int kem, const uint8_t *d_pkR, const uint8_t *d_skS, const uint8_t *d_pkS, const uint8_t *d_ikmE, uint8_t *d_enc,
+                                        uint8_t *d_ss, uint8_t *d_ok, size_t n, void *stream);
+int circl_hip_hpke_dhkem_auth_decap_dev(int kem, const uint8_t *d_skR, const uint8_t *d_pkR, const uint8_t *d_enc, const uint8_t *d_pkS, uint8_t *d_ss,
+                                        uint8_t *d_ok, size_t n, void *stream);
+/* FIPS 180-4 SHA-256 of every message (crypto/sha256.Sum256): out32[i] = the 32-byte digest of item i; the ragged layout of
+ * circl_hip_sha512. */
+int circl_hip_sha256(const uint8_t *msg_blob, const uint64_t *msg_off, uint8_t *out32, size_t n, int device);
+
 /* ---- kernel-level profiling (used by bench.py for the roofline figures) --------------------
  * While enabled, every *_dev call brackets each kernel it enqueues with HIP events recorded on
  * the caller's stream.  circl_hip_profile_read synchronises the pending events, returns the
@@ -803,7 +849,10 @@ int circl_hip_hybrid_decaps_table_dev(const circl_hip_keytable *table, const uin
 #define CIRCL_HIP_KERNEL_FRODO_KEYGEN 20   /* FrodoKEM-640-SHAKE KeyGen (three launches) */
 #define CIRCL_HIP_KERNEL_FRODO_ENCAPS 21   /* FrodoKEM-640-SHAKE Encaps                */
 #define CIRCL_HIP_KERNEL_FRODO_DECAPS 22   /* FrodoKEM-640-SHAKE Decaps                */
-#define CIRCL_HIP_KERNEL_COUNT 23
+#define CIRCL_HIP_KERNEL_HPKE_X25519 23    /* HPKE DHKEM(X25519, HKDF-SHA256), every operation */
+#define CIRCL_HIP_KERNEL_HPKE_X448 24      /* HPKE DHKEM(X448, HKDF-SHA512), every operation   */
+#define CIRCL_HIP_KERNEL_SHA256 25         /* batch SHA-256                            */
+#define CIRCL_HIP_KERNEL_COUNT 26
 int circl_hip_profile_enable(int on);
 int circl_hip_profile_read(int kernel, double *total_ms, uint64_t *launches);
 /* The VALU issue rates this chip sustains, measured live (bench.py prices the kernels' VALU time against them instead of against
