@@ -56,7 +56,10 @@ SYMBOLS = [
     "circl_hip_hpke_dhkem_decap", "circl_hip_hpke_dhkem_auth_encap", "circl_hip_hpke_dhkem_auth_decap",
     "circl_hip_hpke_dhkem_derive_keypair_dev", "circl_hip_hpke_dhkem_encap_dev", "circl_hip_hpke_dhkem_decap_dev",
     "circl_hip_hpke_dhkem_auth_encap_dev", "circl_hip_hpke_dhkem_auth_decap_dev", "circl_hip_sha256",
-]
+    "circl_hip_hpke_context_size",
+] + [f + d for f in ("circl_hip_hpke_setup_sender", "circl_hip_hpke_setup_receiver", "circl_hip_hpke_seal", "circl_hip_hpke_open", "circl_hip_hpke_export",
+                     "circl_hip_hpke_seal_single", "circl_hip_hpke_open_single", "circl_hip_hpke_export_single", "circl_hip_hpke_export_single_receiver")
+     for d in ("", "_dev")]
 
 OK, EPARAM, ENODEV, EHIP, ENOMEM, EWORKSPACE, EBUSY, EAGAIN = 0, -1, -2, -3, -4, -5, -6, -7
 ALL_DEVICES = -1
@@ -248,6 +251,15 @@ def lib():
         L.circl_hip_hpke_dhkem_auth_encap_dev.argtypes = [i, vp, vp, vp, vp, vp, vp, vp, sz, vp]
         L.circl_hip_hpke_dhkem_auth_decap_dev.argtypes = [i, vp, vp, vp, vp, vp, vp, sz, vp]
         L.circl_hip_sha256.argtypes = [vp, vp, vp, sz, i]
+        L.circl_hip_hpke_context_size.restype, L.circl_hip_hpke_context_size.argtypes = sz, [i]
+        setup = [i, i, i, i] + [vp] * 10      # kem, kdf, aead, mode; four key rows; info, psk, psk_id as blob + offsets
+        for name, args in (("setup_sender", setup + [vp, vp, vp]), ("setup_receiver", setup + [vp, vp]),
+                           ("seal", [i, vp, sz, vp] + [vp] * 5), ("open", [i, vp, sz, vp] + [vp] * 6),
+                           ("export", [i, i, i, vp, sz, vp, vp, sz, vp]),
+                           ("seal_single", setup + [vp] * 7), ("open_single", setup + [vp] * 6),
+                           ("export_single", setup + [vp, vp, sz, vp, vp, vp]), ("export_single_receiver", setup + [vp, vp, sz, vp, vp])):
+            getattr(L, "circl_hip_hpke_" + name).argtypes = args + [sz, i]
+            getattr(L, "circl_hip_hpke_" + name + "_dev").argtypes = args + [sz, vp]
         for f in ("seed", "eseed", "pk", "sk", "ct", "ss"):
             fn = getattr(L, "circl_hip_hybrid_%s_size" % f)
             fn.restype, fn.argtypes = sz, [i]

@@ -1,0 +1,433 @@
+// api_hpke_ctx.hip -- batch HPKE contexts (hpke/hpke.go, hpke/util.go, hpke/aead.go; RFC 9180 sections 5 and 6) behind the C ABI
+// (include/circl_hip.h): Setup of a sender / a receiver, Seal, Open and Export on context rows, and the single-shot forms, over the
+// DHKEMs of api_hpke.hip, HKDF-SHA256 / HKDF-SHA512 and ChaCha20-Poly1305 or the export-only AEAD.  No CPU compute path.
+//
+// Every entry point fills one Call (the pointers as the ABI passes them: device pointers for a _dev form, host pointers for a
+// host form) and goes through check() -- the argument contract, before any device is looked for -- and then launch() or host().
+// Host forms whose outputs are fixed rows (Setup, Export, single-shot Export) go through shard / run_pipeline like the DHKEM's.
+// The pipeline has no ragged OUTPUT, so the host forms that write a ciphertext or plaintext blob (Seal, Open and their single-shot
+// forms) stage a shard themselves: device buffers of exactly the shard's bytes, secret uploads and downloads through page-locked
+// memory that is zeroed, and every device buffer zeroed before it is freed.
+#include "host_compose.h"
+#include "hpke_kernels.h"
+
+using namespace circl::host;
+namespace hp = circl::hpke;
+using circl::dhkem::X25519;
+using circl::dhkem::X448;
+using circl::hkdf::Sha256;
+using circl::hkdf::Sha512;
+
+namespace {
+
+enum Op { kSetupSender, kSetupReceiver, kSeal, kOpen, kExportRows };
+
+struct Call {
+    Op op;
+    int kem = 0x20, kdf = 1, aead = 3, mode = 0, what = hp::kStoreContext;
+    // setup
+    const uint8_t *pkR = nullptr, *ikmE = nullptr, *skR = nullptr, *skS = nullptr, *pkS = nullptr, *enc_in = nullptr;
+    uint8_t *enc_out = nullptr;
+    const uint8_t *info = nullptr, *psk = nullptr, *psk_id = nullptr;
+    const uint64_t *info_off = nullptr, *psk_off = nullptr, *psk_id_off = nullptr;
+    // context rows: written by a setup that stores them (stride = context_size), read by Seal / Open / Export
+    uint8_t *ctx_out = nullptr;
+    const uint8_t *ctx_in = nullptr;
+    size_t ctx_stride = 0;
+    const uint64_t *seq = nullptr;
+    // AEAD: in = plaintext blob (Seal) or ciphertext blob (Open), out = the other one
+    const uint8_t *in = nullptr, *aad = nullptr;
+    const uint64_t *pt_off = nullptr, *aad_off = nullptr;
+    uint8_t *out = nullptr;
+    // Export
+    const uint8_t *exp = nullptr;
+    const uint64_t *exp_off = nullptr;
+    size_t L = 0;
+    uint8_t *exp_out = nullptr;
+    uint8_t *ok = nullptr;
+    size_t n = 0;
+
+    bool setup() const { return op == kSetupSender || op == kSetupReceiver; }
+    bool sender() const { return op == kSetupSender || op == kSeal; }
+    bool does_aead() const { return op == kSeal || op == kOpen || (setup() && what == hp::kAead); }
+    bool does_export() const { return op == kExportRows || (setup() && what == hp::kExport); }
+};
+
+size_t key_bytes(int kem) { return kem == 0x20 ? 32 : 56; }
+size_t hash_bytes(int kdf) { return kdf == 1 ? 32 : kdf == 3 ? 64 : 0; }
+size_t ctx_bytes(int kdf) { return hash_bytes(kdf) ? 48 + hash_bytes(kdf) : 0; }
+
+// the argument contract, the same for both forms; nothing here looks for a device
+int check(const Call &c) {
+    const bool kem_ok = c.kem == 0x20 || c.kem == 0x21, kdf_ok = c.kdf == 1 || c.kdf == 3;
+    const bool aead_ok = c.aead == hp::AEAD_CHACHA20POLY1305 || c.aead == hp::AEAD_EXPORT_ONLY;
+    if (c.setup() || c.does_export()) {
+        if (!kem_ok || !kdf_ok || !aead_ok) return CIRCL_HIP_EPARAM;
+    }
+    if (c.does_aead() && c.aead != hp::AEAD_CHACHA20POLY1305) return CIRCL_HIP_EPARAM;  // export-only has no Seal / Open
+    if (c.setup() && (c.mode < 0 || c.mode > 3)) return CIRCL_HIP_EPARAM;
+    if (c.does_export() && (c.L == 0 || c.L > 255 * hash_bytes(c.kdf))) return CIRCL_HIP_EPARAM;
+    if (!c.setup()) {
+        if (c.ctx_stride % 4 || c.ctx_stride < (c.op == kExportRows ? ctx_bytes(c.kdf) : size_t(48))) return CIRCL_HIP_EPARAM;
+    }
+    if (c.n == 0) return CIRCL_HIP_OK;
+    if (c.setup()) {
+        const bool auth = c.mode & 2, with_psk = c.mode & 1;
+        if (!with_psk && (c.psk || c.psk_id)) return CIRCL_HIP_EPARAM;
+        if (c.op == kSetupSender) {
+            if (!c.pkR || !c.ikmE || !c.enc_out) return CIRCL_HIP_EPARAM;
+            if (auth ? (!c.skS || !c.pkS) : (c.skS || c.pkS)) return CIRCL_HIP_EPARAM;
+        } else {
+            if (!c.skR || !c.enc_in) return CIRCL_HIP_EPARAM;
+            if (auth ? !c.pkS : c.pkS != nullptr) return CIRCL_HIP_EPARAM;
+        }
+        if ((c.info && !c.info_off) || (c.psk && !c.psk_off) || (c.psk_id && !c.psk_id_off)) return CIRCL_HIP_EPARAM;
+        if (c.what == hp::kStoreContext && !c.ctx_out) return CIRCL_HIP_EPARAM;
+    } else if (!c.ctx_in) {
+        return CIRCL_HIP_EPARAM;
+    }
+    if (c.does_aead()) {
+        // a NULL plaintext blob with offsets means empty plaintexts; a ciphertext always has its tags
+        if (!c.out || (c.aad && !c.aad_off)) return CIRCL_HIP_EPARAM;
+        if (c.sender() ? (c.in && !c.pt_off) : !c.in) return CIRCL_HIP_EPARAM;
+    }
+    if (c.does_export() && (!c.exp_out || (c.exp && !c.exp_off))) return CIRCL_HIP_EPARAM;
+    return CIRCL_HIP_OK;
+}
+
+const uint32_t *w(const uint8_t *p) { return reinterpret_cast<const uint32_t *>(p); }
+uint32_t *w(uint8_t *p) { return reinterpret_cast<uint32_t *>(p); }
+
+// one launch on device pointers
+int launch(const Call &c, hipStream_t st) {
+    if (!aligned<4>(c.pkR, c.ikmE, c.skR, c.skS, c.pkS, c.enc_in, c.enc_out, c.ctx_in, c.ctx_out) ||
+        !aligned<8>(c.info_off, c.psk_off, c.psk_id_off, c.pt_off, c.aad_off, c.exp_off, c.seq))
+        return CIRCL_HIP_EWORKSPACE;
+    if (ndev() <= 0) return CIRCL_HIP_ENODEV;
+    const dim3 grid = lanes_grid(c.n), block(64);
+    if (c.setup()) {
+        hp::SetupArgs a = {};
+        a.pkR = w(c.pkR); a.ikmE = w(c.ikmE); a.skR = w(c.skR); a.skS = w(c.skS); a.pkS = w(c.pkS);
+        a.enc_out = w(c.enc_out); a.enc_in = w(c.enc_in);
+        a.info = c.info; a.psk = c.psk; a.psk_id = c.psk_id;
+        a.info_off = c.info_off; a.psk_off = c.psk_off; a.psk_id_off = c.psk_id_off;
+        a.ok = c.ok;
+        a.kem = c.kem; a.kdf = c.kdf; a.aead = c.aead; a.mode = c.mode; a.what = c.what;
+        a.ctx = w(c.ctx_out); a.ctx_stride_words = ctx_bytes(c.kdf) / 4;
+        // a Seal without a plaintext blob: every plaintext is empty and the offsets are not read
+        a.in = c.in; a.aad = c.aad; a.pt_off = c.in ? c.pt_off : nullptr; a.aad_off = c.aad_off; a.out = c.out;
+        a.exp = c.exp; a.exp_off = c.exp_off; a.L = (uint32_t)c.L; a.exp_out = c.exp_out;
+        a.n = c.n;
+        ProfScope ps(CIRCL_HIP_KERNEL_HPKE_SETUP, st);
+        const bool snd = c.op == kSetupSender, s256 = c.kdf == 1;
+#define SETUP_LAUNCH(C, HK)                                                                                      \
+    do {                                                                                                         \
+        if (snd) hipLaunchKernelGGL((hp::setup_kernel<C, HK, true>), grid, block, 0, st, a);                     \
+        else hipLaunchKernelGGL((hp::setup_kernel<C, HK, false>), grid, block, 0, st, a);                        \
+    } while (0)
+        if (c.kem == 0x20 && s256) SETUP_LAUNCH(X25519, Sha256);
+        else if (c.kem == 0x20) SETUP_LAUNCH(X25519, Sha512);
+        else if (s256) SETUP_LAUNCH(X448, Sha256);
+        else SETUP_LAUNCH(X448, Sha512);
+#undef SETUP_LAUNCH
+    } else if (c.op == kExportRows) {
+        const hp::ExportArgs a = {w(c.ctx_in), c.ctx_stride / 4, c.kem, c.kdf, c.aead, c.exp, c.exp_off, (uint32_t)c.L, c.exp_out, c.n};
+        ProfScope ps(CIRCL_HIP_KERNEL_HPKE_EXPORT, st);
+        if (c.kdf == 1) hipLaunchKernelGGL(hp::export_kernel<Sha256>, grid, block, 0, st, a);
+        else hipLaunchKernelGGL(hp::export_kernel<Sha512>, grid, block, 0, st, a);
+    } else {
+        const hp::AeadArgs a = {w(c.ctx_in), c.ctx_stride / 4, c.seq, c.in, c.aad, c.in ? c.pt_off : nullptr, c.aad_off, c.out, c.ok, c.n};
+        ProfScope ps(CIRCL_HIP_KERNEL_HPKE_AEAD, st);
+        if (c.op == kSeal) hipLaunchKernelGGL(hp::aead_kernel<true>, grid, block, 0, st, a);
+        else hipLaunchKernelGGL(hp::aead_kernel<false>, grid, block, 0, st, a);
+    }
+    HIP_TRY(hipGetLastError());
+    return CIRCL_HIP_OK;
+}
+
+int dev_form(const Call &c, void *stream) {
+    if (int rc = check(c)) return rc;
+    if (c.n == 0) return CIRCL_HIP_OK;
+    return launch(c, static_cast<hipStream_t>(stream));
+}
+
+// ---- host forms with fixed output rows: the pipeline --------------------------------------------------------------------------
+int host_rows(const Call &c, int device) {
+    const size_t N = key_bytes(c.kem), CS = c.setup() ? ctx_bytes(c.kdf) : c.ctx_stride;
+    const PipeOpts opts = secret_opts(size_t(1) << 16);
+    return shard(c.n, device, [&](int dev, size_t lo, size_t cnt) {
+        std::vector<HIn> ins;
+        std::vector<HBlob> blobs;
+        std::vector<HOut> outs;
+        auto in = [&](const uint8_t *p, size_t row, bool secret) {
+            if (!p) return -1;
+            ins.push_back({p + lo * row, row, secret});
+            return (int)ins.size() - 1;
+        };
+        auto blob = [&](const uint8_t *b, const uint64_t *off, bool secret) {
+            if (!b) return -1;
+            blobs.push_back({b, off + lo, secret});
+            return (int)blobs.size() - 1;
+        };
+        auto out = [&](uint8_t *p, size_t row, bool secret, bool want) {
+            if (!want) return -1;
+            outs.push_back({p ? p + lo * row : nullptr, row, secret});
+            return (int)outs.size() - 1;
+        };
+        const int i_pkR = in(c.pkR, N, false), i_ikmE = in(c.ikmE, N, true), i_skR = in(c.skR, N, true), i_skS = in(c.skS, N, true), i_pkS = in(c.pkS, N, false),
+                  i_enc = in(c.enc_in, N, false), i_ctx = in(c.ctx_in, CS, true);
+        const int b_info = blob(c.info, c.info_off, false), b_psk = blob(c.psk, c.psk_off, true), b_id = blob(c.psk_id, c.psk_id_off, false),
+                  b_exp = blob(c.exp, c.exp_off, false);
+        const int o_enc = out(c.enc_out, N, false, c.op == kSetupSender), o_ctx = out(c.ctx_out, CS, true, c.setup() && c.what == hp::kStoreContext),
+                  o_exp = out(c.exp_out, c.L, true, c.does_export()), o_ok = out(c.ok, 1, false, c.setup());
+        return run_pipeline(dev, cnt, ins, blobs, outs, kNoWs, opts, [&](Chunk &k) {
+            auto I = [&](int j) -> const uint8_t * { return j < 0 ? nullptr : k.in[j]; };
+            auto B = [&](int j) -> const uint8_t * { return j < 0 ? nullptr : k.blob[j]; };
+            auto F = [&](int j) -> const uint64_t * { return j < 0 ? nullptr : k.off[j]; };
+            auto O = [&](int j) -> uint8_t * { return j < 0 ? nullptr : k.out[j]; };
+            Call d = c;
+            d.pkR = I(i_pkR); d.ikmE = I(i_ikmE); d.skR = I(i_skR); d.skS = I(i_skS); d.pkS = I(i_pkS); d.enc_in = I(i_enc); d.ctx_in = I(i_ctx);
+            d.info = B(b_info); d.info_off = F(b_info); d.psk = B(b_psk); d.psk_off = F(b_psk); d.psk_id = B(b_id); d.psk_id_off = F(b_id);
+            d.exp = B(b_exp); d.exp_off = F(b_exp);
+            d.enc_out = O(o_enc); d.ctx_out = O(o_ctx); d.exp_out = O(o_exp); d.ok = O(o_ok);
+            d.n = k.cnt;
+            return launch(d, k.st);
+        });
+    }, kHeavyOneDeviceMax);
+}
+
+// ---- host forms that write a ragged blob: a shard staged by hand ---------------------------------------------------------------
+struct Stage {
+    hipStream_t st = nullptr;
+    std::vector<std::pair<uint8_t *, size_t>> bufs;
+    int rc = CIRCL_HIP_OK;
+    ~Stage() {
+        for (auto &b : bufs) {
+            (void)hipMemsetAsync(b.first, 0, b.second, st);
+        }
+        (void)hipStreamSynchronize(st);
+        for (auto &b : bufs) (void)hipFree(b.first);
+        (void)hipGetLastError();
+    }
+    uint8_t *alloc(size_t bytes) {
+        void *d = nullptr;
+        const size_t cap = bytes + 16;
+        if (rc == CIRCL_HIP_OK && hipMalloc(&d, cap) != hipSuccess) { (void)hipGetLastError(); rc = CIRCL_HIP_ENOMEM; }
+        if (!d) return nullptr;
+        bufs.push_back({static_cast<uint8_t *>(d), cap});
+        return static_cast<uint8_t *>(d);
+    }
+    // a device copy of h[0 .. bytes) (nullptr stays nullptr), through page-locked memory that is zeroed
+    const uint8_t *up(const void *h, size_t bytes) {
+        if (!h) return nullptr;
+        uint8_t *d = alloc(bytes);
+        if (d && rc == CIRCL_HIP_OK) rc = upload_secret(d, h, bytes, st);
+        return d;
+    }
+    uint8_t *zeros(size_t bytes) {
+        uint8_t *d = alloc(bytes);
+        if (d && rc == CIRCL_HIP_OK && hipMemsetAsync(d, 0, bytes + 16, st) != hipSuccess) rc = CIRCL_HIP_EHIP;
+        return d;
+    }
+    // h[0 .. bytes) = d[0 .. bytes), through page-locked memory that is zeroed
+    void down(void *h, const uint8_t *d, size_t bytes) {
+        if (!h || !bytes || rc != CIRCL_HIP_OK) return;
+        void *pin = nullptr;
+        if (pinned_alloc(&pin, bytes) != hipSuccess) { (void)hipGetLastError(); rc = CIRCL_HIP_ENOMEM; return; }
+        if (hipMemcpyAsync(pin, d, bytes, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) rc = CIRCL_HIP_EHIP;
+        else memcpy(h, pin, bytes);
+        volatile uint8_t *z = static_cast<volatile uint8_t *>(pin);
+        for (size_t i = 0; i < bytes; i++) z[i] = 0;
+        (void)pinned_free(pin);
+    }
+};
+
+int host_ragged(const Call &c, int device) {
+    const size_t N = key_bytes(c.kem);
+    return shard(c.n, device, [&](int dev, size_t lo, size_t cnt) {
+        if (dev < 0 || dev >= ndev()) return (int)CIRCL_HIP_ENODEV;
+        HIP_TRY(hipSetDevice(physical_device(dev)));
+        Stage s;
+        hipStream_t h2d = nullptr, d2h = nullptr;
+        TRY(pipeline_streams(dev, &h2d, &d2h, &s.st));
+        Call d = c;
+        const uint64_t *pt_off = (c.sender() && !c.in) ? nullptr : c.pt_off;  // a Seal without a plaintext blob: every plaintext is empty
+        auto rows = [&](const uint8_t *p, size_t row) { return p ? s.up(p + lo * row, cnt * row) : nullptr; };
+        // a blob's shard, rebased so that the caller's absolute offsets index it
+        auto blob = [&](const uint8_t *b, const uint64_t *off, const uint64_t *&d_off) -> const uint8_t * {
+            d_off = off ? reinterpret_cast<const uint64_t *>(s.up(off + lo, (cnt + 1) * 8)) : nullptr;
+            if (!b || !off) return nullptr;
+            const uint8_t *p = s.up(b + off[lo], (size_t)(off[lo + cnt] - off[lo]));
+            return p ? p - off[lo] : nullptr;
+        };
+        d.pkR = rows(c.pkR, N); d.ikmE = rows(c.ikmE, N); d.skR = rows(c.skR, N); d.skS = rows(c.skS, N); d.pkS = rows(c.pkS, N); d.enc_in = rows(c.enc_in, N);
+        d.ctx_in = rows(c.ctx_in, c.ctx_stride);
+        d.seq = reinterpret_cast<const uint64_t *>(rows(reinterpret_cast<const uint8_t *>(c.seq), 8));
+        d.info = blob(c.info, c.info_off, d.info_off);
+        d.psk = blob(c.psk, c.psk_off, d.psk_off);
+        d.psk_id = blob(c.psk_id, c.psk_id_off, d.psk_id_off);
+        d.aad = blob(c.aad, c.aad_off, d.aad_off);
+        // plaintext bytes [p0, p1) of this shard; its ciphertext is 16 cnt bytes longer and starts 16 lo bytes further on
+        const uint64_t p0 = pt_off ? pt_off[lo] : 0, p1 = pt_off ? pt_off[lo + cnt] : 0;
+        const size_t pt_bytes = (size_t)(p1 - p0), ct_bytes = pt_bytes + 16 * cnt, in_bytes = c.sender() ? pt_bytes : ct_bytes, out_bytes = c.sender() ? ct_bytes : pt_bytes;
+        d.pt_off = pt_off ? reinterpret_cast<const uint64_t *>(s.up(pt_off + lo, (cnt + 1) * 8)) : nullptr;
+        const uint8_t *h_in = c.in ? c.in + p0 + (c.sender() ? 0 : 16 * lo) : nullptr;
+        const uint8_t *d_in = h_in ? s.up(h_in, in_bytes) : nullptr;
+        d.in = d_in ? d_in - p0 : nullptr;
+        uint8_t *d_out = s.zeros(out_bytes);
+        d.out = d_out ? d_out - p0 : nullptr;
+        uint8_t *d_enc = c.op == kSetupSender ? s.zeros(cnt * N) : nullptr, *d_ok = c.op != kSeal ? s.zeros(cnt) : nullptr;
+        d.enc_out = d_enc; d.ok = d_ok;
+        d.n = cnt;
+        TRY(s.rc);
+        TRY(launch(d, s.st));
+        s.down(c.out + p0 + (c.sender() ? 16 * lo : 0), d_out, out_bytes);
+        if (d_enc) s.down(c.enc_out + lo * N, d_enc, cnt * N);
+        if (d_ok && c.ok) s.down(c.ok + lo, d_ok, cnt);
+        return s.rc;
+    }, kHeavyOneDeviceMax);
+}
+
+int host_form(const Call &c, int device) {
+    if (int rc = check(c)) return rc;
+    if (c.n == 0) return CIRCL_HIP_OK;
+    return c.does_aead() ? host_ragged(c, device) : host_rows(c, device);
+}
+
+Call sender_call(int kem, int kdf, int aead, int mode, const uint8_t *pkR, const uint8_t *ikmE, const uint8_t *skS, const uint8_t *pkS, const uint8_t *info_blob,
+                 const uint64_t *info_off, const uint8_t *psk_blob, const uint64_t *psk_off, const uint8_t *psk_id_blob, const uint64_t *psk_id_off, uint8_t *enc,
+                 uint8_t *ok, size_t n) {
+    Call c;
+    c.op = kSetupSender; c.kem = kem; c.kdf = kdf; c.aead = aead; c.mode = mode;
+    c.pkR = pkR; c.ikmE = ikmE; c.skS = skS; c.pkS = pkS; c.enc_out = enc;
+    c.info = info_blob; c.info_off = info_off; c.psk = psk_blob; c.psk_off = psk_off; c.psk_id = psk_id_blob; c.psk_id_off = psk_id_off;
+    c.ok = ok; c.n = n;
+    return c;
+}
+
+Call receiver_call(int kem, int kdf, int aead, int mode, const uint8_t *skR, const uint8_t *pkR, const uint8_t *enc, const uint8_t *pkS, const uint8_t *info_blob,
+                   const uint64_t *info_off, const uint8_t *psk_blob, const uint64_t *psk_off, const uint8_t *psk_id_blob, const uint64_t *psk_id_off, uint8_t *ok,
+                   size_t n) {
+    Call c;
+    c.op = kSetupReceiver; c.kem = kem; c.kdf = kdf; c.aead = aead; c.mode = mode;
+    c.skR = skR; c.pkR = pkR; c.enc_in = enc; c.pkS = pkS;
+    c.info = info_blob; c.info_off = info_off; c.psk = psk_blob; c.psk_off = psk_off; c.psk_id = psk_id_blob; c.psk_id_off = psk_id_off;
+    c.ok = ok; c.n = n;
+    return c;
+}
+
+void with_aead(Call &c, const uint8_t *in, const uint64_t *pt_off, const uint8_t *aad, const uint64_t *aad_off, uint8_t *out) {
+    c.what = hp::kAead; c.in = in; c.pt_off = pt_off; c.aad = aad; c.aad_off = aad_off; c.out = out;
+}
+void with_export(Call &c, const uint8_t *exp, const uint64_t *exp_off, size_t L, uint8_t *out) {
+    c.what = hp::kExport; c.exp = exp; c.exp_off = exp_off; c.L = L; c.exp_out = out;
+}
+Call rows_call(Op op, int aead, const uint8_t *ctx, size_t ctx_stride, size_t n) {
+    Call c;
+    c.op = op; c.aead = aead; c.ctx_in = ctx; c.ctx_stride = ctx_stride; c.n = n;
+    return c;
+}
+
+int run(const Call &c, bool dev, int device, void *stream) { return dev ? dev_form(c, stream) : host_form(c, device); }
+
+}  // namespace
+
+// the setup arguments of a sender / a receiver as every entry point spells them
+#define SENDER_PARAMS                                                                                                                                       \
+    int kem, int kdf, int aead, int mode, const uint8_t *pkR, const uint8_t *ikmE, const uint8_t *skS, const uint8_t *pkS, const uint8_t *info_blob,        \
+        const uint64_t *info_off, const uint8_t *psk_blob, const uint64_t *psk_off, const uint8_t *psk_id_blob, const uint64_t *psk_id_off
+#define SENDER_ARGS kem, kdf, aead, mode, pkR, ikmE, skS, pkS, info_blob, info_off, psk_blob, psk_off, psk_id_blob, psk_id_off
+#define RECEIVER_PARAMS                                                                                                                                     \
+    int kem, int kdf, int aead, int mode, const uint8_t *skR, const uint8_t *pkR, const uint8_t *enc, const uint8_t *pkS, const uint8_t *info_blob,         \
+        const uint64_t *info_off, const uint8_t *psk_blob, const uint64_t *psk_off, const uint8_t *psk_id_blob, const uint64_t *psk_id_off
+#define RECEIVER_ARGS kem, kdf, aead, mode, skR, pkR, enc, pkS, info_blob, info_off, psk_blob, psk_off, psk_id_blob, psk_id_off
+
+// both forms of one entry point: NAME(params..., n, int device) and NAME_dev(params..., n, void *stream)
+#define BOTH_FORMS(NAME, PARAMS, BODY)                                        \
+    int NAME(PARAMS, size_t n, int device) {                                  \
+        const bool dev_ = false;                                              \
+        void *stream = nullptr;                                               \
+        BODY                                                                  \
+    }                                                                         \
+    int NAME##_dev(PARAMS, size_t n, void *stream) {                          \
+        const bool dev_ = true;                                               \
+        const int device = 0;                                                 \
+        BODY                                                                  \
+    }
+#define P(...) __VA_ARGS__
+
+extern "C" {
+
+size_t circl_hip_hpke_context_size(int kdf) { return ctx_bytes(kdf); }
+
+BOTH_FORMS(circl_hip_hpke_setup_sender, P(SENDER_PARAMS, uint8_t *enc, uint8_t *ctx, uint8_t *ok), {
+    Call c = sender_call(SENDER_ARGS, enc, ok, n);
+    c.ctx_out = ctx;
+    return run(c, dev_, device, stream);
+})
+
+BOTH_FORMS(circl_hip_hpke_setup_receiver, P(RECEIVER_PARAMS, uint8_t *ctx, uint8_t *ok), {
+    Call c = receiver_call(RECEIVER_ARGS, ok, n);
+    c.ctx_out = ctx;
+    return run(c, dev_, device, stream);
+})
+
+BOTH_FORMS(circl_hip_hpke_seal,
+           P(int aead, const uint8_t *ctx, size_t ctx_stride, const uint64_t *seq, const uint8_t *pt_blob, const uint64_t *pt_off, const uint8_t *aad_blob,
+             const uint64_t *aad_off, uint8_t *ct_blob),
+           {
+               Call c = rows_call(kSeal, aead, ctx, ctx_stride, n);
+               c.seq = seq;
+               with_aead(c, pt_blob, pt_off, aad_blob, aad_off, ct_blob);
+               return run(c, dev_, device, stream);
+           })
+
+BOTH_FORMS(circl_hip_hpke_open,
+           P(int aead, const uint8_t *ctx, size_t ctx_stride, const uint64_t *seq, const uint8_t *ct_blob, const uint64_t *pt_off, const uint8_t *aad_blob,
+             const uint64_t *aad_off, uint8_t *pt_blob, uint8_t *ok),
+           {
+               Call c = rows_call(kOpen, aead, ctx, ctx_stride, n);
+               c.seq = seq;
+               c.ok = ok;
+               with_aead(c, ct_blob, pt_off, aad_blob, aad_off, pt_blob);
+               return run(c, dev_, device, stream);
+           })
+
+BOTH_FORMS(circl_hip_hpke_export,
+           P(int kdf, int kem, int aead, const uint8_t *ctx, size_t ctx_stride, const uint8_t *exp_blob, const uint64_t *exp_off, size_t L, uint8_t *out), {
+               Call c = rows_call(kExportRows, aead, ctx, ctx_stride, n);
+               c.kem = kem;
+               c.kdf = kdf;
+               with_export(c, exp_blob, exp_off, L, out);
+               return run(c, dev_, device, stream);
+           })
+
+BOTH_FORMS(circl_hip_hpke_seal_single,
+           P(SENDER_PARAMS, const uint8_t *pt_blob, const uint64_t *pt_off, const uint8_t *aad_blob, const uint64_t *aad_off, uint8_t *enc, uint8_t *ct_blob,
+             uint8_t *ok),
+           {
+               Call c = sender_call(SENDER_ARGS, enc, ok, n);
+               with_aead(c, pt_blob, pt_off, aad_blob, aad_off, ct_blob);
+               return run(c, dev_, device, stream);
+           })
+
+BOTH_FORMS(circl_hip_hpke_open_single,
+           P(RECEIVER_PARAMS, const uint8_t *ct_blob, const uint64_t *pt_off, const uint8_t *aad_blob, const uint64_t *aad_off, uint8_t *pt_blob, uint8_t *ok), {
+               Call c = receiver_call(RECEIVER_ARGS, ok, n);
+               with_aead(c, ct_blob, pt_off, aad_blob, aad_off, pt_blob);
+               return run(c, dev_, device, stream);
+           })
+
+BOTH_FORMS(circl_hip_hpke_export_single, P(SENDER_PARAMS, const uint8_t *exp_blob, const uint64_t *exp_off, size_t L, uint8_t *enc, uint8_t *out, uint8_t *ok), {
+    Call c = sender_call(SENDER_ARGS, enc, ok, n);
+    with_export(c, exp_blob, exp_off, L, out);
+    return run(c, dev_, device, stream);
+})
+
+BOTH_FORMS(circl_hip_hpke_export_single_receiver, P(RECEIVER_PARAMS, const uint8_t *exp_blob, const uint64_t *exp_off, size_t L, uint8_t *out, uint8_t *ok), {
+    Call c = receiver_call(RECEIVER_ARGS, ok, n);
+    with_export(c, exp_blob, exp_off, L, out);
+    return run(c, dev_, device, stream);
+})
+
+}  // extern "C"

@@ -147,6 +147,7 @@ struct HIn {                 // fixed-size rows: item i is row i
 struct HBlob {               // ragged rows: item i is blob[off[i] .. off[i+1]); blob == nullptr: absent (kernels get nullptr)
     const uint8_t *blob;
     const uint64_t *off;
+    bool secret = false;     // wipe the staging copy afterwards (run_pipeline; a coalesced batch takes no secret blob)
 };
 struct HOut {
     uint8_t *p;              // nullptr: the device buffer exists but nothing is copied back

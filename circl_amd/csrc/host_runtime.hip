@@ -723,7 +723,10 @@ int run_pipeline(int dev, size_t n, const std::vector<HIn> &ins, const std::vect
             }
         for (size_t k = 0; k < blobs.size(); k++) {
             if (!blobs[k].blob) continue;
-            if (sblob[k].staged && sblob[k].bytes) jobs.push_back({slot->hin + sblob[k].hofs, blobs[k].blob + blobs[k].off[lo], sblob[k].bytes});
+            if (sblob[k].staged && sblob[k].bytes) {
+                jobs.push_back({slot->hin + sblob[k].hofs, blobs[k].blob + blobs[k].off[lo], sblob[k].bytes});
+                if (blobs[k].secret) cur.secret_in.push_back(sblob[k]);
+            }
             jobs.push_back({slot->hin + soff[k].hofs, blobs[k].off + lo, soff[k].bytes});
         }
         const bool retire_front = inflight.size() > depth;  // (the new chunk is already in the deque)

@@ -17,7 +17,7 @@ KERNELS = {"mlkem_hash": 0, "mlkem_encrypt": 1, "mlkem_decrypt": 2, "mlkem_keyge
            "ed25519_keygen": 12, "ed25519_sign": 13, "ed25519_verify": 14, "sha512": 15,
            "x448": 16, "ed448_keygen": 17, "ed448_sign": 18, "ed448_verify": 19,
            "frodo_keygen": 20, "frodo_encaps": 21, "frodo_decaps": 22,
-           "hpke_x25519": 23, "hpke_x448": 24, "sha256": 25}
+           "hpke_x25519": 23, "hpke_x448": 24, "sha256": 25, "hpke_setup": 26, "hpke_aead": 27, "hpke_export": 28}
 
 
 def _stream():
@@ -383,3 +383,111 @@ class HpkeDhkemDevice:
         nat.check(self.L.circl_hip_hpke_dhkem_auth_decap_dev(self.kem, _chk(skR, self.N), self._opt(pkR), _chk(enc, self.N), _chk(pkS, self.N),
                                                              _chk(ss, self.S), _chk(ok), n, _stream()), "hpke_dhkem_auth_decap_dev")
         return ss, ok
+
+
+class Ragged:
+    """n byte strings on the device: blob (uint8) and the n + 1 offsets (int64 tensor holding the uint64 values).  None stands for
+    'every item empty' wherever a Ragged is expected."""
+
+    def __init__(self, items, device="cuda"):
+        import numpy as np
+        off = np.zeros(len(items) + 1, np.int64)
+        off[1:] = np.cumsum([len(x) for x in items])
+        self.lens = [len(x) for x in items]
+        self.off_host = off
+        self.blob = torch.from_numpy(np.frombuffer(b"".join(bytes(x) for x in items) + bytes(16), np.uint8).copy()).to(device)
+        self.off = torch.from_numpy(off).to(device)
+
+    def args(self):
+        return self.blob.data_ptr(), self.off.data_ptr()
+
+
+def _rag_args(r):
+    return (None, None) if r is None else r.args()
+
+
+class HpkeSuiteDevice:
+    """One HPKE suite (kem, kdf, aead) on resident tensors (circl_hip_hpke_*_dev), on torch's current stream.  Key rows are (n, N), context
+    rows (n, CS); ragged inputs are Ragged objects (or None).  Ciphertexts / plaintexts are flat uint8 tensors laid out by the plaintext
+    offsets: item i's ciphertext is at pt_off[i] + 16 i."""
+
+    def __init__(self, kem, kdf, aead, device="cuda"):
+        self.kem, self.kdf, self.aead, self.device = kem, kdf, aead, device
+        self.L = nat.lib()
+        self.N, self.CS = self.L.circl_hip_hpke_dhkem_key_size(kem), self.L.circl_hip_hpke_context_size(kdf)
+        if not self.N or not self.CS:
+            raise ValueError("HPKE suite (0x%x, 0x%x, 0x%x) is not served" % (kem, kdf, aead))
+
+    def _out(self, *shape):
+        return torch.empty(shape, dtype=torch.uint8, device=self.device)
+
+    def _row(self, t):
+        return None if t is None else _chk(t, self.N)
+
+    def _setup(self, mode, rows, info, psk, psk_id):
+        return [self.kem, self.kdf, self.aead, mode] + [self._row(r) for r in rows] + [*_rag_args(info), *_rag_args(psk), *_rag_args(psk_id)]
+
+    def setup_sender(self, mode, pkR, ikmE, info=None, psk=None, psk_id=None, skS=None, pkS=None):
+        n = pkR.shape[0]
+        enc, ctx, ok = self._out(n, self.N), self._out(n, self.CS), self._out(n)
+        nat.check(self.L.circl_hip_hpke_setup_sender_dev(*self._setup(mode, (pkR, ikmE, skS, pkS), info, psk, psk_id), _chk(enc), _chk(ctx), _chk(ok), n,
+                                                         _stream()), "hpke_setup_sender_dev")
+        return enc, ctx, ok
+
+    def setup_receiver(self, mode, skR, enc, info=None, psk=None, psk_id=None, pkS=None, pkR=None):
+        n = skR.shape[0]
+        ctx, ok = self._out(n, self.CS), self._out(n)
+        nat.check(self.L.circl_hip_hpke_setup_receiver_dev(*self._setup(mode, (skR, pkR, enc, pkS), info, psk, psk_id), _chk(ctx), _chk(ok), n, _stream()),
+                  "hpke_setup_receiver_dev")
+        return ctx, ok
+
+    def seal(self, ctx, pt, aad=None, seq=None):
+        """pt: Ragged; seq: int64 tensor holding the uint64 sequence numbers, or None -> flat ciphertext tensor"""
+        n = ctx.shape[0]
+        ct = self._out(int(pt.off_host[n]) + 16 * n)
+        nat.check(self.L.circl_hip_hpke_seal_dev(self.aead, _chk(ctx, self.CS), self.CS, None if seq is None else seq.data_ptr(), *pt.args(), *_rag_args(aad),
+                                                 _chk(ct), n, _stream()), "hpke_seal_dev")
+        return ct
+
+    def open(self, ctx, ct, pt_off, aad=None, seq=None):
+        """ct: flat tensor; pt_off: Ragged giving the plaintext layout (its blob is not read) -> (flat plaintext tensor, ok)"""
+        n = ctx.shape[0]
+        pt, ok = self._out(int(pt_off.off_host[n]) + 1), self._out(n)
+        nat.check(self.L.circl_hip_hpke_open_dev(self.aead, _chk(ctx, self.CS), self.CS, None if seq is None else seq.data_ptr(), _chk(ct), pt_off.off.data_ptr(),
+                                                 *_rag_args(aad), _chk(pt), _chk(ok), n, _stream()), "hpke_open_dev")
+        return pt, ok
+
+    def export(self, ctx, exporter_context, length):
+        n = ctx.shape[0]
+        out = self._out(n, length)
+        nat.check(self.L.circl_hip_hpke_export_dev(self.kdf, self.kem, self.aead, _chk(ctx, self.CS), self.CS, *_rag_args(exporter_context), length, _chk(out), n,
+                                                   _stream()), "hpke_export_dev")
+        return out
+
+    def seal_single(self, mode, pkR, ikmE, pt, aad=None, info=None, psk=None, psk_id=None, skS=None, pkS=None):
+        n = pkR.shape[0]
+        enc, ct, ok = self._out(n, self.N), self._out(int(pt.off_host[n]) + 16 * n), self._out(n)
+        nat.check(self.L.circl_hip_hpke_seal_single_dev(*self._setup(mode, (pkR, ikmE, skS, pkS), info, psk, psk_id), *pt.args(), *_rag_args(aad), _chk(enc),
+                                                        _chk(ct), _chk(ok), n, _stream()), "hpke_seal_single_dev")
+        return enc, ct, ok
+
+    def open_single(self, mode, skR, enc, ct, pt_off, aad=None, info=None, psk=None, psk_id=None, pkS=None, pkR=None):
+        n = skR.shape[0]
+        pt, ok = self._out(int(pt_off.off_host[n]) + 1), self._out(n)
+        nat.check(self.L.circl_hip_hpke_open_single_dev(*self._setup(mode, (skR, pkR, enc, pkS), info, psk, psk_id), _chk(ct), pt_off.off.data_ptr(),
+                                                        *_rag_args(aad), _chk(pt), _chk(ok), n, _stream()), "hpke_open_single_dev")
+        return pt, ok
+
+    def export_single(self, mode, pkR, ikmE, exporter_context, length, info=None, psk=None, psk_id=None, skS=None, pkS=None):
+        n = pkR.shape[0]
+        enc, out, ok = self._out(n, self.N), self._out(n, length), self._out(n)
+        nat.check(self.L.circl_hip_hpke_export_single_dev(*self._setup(mode, (pkR, ikmE, skS, pkS), info, psk, psk_id), *_rag_args(exporter_context), length,
+                                                          _chk(enc), _chk(out), _chk(ok), n, _stream()), "hpke_export_single_dev")
+        return enc, out, ok
+
+    def export_single_receiver(self, mode, skR, enc, exporter_context, length, info=None, psk=None, psk_id=None, pkS=None, pkR=None):
+        n = skR.shape[0]
+        out, ok = self._out(n, length), self._out(n)
+        nat.check(self.L.circl_hip_hpke_export_single_receiver_dev(*self._setup(mode, (skR, pkR, enc, pkS), info, psk, psk_id), *_rag_args(exporter_context),
+                                                                   length, _chk(out), _chk(ok), n, _stream()), "hpke_export_single_receiver_dev")
+        return out, ok

@@ -1003,3 +1003,132 @@ def hpke_dhkem_auth_decap(kem, skR, enc, pkS, pkR=None, device=0):
     ss, ok = np.empty((n, S), np.uint8), np.empty(n, np.uint8)
     nat.check(nat.lib().circl_hip_hpke_dhkem_auth_decap(kem, _p(skR), _po(pkR), _p(enc), _p(pkS), _p(ss), _p(ok), n, device), "hpke_dhkem_auth_decap")
     return ss, ok
+
+
+# ---- HPKE contexts: key schedule, ChaCha20-Poly1305 Seal / Open, Export (hpke/hpke.go, hpke/util.go, hpke/aead.go) ----
+HPKE_KDF_HKDF_SHA256, HPKE_KDF_HKDF_SHA512 = 1, 3
+HPKE_AEAD_CHACHA20POLY1305, HPKE_AEAD_EXPORT_ONLY = 3, 0xFFFF
+HPKE_MODE_BASE, HPKE_MODE_PSK, HPKE_MODE_AUTH, HPKE_MODE_AUTH_PSK = range(4)
+
+
+def hpke_context_size(kdf):
+    return nat.lib().circl_hip_hpke_context_size(kdf)
+
+
+def _rag(items, n):
+    """a list of byte strings (or None: every item empty) -> (blob, offsets) arrays or (None, None)"""
+    if items is None:
+        return None, None
+    if len(items) != n:
+        raise ValueError("hpke: a ragged input has %d items, the call %d" % (len(items), n))
+    return _blob(items)
+
+
+def _unrag(blob, off, extra=0):
+    return [blob[int(off[k]) + extra * k:int(off[k + 1]) + extra * (k + 1)].tobytes() for k in range(len(off) - 1)]
+
+
+class HpkeSuite:
+    """One HPKE suite (kem, kdf, aead) on host buffers.  Key rows are (n, N) arrays or byte strings; info, psk, psk_id, aad, plaintexts and
+    exporter contexts are lists of n byte strings (None: every item empty).  Failed items (a low-order point, the psk rule, a tag that does
+    not verify) have ok = 0 and zero outputs.  The caller owns the sequence numbers of a context."""
+
+    def __init__(self, kem, kdf, aead, device=0):
+        self.kem, self.kdf, self.aead, self.device = kem, kdf, aead, device
+        self.CS = hpke_context_size(kdf)
+        if kem not in HPKE_DHKEM_SIZES or not self.CS or aead not in (HPKE_AEAD_CHACHA20POLY1305, HPKE_AEAD_EXPORT_ONLY):
+            raise ValueError("HPKE suite (0x%x, 0x%x, 0x%x) is not served" % (kem, kdf, aead))
+        self.N = HPKE_DHKEM_SIZES[kem]["key"]
+        self.L = nat.lib()
+
+    def _setup_args(self, mode, rows, info, psk, psk_id):
+        _, _, n, rows = _hpke_rows(self.kem, *rows)
+        rag = [_rag(x, n) for x in (info, psk, psk_id)]
+        keep = (rows, rag)
+        args = [self.kem, self.kdf, self.aead, mode] + [_po(r) for r in rows] + [_po(a) for pair in rag for a in pair]
+        return n, args, keep
+
+    def setup_sender(self, mode, pkR, ikmE, info=None, psk=None, psk_id=None, skS=None, pkS=None):
+        """-> (enc (n, N), ctx (n, context size), ok (n,))"""
+        n, args, keep = self._setup_args(mode, (pkR, ikmE, skS, pkS), info, psk, psk_id)
+        enc, ctx, ok = np.empty((n, self.N), np.uint8), np.empty((n, self.CS), np.uint8), np.empty(n, np.uint8)
+        nat.check(self.L.circl_hip_hpke_setup_sender(*args, _p(enc), _p(ctx), _p(ok), n, self.device), "hpke_setup_sender")
+        return enc, ctx, ok
+
+    def setup_receiver(self, mode, skR, enc, info=None, psk=None, psk_id=None, pkS=None, pkR=None):
+        """-> (ctx, ok)"""
+        n, args, keep = self._setup_args(mode, (skR, pkR, enc, pkS), info, psk, psk_id)
+        ctx, ok = np.empty((n, self.CS), np.uint8), np.empty(n, np.uint8)
+        nat.check(self.L.circl_hip_hpke_setup_receiver(*args, _p(ctx), _p(ok), n, self.device), "hpke_setup_receiver")
+        return ctx, ok
+
+    @staticmethod
+    def _seq(seq, n):
+        return None if seq is None else np.ascontiguousarray(np.broadcast_to(np.asarray(seq, np.uint64), (n,)))
+
+    def seal(self, ctx, pts, aads=None, seq=None):
+        """-> the n ciphertexts (ct || tag) as byte strings"""
+        ctx = _u8(ctx, self.CS)
+        n = ctx.shape[0]
+        (pb, po), (ab, ao), sq = _rag(pts, n), _rag(aads, n), self._seq(seq, n)
+        ct = np.empty(int(po[n]) + 16 * n, np.uint8)
+        nat.check(self.L.circl_hip_hpke_seal(self.aead, _p(ctx), self.CS, _po(sq), _p(pb), _p(po), _po(ab), _po(ao), _p(ct), n, self.device), "hpke_seal")
+        return _unrag(ct, po, 16)
+
+    def open(self, ctx, cts, aads=None, seq=None):
+        """-> (the n plaintexts as byte strings, ok (n,)); a ciphertext shorter than a tag is refused here"""
+        ctx = _u8(ctx, self.CS)
+        n = ctx.shape[0]
+        if len(cts) != n or any(len(c) < 16 for c in cts):
+            raise ValueError("hpke_open: need %d ciphertexts of at least 16 bytes" % n)
+        cb, _ = _blob(cts)
+        _, po = _blob([bytes(len(c) - 16) for c in cts])
+        (ab, ao), sq = _rag(aads, n), self._seq(seq, n)
+        pt, ok = np.empty(int(po[n]) + 1, np.uint8), np.empty(n, np.uint8)
+        nat.check(self.L.circl_hip_hpke_open(self.aead, _p(ctx), self.CS, _po(sq), _p(cb), _p(po), _po(ab), _po(ao), _p(pt), _p(ok), n, self.device), "hpke_open")
+        return _unrag(pt, po), ok
+
+    def export(self, ctx, exporter_contexts, length):
+        """-> (n, length)"""
+        ctx = _u8(ctx, self.CS)
+        n = ctx.shape[0]
+        eb, eo = _rag(exporter_contexts, n)
+        out = np.empty((n, max(length, 0)), np.uint8)
+        nat.check(self.L.circl_hip_hpke_export(self.kdf, self.kem, self.aead, _p(ctx), self.CS, _po(eb), _po(eo), length, _p(out), n, self.device), "hpke_export")
+        return out
+
+    def seal_single(self, mode, pkR, ikmE, pts, aads=None, info=None, psk=None, psk_id=None, skS=None, pkS=None):
+        """RFC 9180 section 6 Seal<MODE> -> (enc, the n ciphertexts, ok)"""
+        n, args, keep = self._setup_args(mode, (pkR, ikmE, skS, pkS), info, psk, psk_id)
+        (pb, po), (ab, ao) = _rag(pts, n), _rag(aads, n)
+        enc, ct, ok = np.empty((n, self.N), np.uint8), np.empty(int(po[n]) + 16 * n, np.uint8), np.empty(n, np.uint8)
+        nat.check(self.L.circl_hip_hpke_seal_single(*args, _p(pb), _p(po), _po(ab), _po(ao), _p(enc), _p(ct), _p(ok), n, self.device), "hpke_seal_single")
+        return enc, _unrag(ct, po, 16), ok
+
+    def open_single(self, mode, skR, enc, cts, aads=None, info=None, psk=None, psk_id=None, pkS=None, pkR=None):
+        """RFC 9180 section 6 Open<MODE> -> (the n plaintexts, ok)"""
+        n, args, keep = self._setup_args(mode, (skR, pkR, enc, pkS), info, psk, psk_id)
+        if len(cts) != n or any(len(c) < 16 for c in cts):
+            raise ValueError("hpke_open_single: need %d ciphertexts of at least 16 bytes" % n)
+        cb, _ = _blob(cts)
+        _, po = _blob([bytes(len(c) - 16) for c in cts])
+        ab, ao = _rag(aads, n)
+        pt, ok = np.empty(int(po[n]) + 1, np.uint8), np.empty(n, np.uint8)
+        nat.check(self.L.circl_hip_hpke_open_single(*args, _p(cb), _p(po), _po(ab), _po(ao), _p(pt), _p(ok), n, self.device), "hpke_open_single")
+        return _unrag(pt, po), ok
+
+    def export_single(self, mode, pkR, ikmE, exporter_contexts, length, info=None, psk=None, psk_id=None, skS=None, pkS=None):
+        """RFC 9180 section 6 SendExport<MODE> -> (enc, exported (n, length), ok)"""
+        n, args, keep = self._setup_args(mode, (pkR, ikmE, skS, pkS), info, psk, psk_id)
+        eb, eo = _rag(exporter_contexts, n)
+        enc, out, ok = np.empty((n, self.N), np.uint8), np.empty((n, max(length, 0)), np.uint8), np.empty(n, np.uint8)
+        nat.check(self.L.circl_hip_hpke_export_single(*args, _po(eb), _po(eo), length, _p(enc), _p(out), _p(ok), n, self.device), "hpke_export_single")
+        return enc, out, ok
+
+    def export_single_receiver(self, mode, skR, enc, exporter_contexts, length, info=None, psk=None, psk_id=None, pkS=None, pkR=None):
+        """RFC 9180 section 6 ReceiveExport<MODE> -> (exported (n, length), ok)"""
+        n, args, keep = self._setup_args(mode, (skR, pkR, enc, pkS), info, psk, psk_id)
+        eb, eo = _rag(exporter_contexts, n)
+        out, ok = np.empty((n, max(length, 0)), np.uint8), np.empty(n, np.uint8)
+        nat.check(self.L.circl_hip_hpke_export_single_receiver(*args, _po(eb), _po(eo), length, _p(out), _p(ok), n, self.device), "hpke_export_single_receiver")
+        return out, ok

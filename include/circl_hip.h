@@ -822,6 +822,80 @@ int circl_hip_hpke_dhkem_auth_decap_dev(int kem, const uint8_t *d_skR, const uin
  * circl_hip_sha512. */
 int circl_hip_sha256(const uint8_t *msg_blob, const uint64_t *msg_off, uint8_t *out32, size_t n, int device);
 
+/* ---- HPKE contexts: key schedule, ChaCha20-Poly1305 Seal / Open, Export (hpke/hpke.go, hpke/util.go, hpke/aead.go; RFC 9180
+ * sections 5 and 6) ---------------------------------------------------------------------------------------------------------
+ * A suite is (kem, kdf, aead): kem = 0x20 / 0x21 as above, kdf = CIRCL_HIP_HPKE_KDF_HKDF_SHA256 (1) or _SHA512 (3), any KDF with
+ * any KEM, aead = CIRCL_HIP_HPKE_AEAD_CHACHA20POLY1305 (3) or CIRCL_HIP_HPKE_AEAD_EXPORT_ONLY (0xFFFF); mode = 0 base, 1 psk,
+ * 2 auth, 3 auth_psk.  Every other code point (HKDF-SHA384, the AES-GCM AEADs, the P-curve and hybrid KEMs) and mode > 3 are
+ * CIRCL_HIP_EPARAM, reported before a device is looked for, as is every breach of the rules below.
+ * One item per lane, one launch per call, no workspace.  A setup runs the DHKEM operation and the key schedule in one kernel; the
+ * shared secret stays in the lane.  Its result is a CONTEXT ROW of circl_hip_hpke_context_size(kdf) = 48 + Nh = 80 / 112 bytes
+ * (0 for an unknown kdf): key[32] || base_nonce[12] || 0[4] || exporter_secret[Nh]; key and base_nonce are zero for export-only.
+ * Context rows are secret and 4-byte aligned; Seal / Open / Export read them at ctx_stride bytes apart (a multiple of 4, at least
+ * 48 for Seal / Open and the context size for Export).
+ * Ragged arguments (info, psk, psk_id, aad, the exporter context, plaintexts) are a blob and n + 1 uint64_t offsets; a NULL blob
+ * means that every item's input is empty (its offsets are then not read).  Item i's plaintext is pt_off[i + 1] - pt_off[i] bytes
+ * at pt_blob[pt_off[i]]; its ciphertext (ct || tag) is 16 bytes longer at ct_blob[pt_off[i] + 16 i]: the one offset array
+ * describes both sides.  The ciphertext blob of Open is required.
+ *   setup_sender:   SetupBase/PSK/Auth/AuthPSK S with the ephemeral key derived from ikmE -> enc, ctx.  skS and pkS are NULL in
+ *                   modes 0 and 1 and both required in modes 2 and 3.
+ *   setup_receiver: SetupBase/PSK/Auth/AuthPSK R -> ctx.  pkR (the receiver's own public key) may be NULL; pkS is NULL in modes
+ *                   0 and 1 and required in modes 2 and 3.
+ *   psk / psk_id:   the blobs must be NULL in modes 0 and 2.  In modes 1 and 3 an item whose psk or psk_id is empty fails
+ *                   (verifyPSKInputs); there is no minimum psk length, as in the reference.
+ *   seal / open:    ChaCha20-Poly1305 under key and base_nonce XOR BE96(seq[i]) (seq == NULL: 0).  The caller owns the sequence
+ *                   numbers.  Open verifies the tag before it decrypts.  aead must be CHACHA20POLY1305.
+ *   export:         LabeledExpand(exporter_secret, "sec", exporter_context_i, L), 1 <= L <= 255 Nh, out = n rows of L bytes.
+ *   *_single:       RFC 9180 section 6: setup and a Seal / Open at sequence number 0, or an Export, in ONE kernel; neither the
+ *                   shared secret nor the context reaches memory.
+ * ok[i] = 0 and every output row of item i all zero where the KEM fails (a low-order point), the psk rule fails or, for Open,
+ * the tag does not verify.  ok may be NULL.  The host forms zero their staging; the _dev forms want 4-byte aligned rows and
+ * 8-byte aligned offset and seq arrays (CIRCL_HIP_EWORKSPACE otherwise).  n == 0 is CIRCL_HIP_OK. */
+#define CIRCL_HIP_HPKE_KDF_HKDF_SHA256 0x0001
+#define CIRCL_HIP_HPKE_KDF_HKDF_SHA512 0x0003
+#define CIRCL_HIP_HPKE_AEAD_CHACHA20POLY1305 0x0003
+#define CIRCL_HIP_HPKE_AEAD_EXPORT_ONLY 0xFFFF
+size_t circl_hip_hpke_context_size(int kdf);
+#define CIRCL_HIP_HPKE_SENDER_                                                                                                                       \
+    int kem, int kdf, int aead, int mode, const uint8_t *pkR, const uint8_t *ikmE, const uint8_t *skS, const uint8_t *pkS, const uint8_t *info_blob, \
+        const uint64_t *info_off, const uint8_t *psk_blob, const uint64_t *psk_off, const uint8_t *psk_id_blob, const uint64_t *psk_id_off
+#define CIRCL_HIP_HPKE_RECEIVER_                                                                                                                    \
+    int kem, int kdf, int aead, int mode, const uint8_t *skR, const uint8_t *pkR, const uint8_t *enc, const uint8_t *pkS, const uint8_t *info_blob, \
+        const uint64_t *info_off, const uint8_t *psk_blob, const uint64_t *psk_off, const uint8_t *psk_id_blob, const uint64_t *psk_id_off
+#define CIRCL_HIP_HPKE_SEAL_ const uint8_t *pt_blob, const uint64_t *pt_off, const uint8_t *aad_blob, const uint64_t *aad_off
+#define CIRCL_HIP_HPKE_OPEN_ const uint8_t *ct_blob, const uint64_t *pt_off, const uint8_t *aad_blob, const uint64_t *aad_off
+#define CIRCL_HIP_HPKE_ROWS_ const uint8_t *ctx, size_t ctx_stride
+int circl_hip_hpke_setup_sender(CIRCL_HIP_HPKE_SENDER_, uint8_t *enc, uint8_t *ctx, uint8_t *ok, size_t n, int device);
+int circl_hip_hpke_setup_receiver(CIRCL_HIP_HPKE_RECEIVER_, uint8_t *ctx, uint8_t *ok, size_t n, int device);
+int circl_hip_hpke_seal(int aead, CIRCL_HIP_HPKE_ROWS_, const uint64_t *seq, CIRCL_HIP_HPKE_SEAL_, uint8_t *ct_blob, size_t n, int device);
+int circl_hip_hpke_open(int aead, CIRCL_HIP_HPKE_ROWS_, const uint64_t *seq, CIRCL_HIP_HPKE_OPEN_, uint8_t *pt_blob, uint8_t *ok, size_t n, int device);
+int circl_hip_hpke_export(int kdf, int kem, int aead, CIRCL_HIP_HPKE_ROWS_, const uint8_t *exp_blob, const uint64_t *exp_off, size_t L, uint8_t *out, size_t n,
+                          int device);
+int circl_hip_hpke_seal_single(CIRCL_HIP_HPKE_SENDER_, CIRCL_HIP_HPKE_SEAL_, uint8_t *enc, uint8_t *ct_blob, uint8_t *ok, size_t n, int device);
+int circl_hip_hpke_open_single(CIRCL_HIP_HPKE_RECEIVER_, CIRCL_HIP_HPKE_OPEN_, uint8_t *pt_blob, uint8_t *ok, size_t n, int device);
+int circl_hip_hpke_export_single(CIRCL_HIP_HPKE_SENDER_, const uint8_t *exp_blob, const uint64_t *exp_off, size_t L, uint8_t *enc, uint8_t *out, uint8_t *ok,
+                                 size_t n, int device);
+int circl_hip_hpke_export_single_receiver(CIRCL_HIP_HPKE_RECEIVER_, const uint8_t *exp_blob, const uint64_t *exp_off, size_t L, uint8_t *out, uint8_t *ok,
+                                          size_t n, int device);
+/* the device-resident forms: the same arguments as device pointers, on the caller's stream */
+int circl_hip_hpke_setup_sender_dev(CIRCL_HIP_HPKE_SENDER_, uint8_t *enc, uint8_t *ctx, uint8_t *ok, size_t n, void *stream);
+int circl_hip_hpke_setup_receiver_dev(CIRCL_HIP_HPKE_RECEIVER_, uint8_t *ctx, uint8_t *ok, size_t n, void *stream);
+int circl_hip_hpke_seal_dev(int aead, CIRCL_HIP_HPKE_ROWS_, const uint64_t *seq, CIRCL_HIP_HPKE_SEAL_, uint8_t *ct_blob, size_t n, void *stream);
+int circl_hip_hpke_open_dev(int aead, CIRCL_HIP_HPKE_ROWS_, const uint64_t *seq, CIRCL_HIP_HPKE_OPEN_, uint8_t *pt_blob, uint8_t *ok, size_t n, void *stream);
+int circl_hip_hpke_export_dev(int kdf, int kem, int aead, CIRCL_HIP_HPKE_ROWS_, const uint8_t *exp_blob, const uint64_t *exp_off, size_t L, uint8_t *out,
+                              size_t n, void *stream);
+int circl_hip_hpke_seal_single_dev(CIRCL_HIP_HPKE_SENDER_, CIRCL_HIP_HPKE_SEAL_, uint8_t *enc, uint8_t *ct_blob, uint8_t *ok, size_t n, void *stream);
+int circl_hip_hpke_open_single_dev(CIRCL_HIP_HPKE_RECEIVER_, CIRCL_HIP_HPKE_OPEN_, uint8_t *pt_blob, uint8_t *ok, size_t n, void *stream);
+int circl_hip_hpke_export_single_dev(CIRCL_HIP_HPKE_SENDER_, const uint8_t *exp_blob, const uint64_t *exp_off, size_t L, uint8_t *enc, uint8_t *out,
+                                     uint8_t *ok, size_t n, void *stream);
+int circl_hip_hpke_export_single_receiver_dev(CIRCL_HIP_HPKE_RECEIVER_, const uint8_t *exp_blob, const uint64_t *exp_off, size_t L, uint8_t *out, uint8_t *ok,
+                                              size_t n, void *stream);
+#undef CIRCL_HIP_HPKE_SENDER_
+#undef CIRCL_HIP_HPKE_RECEIVER_
+#undef CIRCL_HIP_HPKE_SEAL_
+#undef CIRCL_HIP_HPKE_OPEN_
+#undef CIRCL_HIP_HPKE_ROWS_
+
 /* ---- kernel-level profiling (used by bench.py for the roofline figures) --------------------
  * While enabled, every *_dev call brackets each kernel it enqueues with HIP events recorded on
  * the caller's stream.  circl_hip_profile_read synchronises the pending events, returns the
@@ -852,7 +926,10 @@ int circl_hip_sha256(const uint8_t *msg_blob, const uint64_t *msg_off, uint8_t *
 #define CIRCL_HIP_KERNEL_HPKE_X25519 23    /* HPKE DHKEM(X25519, HKDF-SHA256), every operation */
 #define CIRCL_HIP_KERNEL_HPKE_X448 24      /* HPKE DHKEM(X448, HKDF-SHA512), every operation   */
 #define CIRCL_HIP_KERNEL_SHA256 25         /* batch SHA-256                            */
-#define CIRCL_HIP_KERNEL_COUNT 26
+#define CIRCL_HIP_KERNEL_HPKE_SETUP 26     /* HPKE setup (DHKEM + key schedule) and the single-shot forms */
+#define CIRCL_HIP_KERNEL_HPKE_AEAD 27      /* HPKE Seal / Open on context rows (ChaCha20-Poly1305) */
+#define CIRCL_HIP_KERNEL_HPKE_EXPORT 28    /* HPKE Export on context rows              */
+#define CIRCL_HIP_KERNEL_COUNT 29
 int circl_hip_profile_enable(int on);
 int circl_hip_profile_read(int kernel, double *total_ms, uint64_t *launches);
 /* The VALU issue rates this chip sustains, measured live (bench.py prices the kernels' VALU time against them instead of against
