@@ -3,11 +3,11 @@
 // DHKEMs of api_hpke.hip, HKDF-SHA256 / HKDF-SHA512 and ChaCha20-Poly1305 or the export-only AEAD.  No CPU compute path.
 //
 // Every entry point fills one Call (the pointers as the ABI passes them: device pointers for a _dev form, host pointers for a
-// host form) and goes through check() -- the argument contract, before any device is looked for -- and then launch() or host().
-// Host forms whose outputs are fixed rows (Setup, Export, single-shot Export) go through shard / run_pipeline like the DHKEM's.
-// The pipeline has no ragged OUTPUT, so the host forms that write a ciphertext or plaintext blob (Seal, Open and their single-shot
-// forms) stage a shard themselves: device buffers of exactly the shard's bytes, secret uploads and downloads through page-locked
-// memory that is zeroed, and every device buffer zeroed before it is freed.
+// host form) and goes through check() -- the argument contract, before any device is looked for -- and then launch() or host_pipeline().
+// Every host form goes through shard / run_pipeline like the DHKEM's.  Seal, Open and their single-shot forms read and write blobs
+// that share ONE offset array: the plaintext side is a blob / a ragged output over pt_off, the ciphertext side the same with a pad
+// of 16 bytes per item (host_common.h HBlob / HOut).  Plaintexts and the secret rows are wiped from the page-locked staging, and
+// the device staging of every chunk is zeroed whole.
 #include "host_compose.h"
 #include "hpke_kernels.h"
 
@@ -151,22 +151,25 @@ int dev_form(const Call &c, void *stream) {
     return launch(c, static_cast<hipStream_t>(stream));
 }
 
-// ---- host forms with fixed output rows: the pipeline --------------------------------------------------------------------------
-int host_rows(const Call &c, int device) {
+// ---- host forms: shard / run_pipeline -------------------------------------------------------------------------------------------
+int host_pipeline(const Call &c, int device) {
     const size_t N = key_bytes(c.kem), CS = c.setup() ? ctx_bytes(c.kdf) : c.ctx_stride;
     const PipeOpts opts = secret_opts(size_t(1) << 16);
+    // the offsets that size both AEAD blobs, as launch() reads them; without them every plaintext is empty and a ciphertext is a row of 16
+    const uint64_t *pt_off = c.does_aead() && c.in ? c.pt_off : nullptr;
+    const bool sealing = c.does_aead() && c.sender(), opening = c.does_aead() && !c.sender();  // plaintext in / plaintext out: the secret side
     return shard(c.n, device, [&](int dev, size_t lo, size_t cnt) {
         std::vector<HIn> ins;
         std::vector<HBlob> blobs;
         std::vector<HOut> outs;
-        auto in = [&](const uint8_t *p, size_t row, bool secret) {
+        auto in = [&](const void *p, size_t row, bool secret) {
             if (!p) return -1;
-            ins.push_back({p + lo * row, row, secret});
+            ins.push_back({static_cast<const uint8_t *>(p) + lo * row, row, secret});
             return (int)ins.size() - 1;
         };
-        auto blob = [&](const uint8_t *b, const uint64_t *off, bool secret) {
+        auto blob = [&](const uint8_t *b, const uint64_t *off, bool secret, size_t pad = 0) {
             if (!b) return -1;
-            blobs.push_back({b, off + lo, secret});
+            blobs.push_back({b + pad * lo, off + lo, secret, pad});
             return (int)blobs.size() - 1;
         };
         auto out = [&](uint8_t *p, size_t row, bool secret, bool want) {
@@ -174,12 +177,19 @@ int host_rows(const Call &c, int device) {
             outs.push_back({p ? p + lo * row : nullptr, row, secret});
             return (int)outs.size() - 1;
         };
+        auto ragged = [&](uint8_t *p, bool secret, size_t pad) {
+            outs.push_back({p + pad * lo, 0, secret, pt_off + lo, pad});
+            return (int)outs.size() - 1;
+        };
         const int i_pkR = in(c.pkR, N, false), i_ikmE = in(c.ikmE, N, true), i_skR = in(c.skR, N, true), i_skS = in(c.skS, N, true), i_pkS = in(c.pkS, N, false),
-                  i_enc = in(c.enc_in, N, false), i_ctx = in(c.ctx_in, CS, true);
+                  i_enc = in(c.enc_in, N, false), i_ctx = in(c.ctx_in, CS, true), i_seq = in(c.seq, 8, false),
+                  i_tags = in(opening && !pt_off ? c.in : nullptr, 16, false);
         const int b_info = blob(c.info, c.info_off, false), b_psk = blob(c.psk, c.psk_off, true), b_id = blob(c.psk_id, c.psk_id_off, false),
-                  b_exp = blob(c.exp, c.exp_off, false);
+                  b_exp = blob(c.exp, c.exp_off, false), b_aad = blob(c.aad, c.aad_off, false),
+                  b_in = blob(pt_off ? c.in : nullptr, pt_off, sealing, sealing ? 0 : 16);
         const int o_enc = out(c.enc_out, N, false, c.op == kSetupSender), o_ctx = out(c.ctx_out, CS, true, c.setup() && c.what == hp::kStoreContext),
-                  o_exp = out(c.exp_out, c.L, true, c.does_export()), o_ok = out(c.ok, 1, false, c.setup());
+                  o_exp = out(c.exp_out, c.L, true, c.does_export()), o_ok = out(c.ok, 1, false, c.setup() || c.op == kOpen),
+                  o_aead = !c.does_aead() ? -1 : pt_off ? ragged(c.out, opening, sealing ? 16 : 0) : out(c.out, sealing ? 16 : 0, false, true);
         return run_pipeline(dev, cnt, ins, blobs, outs, kNoWs, opts, [&](Chunk &k) {
             auto I = [&](int j) -> const uint8_t * { return j < 0 ? nullptr : k.in[j]; };
             auto B = [&](int j) -> const uint8_t * { return j < 0 ? nullptr : k.blob[j]; };
@@ -187,111 +197,21 @@ int host_rows(const Call &c, int device) {
             auto O = [&](int j) -> uint8_t * { return j < 0 ? nullptr : k.out[j]; };
             Call d = c;
             d.pkR = I(i_pkR); d.ikmE = I(i_ikmE); d.skR = I(i_skR); d.skS = I(i_skS); d.pkS = I(i_pkS); d.enc_in = I(i_enc); d.ctx_in = I(i_ctx);
+            d.seq = reinterpret_cast<const uint64_t *>(I(i_seq));
             d.info = B(b_info); d.info_off = F(b_info); d.psk = B(b_psk); d.psk_off = F(b_psk); d.psk_id = B(b_id); d.psk_id_off = F(b_id);
-            d.exp = B(b_exp); d.exp_off = F(b_exp);
-            d.enc_out = O(o_enc); d.ctx_out = O(o_ctx); d.exp_out = O(o_exp); d.ok = O(o_ok);
+            d.exp = B(b_exp); d.exp_off = F(b_exp); d.aad = B(b_aad); d.aad_off = F(b_aad);
+            d.in = pt_off ? B(b_in) : I(i_tags); d.pt_off = F(b_in);
+            d.enc_out = O(o_enc); d.ctx_out = O(o_ctx); d.exp_out = O(o_exp); d.ok = O(o_ok); d.out = O(o_aead);
             d.n = k.cnt;
             return launch(d, k.st);
         });
     }, kHeavyOneDeviceMax);
 }
 
-// ---- host forms that write a ragged blob: a shard staged by hand ---------------------------------------------------------------
-struct Stage {
-    hipStream_t st = nullptr;
-    std::vector<std::pair<uint8_t *, size_t>> bufs;
-    int rc = CIRCL_HIP_OK;
-    ~Stage() {
-        for (auto &b : bufs) {
-            (void)hipMemsetAsync(b.first, 0, b.second, st);
-        }
-        (void)hipStreamSynchronize(st);
-        for (auto &b : bufs) (void)hipFree(b.first);
-        (void)hipGetLastError();
-    }
-    uint8_t *alloc(size_t bytes) {
-        void *d = nullptr;
-        const size_t cap = bytes + 16;
-        if (rc == CIRCL_HIP_OK && hipMalloc(&d, cap) != hipSuccess) { (void)hipGetLastError(); rc = CIRCL_HIP_ENOMEM; }
-        if (!d) return nullptr;
-        bufs.push_back({static_cast<uint8_t *>(d), cap});
-        return static_cast<uint8_t *>(d);
-    }
-    // a device copy of h[0 .. bytes) (nullptr stays nullptr), through page-locked memory that is zeroed
-    const uint8_t *up(const void *h, size_t bytes) {
-        if (!h) return nullptr;
-        uint8_t *d = alloc(bytes);
-        if (d && rc == CIRCL_HIP_OK) rc = upload_secret(d, h, bytes, st);
-        return d;
-    }
-    uint8_t *zeros(size_t bytes) {
-        uint8_t *d = alloc(bytes);
-        if (d && rc == CIRCL_HIP_OK && hipMemsetAsync(d, 0, bytes + 16, st) != hipSuccess) rc = CIRCL_HIP_EHIP;
-        return d;
-    }
-    // h[0 .. bytes) = d[0 .. bytes), through page-locked memory that is zeroed
-    void down(void *h, const uint8_t *d, size_t bytes) {
-        if (!h || !bytes || rc != CIRCL_HIP_OK) return;
-        void *pin = nullptr;
-        if (pinned_alloc(&pin, bytes) != hipSuccess) { (void)hipGetLastError(); rc = CIRCL_HIP_ENOMEM; return; }
-        if (hipMemcpyAsync(pin, d, bytes, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) rc = CIRCL_HIP_EHIP;
-        else memcpy(h, pin, bytes);
-        volatile uint8_t *z = static_cast<volatile uint8_t *>(pin);
-        for (size_t i = 0; i < bytes; i++) z[i] = 0;
-        (void)pinned_free(pin);
-    }
-};
-
-int host_ragged(const Call &c, int device) {
-    const size_t N = key_bytes(c.kem);
-    return shard(c.n, device, [&](int dev, size_t lo, size_t cnt) {
-        if (dev < 0 || dev >= ndev()) return (int)CIRCL_HIP_ENODEV;
-        HIP_TRY(hipSetDevice(physical_device(dev)));
-        Stage s;
-        hipStream_t h2d = nullptr, d2h = nullptr;
-        TRY(pipeline_streams(dev, &h2d, &d2h, &s.st));
-        Call d = c;
-        const uint64_t *pt_off = (c.sender() && !c.in) ? nullptr : c.pt_off;  // a Seal without a plaintext blob: every plaintext is empty
-        auto rows = [&](const uint8_t *p, size_t row) { return p ? s.up(p + lo * row, cnt * row) : nullptr; };
-        // a blob's shard, rebased so that the caller's absolute offsets index it
-        auto blob = [&](const uint8_t *b, const uint64_t *off, const uint64_t *&d_off) -> const uint8_t * {
-            d_off = off ? reinterpret_cast<const uint64_t *>(s.up(off + lo, (cnt + 1) * 8)) : nullptr;
-            if (!b || !off) return nullptr;
-            const uint8_t *p = s.up(b + off[lo], (size_t)(off[lo + cnt] - off[lo]));
-            return p ? p - off[lo] : nullptr;
-        };
-        d.pkR = rows(c.pkR, N); d.ikmE = rows(c.ikmE, N); d.skR = rows(c.skR, N); d.skS = rows(c.skS, N); d.pkS = rows(c.pkS, N); d.enc_in = rows(c.enc_in, N);
-        d.ctx_in = rows(c.ctx_in, c.ctx_stride);
-        d.seq = reinterpret_cast<const uint64_t *>(rows(reinterpret_cast<const uint8_t *>(c.seq), 8));
-        d.info = blob(c.info, c.info_off, d.info_off);
-        d.psk = blob(c.psk, c.psk_off, d.psk_off);
-        d.psk_id = blob(c.psk_id, c.psk_id_off, d.psk_id_off);
-        d.aad = blob(c.aad, c.aad_off, d.aad_off);
-        // plaintext bytes [p0, p1) of this shard; its ciphertext is 16 cnt bytes longer and starts 16 lo bytes further on
-        const uint64_t p0 = pt_off ? pt_off[lo] : 0, p1 = pt_off ? pt_off[lo + cnt] : 0;
-        const size_t pt_bytes = (size_t)(p1 - p0), ct_bytes = pt_bytes + 16 * cnt, in_bytes = c.sender() ? pt_bytes : ct_bytes, out_bytes = c.sender() ? ct_bytes : pt_bytes;
-        d.pt_off = pt_off ? reinterpret_cast<const uint64_t *>(s.up(pt_off + lo, (cnt + 1) * 8)) : nullptr;
-        const uint8_t *h_in = c.in ? c.in + p0 + (c.sender() ? 0 : 16 * lo) : nullptr;
-        const uint8_t *d_in = h_in ? s.up(h_in, in_bytes) : nullptr;
-        d.in = d_in ? d_in - p0 : nullptr;
-        uint8_t *d_out = s.zeros(out_bytes);
-        d.out = d_out ? d_out - p0 : nullptr;
-        uint8_t *d_enc = c.op == kSetupSender ? s.zeros(cnt * N) : nullptr, *d_ok = c.op != kSeal ? s.zeros(cnt) : nullptr;
-        d.enc_out = d_enc; d.ok = d_ok;
-        d.n = cnt;
-        TRY(s.rc);
-        TRY(launch(d, s.st));
-        s.down(c.out + p0 + (c.sender() ? 16 * lo : 0), d_out, out_bytes);
-        if (d_enc) s.down(c.enc_out + lo * N, d_enc, cnt * N);
-        if (d_ok && c.ok) s.down(c.ok + lo, d_ok, cnt);
-        return s.rc;
-    }, kHeavyOneDeviceMax);
-}
-
 int host_form(const Call &c, int device) {
     if (int rc = check(c)) return rc;
     if (c.n == 0) return CIRCL_HIP_OK;
-    return c.does_aead() ? host_ragged(c, device) : host_rows(c, device);
+    return host_pipeline(c, device);
 }
 
 Call sender_call(int kem, int kdf, int aead, int mode, const uint8_t *pkR, const uint8_t *ikmE, const uint8_t *skS, const uint8_t *pkS, const uint8_t *info_blob,

@@ -859,9 +859,18 @@ void coalescer_stats(const Coalescer *co, uint64_t *calls, uint64_t *items, uint
 bool coalescer_is_async(const Coalescer *co) { return co && co->async; }
 int coalescer_eventfd(const Coalescer *co) { return co ? co->efd : -1; }
 
+// a batch is laid out in fixed rows and unpadded blobs: a ragged output or a padded blob is the pipeline's alone
+static bool ragged_or_padded(const std::vector<HBlob> &blobs, const std::vector<HOut> &outs) {
+    for (auto &b : blobs)
+        if (b.pad) return true;
+    for (auto &o : outs)
+        if (o.off) return true;
+    return false;
+}
+
 int coalescer_async_start(Coalescer *co, const std::vector<HIn> &ins, const std::vector<HBlob> &blobs, const std::vector<HOut> &outs,
                           const std::function<size_t(size_t)> &ws_bytes, const PipeOpts &opts, const std::function<int(Chunk &)> &launch, bool want_eventfd) {
-    if (!co || co->async || co->ready.load() != 0) return CIRCL_HIP_EPARAM;
+    if (!co || co->async || co->ready.load() != 0 || ragged_or_padded(blobs, outs)) return CIRCL_HIP_EPARAM;
     co->async = true;
     co->a_launch = launch;
     co->a_ws = ws_bytes;
@@ -937,7 +946,7 @@ int coalescer_wait(Coalescer *co, uint64_t seq, int64_t timeout_us) {
 int coalesce_run(Coalescer *co, size_t n, const std::vector<HIn> &ins, const std::vector<HBlob> &blobs, const std::vector<HOut> &outs,
                  const std::function<size_t(size_t)> &ws_bytes, const PipeOpts &opts, const std::function<int(Chunk &)> &launch) {
     if (n == 0) return CIRCL_HIP_OK;
-    if (!co || n > co->call_max || blobs.size() > (size_t)kMaxBlobs || outs.size() > (size_t)kMaxOuts) return kNotCoalesced;
+    if (!co || n > co->call_max || blobs.size() > (size_t)kMaxBlobs || outs.size() > (size_t)kMaxOuts || ragged_or_padded(blobs, outs)) return kNotCoalesced;
     if (co->async) {  // a blocking call through a table whose queue is asynchronous: submit, then wait for the ticket
         uint64_t seq = 0;
         const int rc = coalesce_submit(co, n, ins, blobs, outs, &seq, true);

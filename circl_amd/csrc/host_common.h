@@ -144,21 +144,38 @@ struct HIn {                 // fixed-size rows: item i is row i
     bool optional = false;   // coalesce_run / coalesce_submit: p == nullptr means rows of ZEROS (an absent key_idx / rnd); without it a
                              // NULL pointer is CIRCL_HIP_EPARAM there, as it is in run_pipeline
 };
-struct HBlob {               // ragged rows: item i is blob[off[i] .. off[i+1]); blob == nullptr: absent (kernels get nullptr)
+// Where items [lo, lo + cnt) of an array lie: rows of `row` bytes, or -- with offsets -- ragged rows that are `pad` bytes longer
+// than the offsets say (item i is [off[i] + pad i, off[i + 1] + pad (i + 1)): a ciphertext is its plaintext plus a tag).
+inline size_t span_start(const uint64_t *off, size_t row, size_t pad, size_t lo) { return off ? (size_t)off[lo] + pad * lo : row * lo; }
+inline size_t span_bytes(const uint64_t *off, size_t row, size_t pad, size_t lo, size_t cnt) {
+    return off ? (size_t)(off[lo + cnt] - off[lo]) + pad * cnt : row * cnt;
+}
+struct HBlob {               // ragged rows: item i is blob[off[i] + pad i .. off[i+1] + pad (i+1)); blob == nullptr: absent (kernels get nullptr)
     const uint8_t *blob;
     const uint64_t *off;
     bool secret = false;     // wipe the staging copy afterwards (run_pipeline; a coalesced batch takes no secret blob)
+    size_t pad = 0;          // run_pipeline only (a coalesced batch takes no padded blob)
+    const uint8_t *at(size_t lo) const { return blob + span_start(off, 0, pad, lo); }
+    size_t bytes(size_t lo, size_t cnt) const { return span_bytes(off, 0, pad, lo, cnt); }
 };
 struct HOut {
     uint8_t *p;              // nullptr: the device buffer exists but nothing is copied back
     size_t row;
     bool secret = false;
+    // With `off` (run_pipeline only): a RAGGED output, item i is p[off[i] + pad i .. off[i+1] + pad (i+1)) and `row` is not used.
+    // It stages no offsets of its own: the launch takes them from the input blob that shares them (Chunk::off).  Nothing zero-fills
+    // an output before the launch; a launch that may leave bytes of an item unwritten would hand the caller stale staging.
+    const uint64_t *off = nullptr;
+    size_t pad = 0;
+    uint8_t *at(size_t lo) const { return p + span_start(off, row, pad, lo); }
+    size_t bytes(size_t lo, size_t cnt) const { return span_bytes(off, row, pad, lo, cnt); }
 };
-struct Chunk {               // what `launch` gets: device pointers of one chunk
+struct Chunk {               // what `launch` gets: device pointers of one chunk [lo, lo + cnt)
     std::vector<uint8_t *> in;            // one per HIn
-    std::vector<const uint8_t *> blob;    // one per HBlob, REBASED so that the caller's absolute offsets index it (nullptr if absent)
+    std::vector<const uint8_t *> blob;    // one per HBlob, REBASED by off[lo] so that the caller's absolute offsets index it (nullptr if
+                                          // absent); the pad term is the launch's to add, with the CHUNK-LOCAL item index (+ pad * i)
     std::vector<const uint64_t *> off;    // one per HBlob: the chunk's cnt + 1 offsets (nullptr if absent)
-    std::vector<uint8_t *> out;           // one per HOut
+    std::vector<uint8_t *> out;           // one per HOut; a ragged one is rebased by off[lo] exactly as a blob is
     uint8_t *ws;
     size_t ws_bytes;
     size_t cnt;

@@ -572,9 +572,9 @@ int run_pipeline(int dev, size_t n, const std::vector<HIn> &ins, const std::vect
         constexpr size_t inline_bytes = size_t(4) << 20;
         size_t moved = 0;
         for (auto &in : ins) moved += in.row * (in.per_call ? 1 : n);
-        for (auto &o : outs) moved += o.row * n;
+        for (auto &o : outs) moved += o.bytes(0, n);
         for (auto &b : blobs)
-            if (b.blob) moved += (size_t)(b.off[n] - b.off[0]) + 8 * (n + 1);
+            if (b.blob) moved += b.bytes(0, n) + 8 * (n + 1);
         if (n <= chunk && moved <= inline_bytes) h2d = d2h = st;
         tiny = n <= chunk && moved <= zero_copy_bytes();
     }
@@ -621,7 +621,7 @@ int run_pipeline(int dev, size_t n, const std::vector<HIn> &ins, const std::vect
     // stage-out of a finished chunk = copy jobs (staging -> caller memory), then wipe jobs (secret staging areas)
     auto out_jobs = [&](InFlight &f, std::vector<CopyJob> &jobs) {
         for (size_t k = 0; k < outs.size(); k++)
-            if (outs[k].p && f.out[k].staged) jobs.push_back({outs[k].p + f.lo * outs[k].row, f.slot->hout + f.out[k].hofs, f.out[k].bytes});
+            if (outs[k].p && f.out[k].staged) jobs.push_back({outs[k].at(f.lo), f.slot->hout + f.out[k].hofs, f.out[k].bytes});
     };
     auto wipe_jobs = [&](InFlight &f, std::vector<CopyJob> &jobs) {
         // (a merged / zero-copy call brings EVERY output segment to the page-locked area, wanted by the caller or not)
@@ -667,7 +667,7 @@ int run_pipeline(int dev, size_t n, const std::vector<HIn> &ins, const std::vect
         }
         for (size_t k = 0; k < blobs.size(); k++) {
             if (!blobs[k].blob) continue;
-            sblob[k].bytes = (size_t)(blobs[k].off[lo + cnt] - blobs[k].off[lo]);
+            sblob[k].bytes = blobs[k].bytes(lo, cnt);
             sblob[k].dofs = take_d(sblob[k].bytes);
             sblob[k].staged = !blob_pinned[k];
             if (merge_in) { sblob[k].hofs = sblob[k].dofs; hin_ofs = dofs; }
@@ -681,7 +681,7 @@ int run_pipeline(int dev, size_t n, const std::vector<HIn> &ins, const std::vect
         const size_t in_end = dofs, out_begin = dofs;
         for (size_t k = 0; k < outs.size(); k++) {
             Seg &s = f.out[k];
-            s.bytes = outs[k].row * cnt;
+            s.bytes = outs[k].bytes(lo, cnt);
             s.dofs = take_d(s.bytes);
             s.staged = outs[k].p && !out_pinned[k];
             if (merge_out) { s.hofs = s.dofs - out_begin; hout_ofs = dofs - out_begin; }
@@ -724,7 +724,7 @@ int run_pipeline(int dev, size_t n, const std::vector<HIn> &ins, const std::vect
         for (size_t k = 0; k < blobs.size(); k++) {
             if (!blobs[k].blob) continue;
             if (sblob[k].staged && sblob[k].bytes) {
-                jobs.push_back({slot->hin + sblob[k].hofs, blobs[k].blob + blobs[k].off[lo], sblob[k].bytes});
+                jobs.push_back({slot->hin + sblob[k].hofs, blobs[k].at(lo), sblob[k].bytes});
                 if (blobs[k].secret) cur.secret_in.push_back(sblob[k]);
             }
             jobs.push_back({slot->hin + soff[k].hofs, blobs[k].off + lo, soff[k].bytes});
@@ -760,14 +760,17 @@ int run_pipeline(int dev, size_t n, const std::vector<HIn> &ins, const std::vect
             if (!blobs[k].blob) { c.blob.push_back(nullptr); c.off.push_back(nullptr); continue; }
             uint8_t *dp = zc ? slot->hin_dev + sblob[k].hofs : slot->d + sblob[k].dofs;
             if (sblob[k].bytes && !merge_in) {
-                const void *src = sblob[k].staged ? (const void *)(slot->hin + sblob[k].hofs) : (const void *)(blobs[k].blob + blobs[k].off[lo]);
+                const void *src = sblob[k].staged ? (const void *)(slot->hin + sblob[k].hofs) : (const void *)blobs[k].at(lo);
                 HIP_TRY(hipMemcpyAsync(dp, src, sblob[k].bytes, hipMemcpyHostToDevice, h2d));
             }
             if (!merge_in) HIP_TRY(hipMemcpyAsync(slot->d + soff[k].dofs, slot->hin + soff[k].hofs, soff[k].bytes, hipMemcpyHostToDevice, h2d));
             c.blob.push_back(dp - blobs[k].off[lo]);  // the kernels index it with the caller's absolute offsets
             c.off.push_back(reinterpret_cast<const uint64_t *>(zc ? slot->hin_dev + soff[k].hofs : slot->d + soff[k].dofs));
         }
-        for (size_t k = 0; k < outs.size(); k++) c.out.push_back(zc ? slot->hout_dev + cur.out[k].hofs : slot->d + cur.out[k].dofs);
+        for (size_t k = 0; k < outs.size(); k++) {
+            uint8_t *dp = zc ? slot->hout_dev + cur.out[k].hofs : slot->d + cur.out[k].dofs;
+            c.out.push_back(outs[k].off ? dp - outs[k].off[lo] : dp);  // (a ragged output is indexed like a blob)
+        }
         HIP_TRY(hipEventRecord(slot->ev_in, h2d));  // (the look-ahead bound of the next chunk waits on it)
         if (h2d != st) HIP_TRY(hipStreamWaitEvent(st, slot->ev_in, 0));
         rc = launch(c);
@@ -779,7 +782,7 @@ int run_pipeline(int dev, size_t n, const std::vector<HIn> &ins, const std::vect
         if (merge_out && out_end > out_begin && !zc) HIP_TRY(hipMemcpyAsync(slot->hout, slot->d + out_begin, out_end - out_begin, hipMemcpyDeviceToHost, d2h));
         for (size_t k = 0; k < outs.size(); k++) {
             if (!outs[k].p || !cur.out[k].bytes || merge_out) continue;
-            void *dst = cur.out[k].staged ? (void *)(slot->hout + cur.out[k].hofs) : (void *)(outs[k].p + lo * outs[k].row);
+            void *dst = cur.out[k].staged ? (void *)(slot->hout + cur.out[k].hofs) : (void *)outs[k].at(lo);
             HIP_TRY(hipMemcpyAsync(dst, slot->d + cur.out[k].dofs, cur.out[k].bytes, hipMemcpyDeviceToHost, d2h));
         }
         if (opts.wipe_device) {  // keys, seeds and intermediates do not outlive the chunk

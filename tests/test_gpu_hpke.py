@@ -216,7 +216,7 @@ def test_chunk_boundary_and_all_devices(api, tmp_path, kem, chunk, device):
     env = dict(os.environ)
     env.pop("CIRCL_HIP_HOST_CHUNK", None)
     if chunk:
-        env["CIRCL_HIP_HOST_CHUNK"] = chunk
+        env["CIRCL_HIP_HOST_CHUNK"] = str(int(chunk).bit_length() - 1)   # the knob is the chunk's log2 (8..24; anything else = the default)
     subprocess.run([sys.executable, os.path.join(ROOT, "tests", "hpke_worker.py"), hex(kem), str(device), src, dst], check=True, env=env, timeout=300)
     o = np.load(dst)
     for name in ("skR", "pkR", "skS", "pkS", "enc", "ss", "aenc", "ass"):     # the first 130 items against the checker

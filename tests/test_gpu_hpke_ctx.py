@@ -284,3 +284,95 @@ def test_export_lengths_and_contexts(api, dev, kdf):
         enc, out, ok = h.export_single(0, k["pkR"], k["ikmE"], exps, L)
         assert ok.all() and (out == want).all(), L
     assert (h.export(ctx, None, 16) == _rows([s.export(x, b"", 16) for x in ks])).all()
+
+
+# ---- the host pipeline's ragged outputs: chunk boundaries, shards and its three copy routes -------------------------------------
+N_PIPE = 300   # two chunks of 256 + 44 items at CIRCL_HIP_HOST_CHUNK = 8; three shards of 100 on three logical devices
+
+
+@pytest.fixture(scope="module")
+def pipe(api):
+    """keys of N_PIPE items (the first 130 from the DHKEM reference, the rest derived from random ikm) and this process's own run
+    with the default settings -- one chunk, the zero-copy route -- computed once and shared"""
+    import hpke_ctx_worker as hw
+    k = kem_reference(0x20)
+    rng = np.random.default_rng(300)
+    ikmR, ikmE = (np.concatenate([k[name], rng.integers(0, 256, (N_PIPE - N, 32), dtype=np.uint8)]) for name in ("ikmR", "ikmE"))
+    skR, pkR = api.hpke_dhkem_derive_keypair(0x20, ikmR)
+    assert (skR[:N] == k["skR"]).all() and (pkR[:N] == k["pkR"]).all()
+    keys = dict(pkR=pkR, skR=skR, ikmE=ikmE)
+    return keys, hw.run(api, pkR, skR, ikmE, 0)
+
+
+def _check_pipeline_run(o, keys, base):
+    """what every configuration asserts about one run of hpke_ctx_worker.run"""
+    import hpke_ctx_worker as hw
+    pts, aads, seq = hw.inputs(N_PIPE)
+    lens = [len(p) for p in pts]
+    assert lens[0] == lens[255] == lens[256] == lens[296] == 0 and lens[299] == 3
+    # byte for byte this process's run with the default settings
+    for name in ("ct", "pt", "ct1", "pt1", "ct_noaad", "fpt", "tags", "enc", "enc1", "ctx", "ctx_r", "ok_s", "ok_r", "ok", "ok1", "ok1r", "fok"):
+        assert o[name].shape == base[name].shape and (o[name] == base[name]).all(), name
+    assert all(o[name].all() for name in ("ok_s", "ok_r", "ok", "ok1", "ok1r"))
+    assert o["pt"].tobytes() == b"".join(pts) and o["pt1"].tobytes() == b"".join(pts)
+    assert o["ct"].size == sum(lens) + 16 * N_PIPE and o["tags"].size == 16 * N_PIPE
+    # the checker at both ends and on both sides of the chunk boundary
+    s = hc.Suite(*hw.SUITE)
+    ct, ct1, ct_noaad, tags = _split(o["ct"], lens, 16), _split(o["ct1"], lens, 16), _split(o["ct_noaad"], lens, 16), _split(o["tags"], [0] * N_PIPE, 16)
+    for i in (0, 255, 256, 299):
+        enc, ks = s.setup_sender(0, bytes(keys["pkR"][i]), bytes(keys["ikmE"][i]), b"")
+        assert bytes(o["enc"][i]) == enc and bytes(o["ctx"][i]) == s.context_row(ks), i
+        assert ct[i] == s.seal(ks, seq[i], pts[i], aads[i]) and ct_noaad[i] == s.seal(ks, seq[i], pts[i], b""), i
+        assert ct1[i] == s.seal(ks, 0, pts[i], aads[i]) and tags[i] == s.seal(ks, seq[i], b"", aads[i]), i
+    # forged tags: ok = 0 and zeros of the right length there, every other item intact
+    assert o["fok"].tolist() == [0 if i in hw.FORGED else 1 for i in range(N_PIPE)]
+    assert _split(o["fpt"], lens) == [bytes(lens[i]) if i in hw.FORGED else pts[i] for i in range(N_PIPE)]
+    # nothing was written before or behind an output blob
+    assert o["guards"].all() and o["guarded_same"].all()
+
+
+def test_pipeline_default_run_takes_the_checks(pipe):
+    keys, base = pipe
+    _check_pipeline_run(base, keys, base)
+
+
+@pytest.mark.parametrize("env,device", [({"CIRCL_HIP_HOST_CHUNK": "8"}, 0), ({"CIRCL_HIP_HOST_CHUNK": "8", "CIRCL_HIP_LOGICAL_DEVICES": "3"}, -1),
+                                        ({"CIRCL_HIP_ZEROCOPY_KB": "0"}, 0)], ids=["chunks", "chunks-in-shards", "merged-copy"])
+def test_pipeline_routes_agree(pipe, tmp_path, env, device):
+    import os
+    import subprocess
+    import sys
+    keys, base = pipe
+    src, dst = str(tmp_path / "in.npz"), str(tmp_path / "out.npz")
+    np.savez(src, **keys)
+    e = {k: v for k, v in os.environ.items() if k not in ("CIRCL_HIP_HOST_CHUNK", "CIRCL_HIP_ZEROCOPY_KB", "CIRCL_HIP_LOGICAL_DEVICES")}
+    e.update(env)
+    subprocess.run([sys.executable, os.path.join(os.path.dirname(os.path.abspath(__file__)), "hpke_ctx_worker.py"), str(device), src, dst], check=True, env=e,
+                   timeout=300)
+    _check_pipeline_run(np.load(dst), keys, base)
+
+
+def test_seal_into_page_locked_blobs(api):
+    """caller blobs from circl_hip_alloc_host are not staged: the pipeline copies straight from / to their ragged addresses"""
+    import ctypes as C
+    import hpke_ctx_worker as hw
+    n = 70
+    k, h = small_batch(0x20, n), api.HpkeSuite(*hw.SUITE)
+    pts, aads, seq = (x[:n] for x in hw.inputs(n))
+    _, ctx, ok = h.setup_sender(0, k["pkR"], k["ikmE"])
+    want = b"".join(h.seal(ctx, pts, aads, seq))
+    (pb, off), (ab, ao), sq = api._blob(pts), api._blob(aads), np.array(seq, np.uint64)
+    P, G = int(off[n]), hw.GUARD
+    L = h.L
+    mem_pt, mem_ct = L.circl_hip_alloc_host(P + 16), L.circl_hip_alloc_host(P + 16 * n + 2 * G)
+    assert mem_pt and mem_ct
+    try:
+        C.memmove(mem_pt, pb.ctypes.data, P)
+        C.memset(mem_ct, hw.FILL, P + 16 * n + 2 * G)
+        rc = L.circl_hip_hpke_seal(3, api._p(ctx), h.CS, api._p(sq), mem_pt, api._p(off), api._p(ab), api._p(ao), mem_ct + G, n, 0)
+        got = C.string_at(mem_ct, P + 16 * n + 2 * G)
+    finally:
+        L.circl_hip_free_host(mem_pt)
+        L.circl_hip_free_host(mem_ct)
+    assert rc == 0 and ok.all()
+    assert got[G:-G] == want and got[:G] == bytes([hw.FILL]) * G and got[-G:] == bytes([hw.FILL]) * G
