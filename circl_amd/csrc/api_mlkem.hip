@@ -6,6 +6,9 @@
 #include "keytable.h"
 #include "mlkem_kernels.h"
 
+#include <type_traits>
+#include <utility>
+
 using namespace circl::host;
 using circl::KeyIdx;
 
@@ -84,19 +87,39 @@ size_t kem_small_group(size_t n, bool reencrypt = false) {
 
 int kem_k(int param) { return param == 512 ? 2 : param == 768 ? 3 : param == 1024 ? 4 : 0; }
 
-// key-table cache behind the per-item workspace: A^T rows (whole groups of G entries), H(ek) and a status byte per entry
-template <int K> size_t kem_table_bytes(size_t nkeys) {
-    using Gm = circl::mlkem::Geom<K>;
-    const size_t padded = (nkeys + Gm::G - 1) / Gm::G * Gm::G;
-    return up256(padded * K * K * 512) + up256(nkeys * 32) + up256(nkeys);
-}
-size_t kem_table_bytes_any(int param, size_t nkeys) {
+// The one switch over the parameter set: f(std::integral_constant<int, K>{}) with K = 2 / 3 / 4, `unknown` for any other param.
+template <class F, class R = decltype(std::declval<F &>()(std::integral_constant<int, 2>{}))>
+R kem_with_k(int param, F &&f, R unknown = CIRCL_HIP_EPARAM) {
     switch (kem_k(param)) {
-    case 2: return kem_table_bytes<2>(nkeys);
-    case 3: return kem_table_bytes<3>(nkeys);
-    case 4: return kem_table_bytes<4>(nkeys);
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 3: return f(std::integral_constant<int, 3>{});
+    case 4: return f(std::integral_constant<int, 4>{});
     }
-    return 0;
+    return unknown;
+}
+// ... behind what every *_dev entry point asks first: is there a device at all
+template <class F> int kem_dev_call(int param, void *stream, F &&f) {
+    if (ndev() <= 0) return CIRCL_HIP_ENODEV;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    return kem_with_k(param, [&](auto k) -> int { return f(k, st); });
+}
+
+// A key table: A^T rows (whole groups of Geom<K>::G entries), then H(ek) per entry, then a status byte per entry.  The ONE place that knows
+// this layout: the cache behind the per-item workspace of the per-call key tables and the memory of the resident ones are both read
+// through this view.
+template <int K> struct KemTable {
+    uint8_t *base;
+    size_t nkeys, padded;
+    KemTable(void *b, size_t nk)
+        : base(static_cast<uint8_t *>(b)), nkeys(nk), padded((nk + circl::mlkem::Geom<K>::G - 1) / circl::mlkem::Geom<K>::G * circl::mlkem::Geom<K>::G) {}
+    size_t rows_bytes() const { return up256(padded * K * K * 512); }
+    int16_t *rows() const { return reinterpret_cast<int16_t *>(base); }
+    uint8_t *h() const { return base + rows_bytes(); }
+    uint8_t *status() const { return h() + up256(nkeys * 32); }
+    size_t bytes() const { return rows_bytes() + up256(nkeys * 32) + up256(nkeys); }  // (asked of a view without memory, too)
+};
+size_t kem_table_bytes_any(int param, size_t nkeys) {
+    return kem_with_k(param, [&](auto k) { return KemTable<k.value>(nullptr, nkeys).bytes(); }, size_t(0));
 }
 
 struct KemWs {  // the carving of a ML-KEM workspace every launch sequence below uses
@@ -115,6 +138,29 @@ struct KemWs {  // the carving of a ML-KEM workspace every launch sequence below
 };
 
 // ---- device-resident ML-KEM ---------------------------------------------------------------
+
+// The ONE launch of the encrypt kernel (K-PKE.Encrypt of an encapsulation, the re-encryption of a decapsulation).  What varies between
+// the routes: where the keys are (`ek`: the encapsulation key -- of a private key, dk + 384 K -- rows `stride` apart, 0 = one key for
+// all), m and the coins r, the outputs, a key-table batch's index vector and expanded rows, and the re-encryption's K-bar / rejection
+// secret.  `want` = items per workgroup (the caller's choice); the key mode decides the LDS carving.
+struct KemEncArgs {
+    const uint8_t *ek = nullptr;
+    size_t stride = 0;
+    const uint8_t *m = nullptr, *r = nullptr;
+    uint8_t *ct = nullptr, *ss = nullptr, *status = nullptr;
+    KeyIdx kx{};
+    const int16_t *key_rows = nullptr;
+    const uint8_t *kbar = nullptr, *ssrej = nullptr;
+};
+template <int K, int MODE, int KM> void kem_encrypt(const KemWs &w, size_t n, size_t want, const KemEncArgs &a, hipStream_t st) {
+    using Gm = circl::mlkem::Geom<K>;
+    constexpr int lds = KM == circl::mlkem::KM_ITEM ? Gm::LDS_SCRATCH_TOTAL : Gm::LDS_SHARED_TOTAL;
+    ProfScope ps(CIRCL_HIP_KERNEL_MLKEM_ENCRYPT, st);
+    auto kern = circl::mlkem::mlkem_encrypt_kernel<K, MODE, 0, true, KM>;
+    const unsigned eb = std::min<unsigned>((unsigned)((n + want - 1) / want), resident_blocks(kern, lds));
+    hipLaunchKernelGGL(kern, dim3(eb), dim3(64), lds, st, a.ek, a.stride, a.m, a.r, a.ct, a.ss, a.status, a.kbar, a.ssrej, w.scratch, w.work, n, a.kx,
+                       a.key_rows);
+}
 
 // R3 = round-3 Kyber (kem/kyber/kyber768/kyber.go:105-154): m = H(seed), lenient key decoding, K = KDF(K' || H(ct)).
 template <int K, bool R3 = false>
@@ -144,17 +190,12 @@ int encaps_dev_impl(const uint8_t *ek, const uint8_t *m, uint8_t *ct, uint8_t *s
         const int coop = kem_hash_form(n, kem_coop_batch());
         const unsigned nb_expand = (unsigned)((n + Gm::G - 1) / Gm::G), nb_hash = kem_hash_blocks(n, coop);
         static_assert(Gm::LDS_FIFO >= 108 * 8, "the cooperative hash's exchange area fits the FIFO area");
-        const size_t want = kem_small_group(n);
         HIP_TRY(hipMemsetAsync(w.work, 0, 256, st));
         {
             ProfScope ps(CIRCL_HIP_KERNEL_MLKEM_HASH, st);
             hipLaunchKernelGGL(mlkem_small_pre_kernel<K>, dim3(nb_hash + nb_expand), dim3(64), Gm::LDS_FIFO, st, ek, m, ss, r_ws, key_rows, n, nb_hash, coop);
         }
-        auto kern = mlkem_encrypt_kernel<K, ENCAPS, 0, true, KM_KEYED>;
-        const unsigned eb = std::min<unsigned>((unsigned)((n + want - 1) / want), resident_blocks(kern, Gm::LDS_SHARED_TOTAL));
-        ProfScope ps(CIRCL_HIP_KERNEL_MLKEM_ENCRYPT, st);
-        hipLaunchKernelGGL(kern, dim3(eb), dim3(64), Gm::LDS_SHARED_TOTAL, st, ek, (size_t)Gm::EK, m, (const uint8_t *)r_ws, ct, ss, status,
-                           (const uint8_t *)nullptr, (const uint8_t *)nullptr, w.scratch, w.work, n, KeyIdx{}, (const int16_t *)key_rows);
+        kem_encrypt<K, ENCAPS, KM_KEYED>(w, n, kem_small_group(n), {ek, (size_t)Gm::EK, m, r_ws, ct, ss, status, KeyIdx{}, key_rows}, st);
         HIP_TRY(hipGetLastError());
         return CIRCL_HIP_OK;
     }
@@ -164,14 +205,7 @@ int encaps_dev_impl(const uint8_t *ek, const uint8_t *m, uint8_t *ct, uint8_t *s
         if (R3) hipLaunchKernelGGL(kyber_r3_hash_kernel<K>, dim3(hb), dim3(256), 0, st, ek, m, ss, r_ws, m_ws, n);
         else hipLaunchKernelGGL(mlkem_hash_kernel<K>, dim3(hb), dim3(256), 0, st, ek, m, ss, r_ws, n);
     }
-    {
-        auto kern = mlkem_encrypt_kernel<K, R3 ? ENCAPS_LENIENT : ENCAPS, 0, true>;
-        const unsigned eb = std::min<unsigned>((unsigned)((n + Gm::G - 1) / Gm::G), resident_blocks(kern, Gm::LDS_SCRATCH_TOTAL));
-        ProfScope ps(CIRCL_HIP_KERNEL_MLKEM_ENCRYPT, st);
-        hipLaunchKernelGGL(kern, dim3(eb), dim3(64), Gm::LDS_SCRATCH_TOTAL, st, ek, (size_t)Gm::EK, R3 ? (const uint8_t *)m_ws : m, (const uint8_t *)r_ws,
-                           ct, ss, status, (const uint8_t *)nullptr, (const uint8_t *)nullptr, w.scratch, w.work, n, KeyIdx{},
-                           (const int16_t *)nullptr);
-    }
+    kem_encrypt<K, R3 ? ENCAPS_LENIENT : ENCAPS, KM_ITEM>(w, n, Gm::G, {ek, (size_t)Gm::EK, R3 ? (const uint8_t *)m_ws : m, r_ws, ct, ss, status}, st);
     if (R3) {
         ProfScope ps(CIRCL_HIP_KERNEL_MLKEM_HASH, st);
         hipLaunchKernelGGL(kyber_r3_finish_kernel<K>, dim3(hb), dim3(256), 0, st, (const uint8_t *)ct, ss, n);
@@ -208,12 +242,7 @@ int encaps_shared_dev_impl(const uint8_t *ek, const uint8_t *m, uint8_t *ct, uin
             ProfScope ps(CIRCL_HIP_KERNEL_MLKEM_HASH, st);
             hipLaunchKernelGGL(mlkem_small_shared_pre_kernel<K>, dim3(1 + (unsigned)((n + 31) / 32)), dim3(64), Gm::LDS_FIFO, st, ek, m, ss, r_ws, key_rows, n);
         }
-        auto kern = mlkem_encrypt_kernel<K, ENCAPS, 0, true, KM_KEYED>;
-        const size_t want = kem_small_group(n);
-        const unsigned eb = std::min<unsigned>((unsigned)((n + want - 1) / want), resident_blocks(kern, Gm::LDS_SHARED_TOTAL));
-        ProfScope ps(CIRCL_HIP_KERNEL_MLKEM_ENCRYPT, st);
-        hipLaunchKernelGGL(kern, dim3(eb), dim3(64), Gm::LDS_SHARED_TOTAL, st, ek, (size_t)0, m, (const uint8_t *)r_ws, ct, ss, status,
-                           (const uint8_t *)nullptr, (const uint8_t *)nullptr, w.scratch, w.work, n, KeyIdx{}, (const int16_t *)key_rows);
+        kem_encrypt<K, ENCAPS, KM_KEYED>(w, n, kem_small_group(n), {ek, 0, m, r_ws, ct, ss, status, KeyIdx{}, key_rows}, st);
         HIP_TRY(hipGetLastError());
         return CIRCL_HIP_OK;
     }
@@ -223,55 +252,7 @@ int encaps_shared_dev_impl(const uint8_t *ek, const uint8_t *m, uint8_t *ct, uin
         hipLaunchKernelGGL(mlkem_g_shared_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const uint8_t *)h_ws, m, ss,
                            r_ws, n, KeyIdx{});
     }
-    {
-        auto kern = mlkem_encrypt_kernel<K, ENCAPS, 0, true, KM_SHARED>;
-        const unsigned eb = std::min<unsigned>((unsigned)((n + Gm::GS - 1) / Gm::GS), resident_blocks(kern, Gm::LDS_SHARED_TOTAL));
-        ProfScope ps(CIRCL_HIP_KERNEL_MLKEM_ENCRYPT, st);
-        hipLaunchKernelGGL(kern, dim3(eb), dim3(64), Gm::LDS_SHARED_TOTAL, st, ek, (size_t)0, m, (const uint8_t *)r_ws, ct, ss, status,
-                           (const uint8_t *)nullptr, (const uint8_t *)nullptr, w.scratch, w.work, n, KeyIdx{},
-                           (const int16_t *)nullptr);
-    }
-    HIP_TRY(hipGetLastError());
-    return CIRCL_HIP_OK;
-}
-
-// Key-table encapsulation: item i encapsulates to entry key_idx[i] of ek_table (nkeys rows).  Per TABLE ENTRY: H(ek) and
-// A^T (the reference's parsed-key cache, kyber.go:39-43 / cpapke.go:19-25); per ITEM: G, the 2K+1 PRF streams and the ring
-// phase (8 permutations for ML-KEM-768).  The workspace is kem_ws_bytes(n) followed by kem_table_bytes<K>(nkeys).
-template <int K>
-int encaps_keyed_dev_impl(const uint8_t *ek_table, size_t nkeys, const uint32_t *key_idx, const uint8_t *m, uint8_t *ct, uint8_t *ss,
-                          uint8_t *status, size_t n, void *ws, size_t ws_bytes, hipStream_t st) {
-    using Gm = circl::mlkem::Geom<K>;
-    using namespace circl::mlkem;
-    if (n == 0) return CIRCL_HIP_OK;
-    if (nkeys == 0) return CIRCL_HIP_EPARAM;
-    if (ws_bytes < kem_ws_bytes(n) + kem_table_bytes<K>(nkeys) || !aligned<16>(ws, ek_table, m, ct, ss) || !aligned<4>(key_idx))
-        return CIRCL_HIP_EWORKSPACE;
-    KemWs w(ws, n);
-    const KeyIdx kx{key_idx, (uint32_t)(nkeys - 1)};  // a device index vector is bounded to the table on every read
-    uint8_t *r_ws = w.slot0;
-    const size_t padded = (nkeys + Gm::G - 1) / Gm::G * Gm::G;
-    int16_t *key_rows = reinterpret_cast<int16_t *>(static_cast<uint8_t *>(ws) + kem_ws_bytes(n));
-    uint8_t *key_h = reinterpret_cast<uint8_t *>(key_rows) + up256(padded * K * K * 512);
-    HIP_TRY(hipMemsetAsync(w.work, 0, 256, st));
-    {
-        ProfScope ps(CIRCL_HIP_KERNEL_MLKEM_KEYTABLE, st);
-        hipLaunchKernelGGL(mlkem_hek_table_kernel<K>, dim3((unsigned)((nkeys + 255) / 256)), dim3(256), 0, st, ek_table, (size_t)Gm::EK, (size_t)0,
-                           key_h, (uint8_t *)nullptr, 0, nkeys);
-        hipLaunchKernelGGL(mlkem_expand_keys_kernel<K>, dim3((unsigned)(padded / Gm::G)), dim3(64), Gm::LDS_FIFO, st, ek_table, (size_t)Gm::EK,
-                           (size_t)(384 * K), key_rows, nkeys);
-    }
-    {
-        ProfScope ps(CIRCL_HIP_KERNEL_MLKEM_HASH, st);
-        hipLaunchKernelGGL(mlkem_g_shared_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const uint8_t *)key_h, m, ss, r_ws, n, kx);
-    }
-    {
-        auto kern = mlkem_encrypt_kernel<K, ENCAPS, 0, true, KM_KEYED>;
-        const unsigned eb = std::min<unsigned>((unsigned)((n + Gm::GS - 1) / Gm::GS), resident_blocks(kern, Gm::LDS_SHARED_TOTAL));
-        ProfScope ps(CIRCL_HIP_KERNEL_MLKEM_ENCRYPT, st);
-        hipLaunchKernelGGL(kern, dim3(eb), dim3(64), Gm::LDS_SHARED_TOTAL, st, ek_table, (size_t)Gm::EK, m, (const uint8_t *)r_ws, ct, ss, status,
-                           (const uint8_t *)nullptr, (const uint8_t *)nullptr, w.scratch, w.work, n, kx, (const int16_t *)key_rows);
-    }
+    kem_encrypt<K, ENCAPS, KM_SHARED>(w, n, Gm::GS, {ek, 0, m, r_ws, ct, ss, status}, st);
     HIP_TRY(hipGetLastError());
     return CIRCL_HIP_OK;
 }
@@ -302,22 +283,16 @@ int decaps_shared_dev_impl(const uint8_t *dk, const uint8_t *ct, uint8_t *ss, ui
         // shared-key re-encryption with as few items per workgroup as the idle SIMDs allow
         const int coop = kem_hash_form(n, kem_coop_batch());
         const unsigned nb_j = kem_hash_blocks(n, coop);
+        int16_t *key_rows = reinterpret_cast<int16_t *>(static_cast<uint8_t *>(ws) + kem_small_table_ofs(n));
         {
             ProfScope ps(CIRCL_HIP_KERNEL_MLKEM_HASH, st);
             // (+ ONE expansion workgroup behind the n decrypting ones: the key's A^T into the row cache, G copies -- stride 0)
-            int16_t *key_rows = reinterpret_cast<int16_t *>(static_cast<uint8_t *>(ws) + kem_small_table_ofs(n));
             hipLaunchKernelGGL(mlkem_small_decaps_pre_kernel<K>, dim3(nb_j + 1 + (unsigned)n + 1), dim3(64), Gm::LDS_FIFO, st, dk, (size_t)0, ct, mprime, kbar, r_ws,
                                ssrej, status, key_status, key_rows, n, nb_j, 1u, coop);
             hipLaunchKernelGGL(mlkem_fill_status_kernel, dim3(hb), dim3(256), 0, st, status, (const uint8_t *)key_status, n);
         }
-        const int16_t *key_rows = reinterpret_cast<const int16_t *>(static_cast<uint8_t *>(ws) + kem_small_table_ofs(n));
-        auto kern = mlkem_encrypt_kernel<K, REENCRYPT, 0, true, KM_KEYED>;
-        const size_t want = kem_small_group(n, true);
-        const unsigned eb = std::min<unsigned>((unsigned)((n + want - 1) / want), resident_blocks(kern, Gm::LDS_SHARED_TOTAL));
-        ProfScope ps(CIRCL_HIP_KERNEL_MLKEM_ENCRYPT, st);
-        hipLaunchKernelGGL(kern, dim3(eb), dim3(64), Gm::LDS_SHARED_TOTAL, st, dk + 384 * K, (size_t)0, (const uint8_t *)mprime, (const uint8_t *)r_ws,
-                           const_cast<uint8_t *>(ct), ss, status, (const uint8_t *)kbar, (const uint8_t *)ssrej, w.scratch, w.work, n,
-                           KeyIdx{}, key_rows);
+        kem_encrypt<K, REENCRYPT, KM_KEYED>(w, n, kem_small_group(n, true),
+                                            {dk + 384 * K, 0, mprime, r_ws, const_cast<uint8_t *>(ct), ss, status, KeyIdx{}, key_rows, kbar, ssrej}, st);
         HIP_TRY(hipGetLastError());
         return CIRCL_HIP_OK;
     }
@@ -331,63 +306,8 @@ int decaps_shared_dev_impl(const uint8_t *dk, const uint8_t *ct, uint8_t *ss, ui
         hipLaunchKernelGGL(mlkem_decaps_hash_kernel<K>, dim3(hb), dim3(256), 0, st, dk, (size_t)0, ct, (const uint8_t *)mprime, kbar,
                            r_ws, ssrej, status, n, (const uint8_t *)key_status, KeyIdx{});
     }
-    {
-        ProfScope ps(CIRCL_HIP_KERNEL_MLKEM_ENCRYPT, st);
-        auto kern = mlkem_encrypt_kernel<K, REENCRYPT, 0, true, KM_SHARED>;
-        const unsigned eb = std::min<unsigned>((unsigned)((n + Gm::GS - 1) / Gm::GS), resident_blocks(kern, Gm::LDS_SHARED_TOTAL));
-        hipLaunchKernelGGL(kern, dim3(eb), dim3(64), Gm::LDS_SHARED_TOTAL, st, dk + 384 * K, (size_t)0, (const uint8_t *)mprime, (const uint8_t *)r_ws,
-                           const_cast<uint8_t *>(ct), ss, status, (const uint8_t *)kbar, (const uint8_t *)ssrej, w.scratch, w.work, n,
-                           KeyIdx{}, (const int16_t *)nullptr);
-    }
-    HIP_TRY(hipGetLastError());
-    return CIRCL_HIP_OK;
-}
-
-// Key-table decapsulation: item i is decapsulated with entry key_idx[i] of dk_table.  Per table entry: the private key's
-// hash check (kyber.go:219-228) and A^T; per item the 17 permutations of the shared-key path.
-template <int K>
-int decaps_keyed_dev_impl(const uint8_t *dk_table, size_t nkeys, const uint32_t *key_idx, const uint8_t *ct, uint8_t *ss, uint8_t *status,
-                          size_t n, void *ws, size_t ws_bytes, hipStream_t st) {
-    using Gm = circl::mlkem::Geom<K>;
-    using namespace circl::mlkem;
-    if (n == 0) return CIRCL_HIP_OK;
-    if (nkeys == 0) return CIRCL_HIP_EPARAM;
-    if (ws_bytes < kem_ws_bytes(n) + kem_table_bytes<K>(nkeys) || !aligned<16>(ws, dk_table, ct, ss) ||
-        !aligned<4>(key_idx))
-        return CIRCL_HIP_EWORKSPACE;
-    KemWs w(ws, n);
-    const KeyIdx kx{key_idx, (uint32_t)(nkeys - 1)};
-    uint8_t *mprime = w.slot0, *r_ws = w.slot1, *kbar = w.slot2, *ssrej = w.slot3;
-    const size_t padded = (nkeys + Gm::G - 1) / Gm::G * Gm::G;
-    int16_t *key_rows = reinterpret_cast<int16_t *>(static_cast<uint8_t *>(ws) + kem_ws_bytes(n));
-    uint8_t *key_h = reinterpret_cast<uint8_t *>(key_rows) + up256(padded * K * K * 512);
-    uint8_t *key_status = key_h + up256(nkeys * 32);
-    HIP_TRY(hipMemsetAsync(w.work, 0, 256, st));
-    const unsigned hb = (unsigned)((n + 255) / 256);
-    {
-        ProfScope ps(CIRCL_HIP_KERNEL_MLKEM_KEYTABLE, st);
-        hipLaunchKernelGGL(mlkem_hek_table_kernel<K>, dim3((unsigned)((nkeys + 255) / 256)), dim3(256), 0, st, dk_table, (size_t)Gm::DK,
-                           (size_t)(384 * K), key_h, key_status, 1, nkeys);
-        hipLaunchKernelGGL(mlkem_expand_keys_kernel<K>, dim3((unsigned)(padded / Gm::G)), dim3(64), Gm::LDS_FIFO, st, dk_table, (size_t)Gm::DK,
-                           (size_t)(768 * K), key_rows, nkeys);
-    }
-    {
-        ProfScope ps(CIRCL_HIP_KERNEL_MLKEM_DECRYPT, st);
-        hipLaunchKernelGGL(mlkem_decrypt_kernel<K>, dim3((unsigned)n), dim3(64), 0, st, dk_table, (size_t)Gm::DK, ct, mprime, n, kx);
-    }
-    {
-        ProfScope ps(CIRCL_HIP_KERNEL_MLKEM_HASH, st);
-        hipLaunchKernelGGL(mlkem_decaps_hash_kernel<K>, dim3(hb), dim3(256), 0, st, dk_table, (size_t)Gm::DK, ct, (const uint8_t *)mprime, kbar,
-                           r_ws, ssrej, status, n, (const uint8_t *)key_status, kx);
-    }
-    {
-        ProfScope ps(CIRCL_HIP_KERNEL_MLKEM_ENCRYPT, st);
-        auto kern = mlkem_encrypt_kernel<K, REENCRYPT, 0, true, KM_KEYED>;
-        const unsigned eb = std::min<unsigned>((unsigned)((n + Gm::GS - 1) / Gm::GS), resident_blocks(kern, Gm::LDS_SHARED_TOTAL));
-        hipLaunchKernelGGL(kern, dim3(eb), dim3(64), Gm::LDS_SHARED_TOTAL, st, dk_table + 384 * K, (size_t)Gm::DK, (const uint8_t *)mprime,
-                           (const uint8_t *)r_ws, const_cast<uint8_t *>(ct), ss, status, (const uint8_t *)kbar, (const uint8_t *)ssrej, w.scratch,
-                           w.work, n, kx, (const int16_t *)key_rows);
-    }
+    kem_encrypt<K, REENCRYPT, KM_SHARED>(w, n, Gm::GS, {dk + 384 * K, 0, mprime, r_ws, const_cast<uint8_t *>(ct), ss, status, KeyIdx{}, nullptr, kbar, ssrej},
+                                         st);
     HIP_TRY(hipGetLastError());
     return CIRCL_HIP_OK;
 }
@@ -424,13 +344,8 @@ int decaps_dev_impl(const uint8_t *dk, const uint8_t *ct, uint8_t *ss, uint8_t *
             hipLaunchKernelGGL(mlkem_small_decaps_pre_kernel<K>, dim3(2 * nb_hash + (unsigned)n + nb_expand), dim3(64), Gm::LDS_FIFO, st, dk, (size_t)Gm::DK, ct,
                                mprime, kbar, r_ws, ssrej, status, (uint8_t *)nullptr, key_rows, n, nb_hash, nb_hash, coop);
         }
-        auto kern = mlkem_encrypt_kernel<K, REENCRYPT, 0, true, KM_KEYED>;
-        const size_t want = kem_small_group(n, true);
-        const unsigned eb = std::min<unsigned>((unsigned)((n + want - 1) / want), resident_blocks(kern, Gm::LDS_SHARED_TOTAL));
-        ProfScope ps(CIRCL_HIP_KERNEL_MLKEM_ENCRYPT, st);
-        hipLaunchKernelGGL(kern, dim3(eb), dim3(64), Gm::LDS_SHARED_TOTAL, st, dk + 384 * K, (size_t)Gm::DK, (const uint8_t *)mprime, (const uint8_t *)r_ws,
-                           const_cast<uint8_t *>(ct), ss, status, (const uint8_t *)kbar, (const uint8_t *)ssrej, w.scratch, w.work, n,
-                           KeyIdx{}, (const int16_t *)key_rows);
+        kem_encrypt<K, REENCRYPT, KM_KEYED>(w, n, kem_small_group(n, true),
+                                            {dk + 384 * K, (size_t)Gm::DK, mprime, r_ws, const_cast<uint8_t *>(ct), ss, status, KeyIdx{}, key_rows, kbar, ssrej}, st);
         HIP_TRY(hipGetLastError());
         return CIRCL_HIP_OK;
     }
@@ -447,14 +362,8 @@ int decaps_dev_impl(const uint8_t *dk, const uint8_t *ct, uint8_t *ss, uint8_t *
             hipLaunchKernelGGL(mlkem_decaps_hash_kernel<K>, dim3(hb), dim3(256), 0, st, dk, (size_t)Gm::DK, ct, (const uint8_t *)mprime,
                                kbar, r_ws, ssrej, status, n, (const uint8_t *)nullptr, KeyIdx{});
     }
-    {
-        ProfScope ps(CIRCL_HIP_KERNEL_MLKEM_ENCRYPT, st);
-        auto kern = mlkem_encrypt_kernel<K, REENCRYPT, 0, true>;
-        const unsigned eb = std::min<unsigned>((unsigned)((n + Gm::G - 1) / Gm::G), resident_blocks(kern, Gm::LDS_SCRATCH_TOTAL));
-        hipLaunchKernelGGL(kern, dim3(eb), dim3(64), Gm::LDS_SCRATCH_TOTAL, st, dk + 384 * K, (size_t)Gm::DK, (const uint8_t *)mprime,
-                           (const uint8_t *)r_ws, const_cast<uint8_t *>(ct), ss, status, (const uint8_t *)kbar, (const uint8_t *)ssrej,
-                           w.scratch, w.work, n, KeyIdx{}, (const int16_t *)nullptr);
-    }
+    kem_encrypt<K, REENCRYPT, KM_ITEM>(w, n, Gm::G,
+                                       {dk + 384 * K, (size_t)Gm::DK, mprime, r_ws, const_cast<uint8_t *>(ct), ss, status, KeyIdx{}, nullptr, kbar, ssrej}, st);
     if (R3) {
         ProfScope ps(CIRCL_HIP_KERNEL_MLKEM_HASH, st);
         hipLaunchKernelGGL(kyber_r3_finish_kernel<K>, dim3(hb), dim3(256), 0, st, ct, ss, n);
@@ -501,6 +410,132 @@ int keygen_dev_impl(const uint8_t *seed64, uint8_t *ek, uint8_t *dk, size_t n, v
     return CIRCL_HIP_OK;
 }
 
+// ---- key tables --------------------------------------------------------------------------------------------------------------------
+// Item i works with entry key_idx[i] of a table of nkeys keys.  Per ENTRY: H(ek), A^T (the reference's parsed-key cache, kyber.go:39-43 /
+// cpapke.go:19-25) and, for a private key, the verdict of its hash check (kyber.go:219-228); per ITEM what the shared-key forms do (8 / 17
+// permutations for ML-KEM-768).  The entries' material is a KemTable: filled on every call behind the per-item workspace by the *_keyed
+// forms, kept across calls by the resident tables (keytable.h).
+
+// H(ek) (private keys: checked against the stored hash) and A^T of every entry, out of rows `row` bytes apart
+template <int K> void kem_table_fill(const KemTable<K> &tb, const uint8_t *keys, size_t row, bool private_keys, hipStream_t st) {
+    using Gm = circl::mlkem::Geom<K>;
+    using namespace circl::mlkem;
+    const size_t ek_off = private_keys ? 384 * K : 0, rho_off = ek_off + 384 * K;  // dk = s || ek || H(ek) || z, ek = t || rho
+    hipLaunchKernelGGL(mlkem_hek_table_kernel<K>, dim3((unsigned)((tb.nkeys + 255) / 256)), dim3(256), 0, st, keys, row, ek_off, tb.h(),
+                       private_keys ? tb.status() : (uint8_t *)nullptr, private_keys ? 1 : 0, tb.nkeys);
+    hipLaunchKernelGGL(mlkem_expand_keys_kernel<K>, dim3((unsigned)(tb.padded / Gm::G)), dim3(64), Gm::LDS_FIFO, st, keys, row, rho_off, tb.rows(), tb.nkeys);
+}
+
+// `keys` = the encapsulation keys, `stride` apart (0: every item uses entry 0).  `latency`: the table is resident, so a small batch is
+// worth its own routes -- one launch up to kem_chain_batch(false) items, small groups up to kem_small_shared_batch(false).
+template <int K>
+int encaps_with_table(const KemTable<K> &tb, const uint8_t *keys, size_t stride, KeyIdx kx, bool latency, const uint8_t *m, uint8_t *ct, uint8_t *ss,
+                      uint8_t *status, size_t n, const KemWs &w, hipStream_t st) {
+    using Gm = circl::mlkem::Geom<K>;
+    using namespace circl::mlkem;
+    uint8_t *r_ws = w.slot0;
+    if (latency && n <= kem_chain_batch(false)) {  // one launch, a wavefront per item: G -> PRF -> K-PKE.Encrypt (mlkem_encaps_chain_kernel)
+        ProfScope ps(CIRCL_HIP_KERNEL_MLKEM_ENCRYPT, st);
+        circl::TailFlag tail{nullptr, nullptr, 0};  // a coalesced batch's completion flag, raised by this launch's last workgroup (the kernel
+        take_tail_flag(&tail.flag, &tail.count, &tail.value);  // keeps everything in LDS: no workspace to wipe behind it)
+        hipLaunchKernelGGL(mlkem_encaps_chain_kernel<K>, dim3((unsigned)n), dim3(64), 0, st, keys, (size_t)Gm::EK, kx, (const int16_t *)tb.rows(),
+                           (const uint8_t *)tb.h(), m, ct, ss, status, n, tail);
+        HIP_TRY(hipGetLastError());
+        return CIRCL_HIP_OK;
+    }
+    HIP_TRY(hipMemsetAsync(w.work, 0, 256, st));
+    {
+        ProfScope ps(CIRCL_HIP_KERNEL_MLKEM_HASH, st);
+        hipLaunchKernelGGL(mlkem_g_shared_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const uint8_t *)tb.h(), m, ss, r_ws, n, kx);
+    }
+    // small batches: as few items per workgroup as the idle SIMDs allow (kem_small_group), like the other latency-oriented routes
+    const size_t want = latency && n <= kem_small_shared_batch(false) ? kem_small_group(n) : (size_t)Gm::GS;
+    kem_encrypt<K, ENCAPS, KM_KEYED>(w, n, want, {keys, stride, m, r_ws, ct, ss, status, kx, tb.rows()}, st);
+    HIP_TRY(hipGetLastError());
+    return CIRCL_HIP_OK;
+}
+// `dk` = the decapsulation keys (tb.status(): their verdicts).  `latency`: as above -- one launch up to kem_chain_batch() items, small
+// groups up to kem_small_shared_batch(true) and, without an index vector, the one-key pre-pass.
+template <int K>
+int decaps_with_table(const KemTable<K> &tb, const uint8_t *dk, size_t stride, KeyIdx kx, bool latency, const uint8_t *ct, uint8_t *ss, uint8_t *status,
+                      size_t n, const KemWs &w, hipStream_t st) {
+    using Gm = circl::mlkem::Geom<K>;
+    using namespace circl::mlkem;
+    uint8_t *mprime = w.slot0, *r_ws = w.slot1, *kbar = w.slot2, *ssrej = w.slot3;
+    const uint8_t *key_status = tb.status();
+    const unsigned hb = (unsigned)((n + 255) / 256);
+    // up to kem_chain_batch() items: the whole decapsulation of an item in ONE launch, a two-wavefront workgroup per item
+    // (mlkem_decaps_chain_kernel: J beside Decrypt -> G -> PRF -> re-encryption, one barrier, then the select)
+    if (latency && n <= kem_chain_batch()) {
+        ProfScope ps(CIRCL_HIP_KERNEL_MLKEM_DECRYPT, st);
+        circl::TailFlag tail{nullptr, nullptr, 0};
+        take_tail_flag(&tail.flag, &tail.count, &tail.value);
+        hipLaunchKernelGGL(mlkem_decaps_chain_kernel<K>, dim3((unsigned)n), dim3(128), 0, st, dk, (size_t)Gm::DK, kx, (const int16_t *)tb.rows(), key_status, ct, ss,
+                           status, n, tail);
+        HIP_TRY(hipGetLastError());
+        return CIRCL_HIP_OK;
+    }
+    HIP_TRY(hipMemsetAsync(w.work, 0, 256, st));
+    if (latency && !kx && n <= kem_small_shared_batch(true)) {
+        // ONE key, small batch: J(z || ct) on the cooperative permutation / lane pairs beside Decrypt + G (mlkem_small_decaps_pre_kernel
+        // without its hash-check and expansion workgroups: both are in the table)
+        const int coop = kem_hash_form(n, kem_coop_batch());
+        const unsigned nb_j = kem_hash_blocks(n, coop);
+        ProfScope ps(CIRCL_HIP_KERNEL_MLKEM_HASH, st);
+        hipLaunchKernelGGL(mlkem_small_decaps_pre_kernel<K>, dim3(nb_j + (unsigned)n), dim3(64), Gm::LDS_FIFO, st, dk, (size_t)0, ct, mprime, kbar, r_ws, ssrej,
+                           status, (uint8_t *)nullptr, (int16_t *)nullptr, n, nb_j, 0u, coop);
+        hipLaunchKernelGGL(mlkem_fill_status_kernel, dim3(hb), dim3(256), 0, st, status, key_status, n);
+    } else {
+        {
+            ProfScope ps(CIRCL_HIP_KERNEL_MLKEM_DECRYPT, st);
+            hipLaunchKernelGGL(mlkem_decrypt_kernel<K>, dim3((unsigned)n), dim3(64), 0, st, dk, stride, ct, mprime, n, kx);
+        }
+        ProfScope ps(CIRCL_HIP_KERNEL_MLKEM_HASH, st);
+        hipLaunchKernelGGL(mlkem_decaps_hash_kernel<K>, dim3(hb), dim3(256), 0, st, dk, stride, ct, (const uint8_t *)mprime, kbar, r_ws, ssrej, status, n,
+                           key_status, kx);
+    }
+    const size_t want = latency && n <= kem_small_shared_batch(true) ? kem_small_group(n, true) : (size_t)Gm::GS;
+    kem_encrypt<K, REENCRYPT, KM_KEYED>(w, n, want, {dk + 384 * K, stride, mprime, r_ws, const_cast<uint8_t *>(ct), ss, status, kx, tb.rows(), kbar, ssrej}, st);
+    HIP_TRY(hipGetLastError());
+    return CIRCL_HIP_OK;
+}
+
+// The per-call key tables: the table is built behind the per-item workspace (kem_ws_bytes(n), then KemTable<K>::bytes()) and used once,
+// by the throughput routes.
+template <int K>
+int encaps_keyed_dev_impl(const uint8_t *ek_table, size_t nkeys, const uint32_t *key_idx, const uint8_t *m, uint8_t *ct, uint8_t *ss,
+                          uint8_t *status, size_t n, void *ws, size_t ws_bytes, hipStream_t st) {
+    using Gm = circl::mlkem::Geom<K>;
+    if (n == 0) return CIRCL_HIP_OK;
+    if (nkeys == 0) return CIRCL_HIP_EPARAM;
+    if (ws_bytes < kem_ws_bytes(n) + KemTable<K>(nullptr, nkeys).bytes() || !aligned<16>(ws, ek_table, m, ct, ss) || !aligned<4>(key_idx))
+        return CIRCL_HIP_EWORKSPACE;
+    const KemTable<K> tb(static_cast<uint8_t *>(ws) + kem_ws_bytes(n), nkeys);
+    {
+        ProfScope ps(CIRCL_HIP_KERNEL_MLKEM_KEYTABLE, st);
+        kem_table_fill(tb, ek_table, Gm::EK, false, st);
+    }
+    const KeyIdx kx{key_idx, (uint32_t)(nkeys - 1)};  // a device index vector is bounded to the table on every read
+    return encaps_with_table(tb, ek_table, (size_t)Gm::EK, kx, false, m, ct, ss, status, n, KemWs(ws, n), st);
+}
+template <int K>
+int decaps_keyed_dev_impl(const uint8_t *dk_table, size_t nkeys, const uint32_t *key_idx, const uint8_t *ct, uint8_t *ss, uint8_t *status,
+                          size_t n, void *ws, size_t ws_bytes, hipStream_t st) {
+    using Gm = circl::mlkem::Geom<K>;
+    if (n == 0) return CIRCL_HIP_OK;
+    if (nkeys == 0) return CIRCL_HIP_EPARAM;
+    if (ws_bytes < kem_ws_bytes(n) + KemTable<K>(nullptr, nkeys).bytes() || !aligned<16>(ws, dk_table, ct, ss) ||
+        !aligned<4>(key_idx))
+        return CIRCL_HIP_EWORKSPACE;
+    const KemTable<K> tb(static_cast<uint8_t *>(ws) + kem_ws_bytes(n), nkeys);
+    {
+        ProfScope ps(CIRCL_HIP_KERNEL_MLKEM_KEYTABLE, st);
+        kem_table_fill(tb, dk_table, Gm::DK, true, st);
+    }
+    const KeyIdx kx{key_idx, (uint32_t)(nkeys - 1)};
+    return decaps_with_table(tb, dk_table, (size_t)Gm::DK, kx, false, ct, ss, status, n, KemWs(ws, n), st);
+}
+
 // Every ML-KEM host-buffer call wipes what is secret in a chunk's device staging once its results are out: the secret inputs and
 // outputs (seeds, m, private keys, shared secrets: flagged per array) and the per-item workspace slots (the coins r, G's output, m',
 // sigma).  The public keys, the ciphertexts, the matrix scratch and the row cache behind the slots are public and are NOT zeroed
@@ -520,121 +555,36 @@ std::function<size_t(size_t)> kem_ws_fn() {
 }
 
 // ---- key tables that live across calls (keytable.h) ------------------------------------------------------------------------------
-// The table memory has the layout of the per-call key tables' workspace tail (kem_table_bytes): A^T rows of whole groups, H(ek)
-// per entry, a status byte per entry.  key_idx == nullptr: every item uses entry 0 (the kernels see key stride 0).
-template <int K> int kem_table_build(circl_hip_keytable *t, hipStream_t st) {
+// The table memory is a KemTable, like the per-call key tables' workspace tail.  key_idx == nullptr: every item uses entry 0 (the
+// kernels see key stride 0).
+// (a new table's material; the private keys' verdicts start on their way to `key_status`, if that is wanted)
+template <int K> int kem_table_build(circl_hip_keytable *t, uint8_t *key_status, hipStream_t st) {
     using Gm = circl::mlkem::Geom<K>;
-    using namespace circl::mlkem;
-    const size_t padded = (t->nkeys + Gm::G - 1) / Gm::G * Gm::G;
-    int16_t *key_rows = reinterpret_cast<int16_t *>(t->d_table);
-    uint8_t *key_h = t->d_table + up256(padded * K * K * 512);
-    uint8_t *key_status = key_h + up256(t->nkeys * 32);
-    const size_t row = t->private_keys ? Gm::DK : Gm::EK;
-    hipLaunchKernelGGL(mlkem_hek_table_kernel<K>, dim3((unsigned)((t->nkeys + 255) / 256)), dim3(256), 0, st, (const uint8_t *)t->d_keys, row,
-                       (size_t)(t->private_keys ? 384 * K : 0), key_h, key_status, t->private_keys ? 1 : 0, t->nkeys);
-    hipLaunchKernelGGL(mlkem_expand_keys_kernel<K>, dim3((unsigned)(padded / Gm::G)), dim3(64), Gm::LDS_FIFO, st, (const uint8_t *)t->d_keys, row,
-                       (size_t)(t->private_keys ? 768 * K : 384 * K), key_rows, t->nkeys);
+    const KemTable<K> tb(t->d_table, t->nkeys);
+    kem_table_fill(tb, t->d_keys, t->private_keys ? Gm::DK : Gm::EK, t->private_keys != 0, st);
     HIP_TRY(hipGetLastError());
+    if (key_status && t->private_keys && hipMemcpyAsync(key_status, tb.status(), t->nkeys, hipMemcpyDeviceToHost, st) != hipSuccess) return CIRCL_HIP_EHIP;
     return CIRCL_HIP_OK;
 }
 template <int K>
 int encaps_table_dev_impl(const circl_hip_keytable *t, const uint32_t *key_idx, const uint8_t *m, uint8_t *ct, uint8_t *ss, uint8_t *status, size_t n,
                           void *ws, size_t ws_bytes, hipStream_t st) {
-    using Gm = circl::mlkem::Geom<K>;
-    using namespace circl::mlkem;
     if (n == 0) return CIRCL_HIP_OK;
     if (ws_bytes < kem_ws_min(n) || !aligned<16>(ws, m, ct, ss) || !aligned<4>(key_idx))
         return CIRCL_HIP_EWORKSPACE;
-    KemWs w(ws, n);
     const KeyIdx kx{key_idx, (uint32_t)(t->nkeys - 1)};
-    uint8_t *r_ws = w.slot0;
-    const size_t padded = (t->nkeys + Gm::G - 1) / Gm::G * Gm::G;
-    const int16_t *key_rows = reinterpret_cast<const int16_t *>(t->d_table);
-    const uint8_t *key_h = t->d_table + up256(padded * K * K * 512);
-    const size_t stride = key_idx ? (size_t)Gm::EK : 0;
-    if (n <= kem_chain_batch(false)) {  // one launch, a wavefront per item: G -> PRF -> K-PKE.Encrypt (mlkem_encaps_chain_kernel)
-        ProfScope ps(CIRCL_HIP_KERNEL_MLKEM_ENCRYPT, st);
-        circl::TailFlag tail{nullptr, nullptr, 0};  // a coalesced batch's completion flag, raised by this launch's last workgroup (the kernel
-        take_tail_flag(&tail.flag, &tail.count, &tail.value);  // keeps everything in LDS: no workspace to wipe behind it)
-        hipLaunchKernelGGL(mlkem_encaps_chain_kernel<K>, dim3((unsigned)n), dim3(64), 0, st, (const uint8_t *)t->d_keys, (size_t)Gm::EK, kx, key_rows, key_h, m, ct,
-                           ss, status, n, tail);
-        HIP_TRY(hipGetLastError());
-        return CIRCL_HIP_OK;
-    }
-    HIP_TRY(hipMemsetAsync(w.work, 0, 256, st));
-    {
-        ProfScope ps(CIRCL_HIP_KERNEL_MLKEM_HASH, st);
-        hipLaunchKernelGGL(mlkem_g_shared_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, key_h, m, ss, r_ws, n, kx);
-    }
-    {
-        auto kern = mlkem_encrypt_kernel<K, ENCAPS, 0, true, KM_KEYED>;
-        // small batches: as few items per workgroup as the idle SIMDs allow (kem_small_group), like the other latency-oriented routes
-        const size_t want = n <= kem_small_shared_batch(false) ? kem_small_group(n) : (size_t)Gm::GS;
-        const unsigned eb = std::min<unsigned>((unsigned)((n + want - 1) / want), resident_blocks(kern, Gm::LDS_SHARED_TOTAL));
-        ProfScope ps(CIRCL_HIP_KERNEL_MLKEM_ENCRYPT, st);
-        hipLaunchKernelGGL(kern, dim3(eb), dim3(64), Gm::LDS_SHARED_TOTAL, st, (const uint8_t *)t->d_keys, stride, m, (const uint8_t *)r_ws, ct, ss, status,
-                           (const uint8_t *)nullptr, (const uint8_t *)nullptr, w.scratch, w.work, n, kx, key_rows);
-    }
-    HIP_TRY(hipGetLastError());
-    return CIRCL_HIP_OK;
+    return encaps_with_table(KemTable<K>(t->d_table, t->nkeys), t->d_keys, key_idx ? (size_t)circl::mlkem::Geom<K>::EK : 0, kx, true, m, ct, ss, status, n,
+                             KemWs(ws, n), st);
 }
 template <int K>
 int decaps_table_dev_impl(const circl_hip_keytable *t, const uint32_t *key_idx, const uint8_t *ct, uint8_t *ss, uint8_t *status, size_t n, void *ws,
                           size_t ws_bytes, hipStream_t st) {
-    using Gm = circl::mlkem::Geom<K>;
-    using namespace circl::mlkem;
     if (n == 0) return CIRCL_HIP_OK;
     if (ws_bytes < kem_ws_min(n) || !aligned<16>(ws, ct, ss) || !aligned<4>(key_idx)) return CIRCL_HIP_EWORKSPACE;
-    KemWs w(ws, n);
+    const KemWs w(ws, n);
     const KeyIdx kx{key_idx, (uint32_t)(t->nkeys - 1)};
-    uint8_t *mprime = w.slot0, *r_ws = w.slot1, *kbar = w.slot2, *ssrej = w.slot3;
-    const size_t padded = (t->nkeys + Gm::G - 1) / Gm::G * Gm::G;
-    const int16_t *key_rows = reinterpret_cast<const int16_t *>(t->d_table);
-    const uint8_t *key_status = t->d_table + up256(padded * K * K * 512) + up256(t->nkeys * 32);
-    const uint8_t *dk = t->d_keys;
-    const size_t stride = key_idx ? (size_t)Gm::DK : 0;
     if (status == nullptr) status = w.status_slot;  // (the kernels want one; the caller may not)
-    const unsigned hb = (unsigned)((n + 255) / 256);
-    // up to kem_chain_batch() items: the whole decapsulation of an item in ONE launch, a two-wavefront workgroup per item
-    // (mlkem_decaps_chain_kernel: J beside Decrypt -> G -> PRF -> re-encryption, one barrier, then the select)
-    if (n <= kem_chain_batch()) {
-        ProfScope ps(CIRCL_HIP_KERNEL_MLKEM_DECRYPT, st);
-        circl::TailFlag tail{nullptr, nullptr, 0};
-        take_tail_flag(&tail.flag, &tail.count, &tail.value);
-        hipLaunchKernelGGL(mlkem_decaps_chain_kernel<K>, dim3((unsigned)n), dim3(128), 0, st, dk, (size_t)Gm::DK, kx, key_rows, key_status, ct, ss, status, n, tail);
-        HIP_TRY(hipGetLastError());
-        return CIRCL_HIP_OK;
-    }
-    HIP_TRY(hipMemsetAsync(w.work, 0, 256, st));
-    const bool small = key_idx == nullptr && n <= kem_small_shared_batch(true);
-    if (small) {
-        // ONE key, small batch: J(z || ct) on the cooperative permutation / lane pairs beside Decrypt + G (mlkem_small_decaps_pre_kernel
-        // without its hash-check and expansion workgroups: both are in the table)
-        const int coop = kem_hash_form(n, kem_coop_batch());
-        const unsigned nb_j = kem_hash_blocks(n, coop);
-        ProfScope ps(CIRCL_HIP_KERNEL_MLKEM_HASH, st);
-        hipLaunchKernelGGL(mlkem_small_decaps_pre_kernel<K>, dim3(nb_j + (unsigned)n), dim3(64), Gm::LDS_FIFO, st, dk, (size_t)0, ct, mprime, kbar, r_ws, ssrej,
-                           status, (uint8_t *)nullptr, (int16_t *)nullptr, n, nb_j, 0u, coop);
-        hipLaunchKernelGGL(mlkem_fill_status_kernel, dim3(hb), dim3(256), 0, st, status, key_status, n);
-    } else {
-        {
-            ProfScope ps(CIRCL_HIP_KERNEL_MLKEM_DECRYPT, st);
-            hipLaunchKernelGGL(mlkem_decrypt_kernel<K>, dim3((unsigned)n), dim3(64), 0, st, dk, stride, ct, mprime, n, kx);
-        }
-        ProfScope ps(CIRCL_HIP_KERNEL_MLKEM_HASH, st);
-        hipLaunchKernelGGL(mlkem_decaps_hash_kernel<K>, dim3(hb), dim3(256), 0, st, dk, stride, ct, (const uint8_t *)mprime, kbar, r_ws, ssrej, status, n,
-                           key_status, kx);
-    }
-    {
-        ProfScope ps(CIRCL_HIP_KERNEL_MLKEM_ENCRYPT, st);
-        auto kern = mlkem_encrypt_kernel<K, REENCRYPT, 0, true, KM_KEYED>;
-        const size_t want = n <= kem_small_shared_batch(true) ? kem_small_group(n, true) : (size_t)Gm::GS;
-        const unsigned eb = std::min<unsigned>((unsigned)((n + want - 1) / want), resident_blocks(kern, Gm::LDS_SHARED_TOTAL));
-        hipLaunchKernelGGL(kern, dim3(eb), dim3(64), Gm::LDS_SHARED_TOTAL, st, dk + 384 * K, stride, (const uint8_t *)mprime, (const uint8_t *)r_ws,
-                           const_cast<uint8_t *>(ct), ss, status, (const uint8_t *)kbar, (const uint8_t *)ssrej, w.scratch, w.work, n, kx, key_rows);
-    }
-    HIP_TRY(hipGetLastError());
-    return CIRCL_HIP_OK;
+    return decaps_with_table(KemTable<K>(t->d_table, t->nkeys), t->d_keys, key_idx ? (size_t)circl::mlkem::Geom<K>::DK : 0, kx, true, ct, ss, status, n, w, st);
 }
 bool kem_table_ok(const circl_hip_keytable *t, int want_private) {
     return t && t->magic == kKeytableMagic && t->family == 1 && t->private_keys == want_private && kem_k(t->param) != 0;
@@ -670,73 +620,70 @@ size_t circl_hip_mlkem_keyed_workspace_size(int param, size_t n, size_t nkeys) {
     return kem_k(param) ? kem_ws_bytes(n) + kem_table_bytes_any(param, nkeys) : 0;
 }
 
-#define KEM_DISPATCH(call2, call3, call4)                  \
-    if (ndev() <= 0) return CIRCL_HIP_ENODEV;              \
-    hipStream_t st = static_cast<hipStream_t>(stream);     \
-    switch (kem_k(param)) {                                \
-    case 2: return call2;                                  \
-    case 3: return call3;                                  \
-    case 4: return call4;                                  \
-    }                                                      \
-    return CIRCL_HIP_EPARAM
-
 int circl_hip_mlkem_encaps_dev(int param, const uint8_t *d_ek, const uint8_t *d_m, uint8_t *d_ct, uint8_t *d_ss,
                                uint8_t *d_status, size_t n, void *d_ws, size_t ws_bytes, void *stream) {
-    KEM_DISPATCH(encaps_dev_impl<2>(d_ek, d_m, d_ct, d_ss, d_status, n, d_ws, ws_bytes, st),
-                 encaps_dev_impl<3>(d_ek, d_m, d_ct, d_ss, d_status, n, d_ws, ws_bytes, st),
-                 encaps_dev_impl<4>(d_ek, d_m, d_ct, d_ss, d_status, n, d_ws, ws_bytes, st));
+    return kem_dev_call(param, stream, [&](auto k, hipStream_t st) { return encaps_dev_impl<k.value>(d_ek, d_m, d_ct, d_ss, d_status, n, d_ws, ws_bytes, st); });
 }
 int circl_hip_mlkem_decaps_dev(int param, const uint8_t *d_dk, const uint8_t *d_ct, uint8_t *d_ss, uint8_t *d_status, size_t n,
                                void *d_ws, size_t ws_bytes, void *stream) {
-    KEM_DISPATCH(decaps_dev_impl<2>(d_dk, d_ct, d_ss, d_status, n, d_ws, ws_bytes, st),
-                 decaps_dev_impl<3>(d_dk, d_ct, d_ss, d_status, n, d_ws, ws_bytes, st),
-                 decaps_dev_impl<4>(d_dk, d_ct, d_ss, d_status, n, d_ws, ws_bytes, st));
+    return kem_dev_call(param, stream, [&](auto k, hipStream_t st) { return decaps_dev_impl<k.value>(d_dk, d_ct, d_ss, d_status, n, d_ws, ws_bytes, st); });
 }
 int circl_hip_mlkem_keygen_dev(int param, const uint8_t *d_seed64, uint8_t *d_ek, uint8_t *d_dk, size_t n, void *d_ws,
                                size_t ws_bytes, void *stream) {
-    KEM_DISPATCH(keygen_dev_impl<2>(d_seed64, d_ek, d_dk, n, d_ws, ws_bytes, st),
-                 keygen_dev_impl<3>(d_seed64, d_ek, d_dk, n, d_ws, ws_bytes, st),
-                 keygen_dev_impl<4>(d_seed64, d_ek, d_dk, n, d_ws, ws_bytes, st));
+    return kem_dev_call(param, stream, [&](auto k, hipStream_t st) { return keygen_dev_impl<k.value>(d_seed64, d_ek, d_dk, n, d_ws, ws_bytes, st); });
 }
 int circl_hip_mlkem_encaps_shared_dev(int param, const uint8_t *d_ek, const uint8_t *d_m, uint8_t *d_ct, uint8_t *d_ss, uint8_t *d_status,
                                       size_t n, void *d_ws, size_t ws_bytes, void *stream) {
-    KEM_DISPATCH(encaps_shared_dev_impl<2>(d_ek, d_m, d_ct, d_ss, d_status, n, d_ws, ws_bytes, st),
-                 encaps_shared_dev_impl<3>(d_ek, d_m, d_ct, d_ss, d_status, n, d_ws, ws_bytes, st),
-                 encaps_shared_dev_impl<4>(d_ek, d_m, d_ct, d_ss, d_status, n, d_ws, ws_bytes, st));
+    return kem_dev_call(param, stream,
+                        [&](auto k, hipStream_t st) { return encaps_shared_dev_impl<k.value>(d_ek, d_m, d_ct, d_ss, d_status, n, d_ws, ws_bytes, st); });
 }
 int circl_hip_mlkem_decaps_shared_dev(int param, const uint8_t *d_dk, const uint8_t *d_ct, uint8_t *d_ss, uint8_t *d_status, size_t n,
                                       void *d_ws, size_t ws_bytes, void *stream) {
-    KEM_DISPATCH(decaps_shared_dev_impl<2>(d_dk, d_ct, d_ss, d_status, n, d_ws, ws_bytes, st),
-                 decaps_shared_dev_impl<3>(d_dk, d_ct, d_ss, d_status, n, d_ws, ws_bytes, st),
-                 decaps_shared_dev_impl<4>(d_dk, d_ct, d_ss, d_status, n, d_ws, ws_bytes, st));
+    return kem_dev_call(param, stream, [&](auto k, hipStream_t st) { return decaps_shared_dev_impl<k.value>(d_dk, d_ct, d_ss, d_status, n, d_ws, ws_bytes, st); });
 }
 int circl_hip_mlkem_encaps_keyed_dev(int param, const uint8_t *d_ek_table, size_t nkeys, const uint32_t *d_key_idx, const uint8_t *d_m,
                                      uint8_t *d_ct, uint8_t *d_ss, uint8_t *d_status, size_t n, void *d_ws, size_t ws_bytes, void *stream) {
-    KEM_DISPATCH(encaps_keyed_dev_impl<2>(d_ek_table, nkeys, d_key_idx, d_m, d_ct, d_ss, d_status, n, d_ws, ws_bytes, st),
-                 encaps_keyed_dev_impl<3>(d_ek_table, nkeys, d_key_idx, d_m, d_ct, d_ss, d_status, n, d_ws, ws_bytes, st),
-                 encaps_keyed_dev_impl<4>(d_ek_table, nkeys, d_key_idx, d_m, d_ct, d_ss, d_status, n, d_ws, ws_bytes, st));
+    return kem_dev_call(param, stream, [&](auto k, hipStream_t st) {
+        return encaps_keyed_dev_impl<k.value>(d_ek_table, nkeys, d_key_idx, d_m, d_ct, d_ss, d_status, n, d_ws, ws_bytes, st);
+    });
 }
 int circl_hip_mlkem_decaps_keyed_dev(int param, const uint8_t *d_dk_table, size_t nkeys, const uint32_t *d_key_idx, const uint8_t *d_ct,
                                      uint8_t *d_ss, uint8_t *d_status, size_t n, void *d_ws, size_t ws_bytes, void *stream) {
-    KEM_DISPATCH(decaps_keyed_dev_impl<2>(d_dk_table, nkeys, d_key_idx, d_ct, d_ss, d_status, n, d_ws, ws_bytes, st),
-                 decaps_keyed_dev_impl<3>(d_dk_table, nkeys, d_key_idx, d_ct, d_ss, d_status, n, d_ws, ws_bytes, st),
-                 decaps_keyed_dev_impl<4>(d_dk_table, nkeys, d_key_idx, d_ct, d_ss, d_status, n, d_ws, ws_bytes, st));
+    return kem_dev_call(param, stream, [&](auto k, hipStream_t st) {
+        return decaps_keyed_dev_impl<k.value>(d_dk_table, nkeys, d_key_idx, d_ct, d_ss, d_status, n, d_ws, ws_bytes, st);
+    });
 }
 
 // ---- host buffers ---------------------------------------------------------------------------------
+// Every operation says its arrays and its launch once; the blocking call, the submitted call and the asynchronous queue share them.
+// (`secret`: wiped from the staging; a table call's key_idx is the one OPTIONAL array: absent = entry 0 for every item)
+static std::vector<HIn> kem_enc_ins(const uint8_t *ek, const uint8_t *m, size_t EK) { return {{ek, EK}, {m, 32, true}}; }
+static std::vector<HIn> kem_dec_ins(const uint8_t *dk, const uint8_t *ct, size_t DK, size_t CT) { return {{dk, DK, true}, {ct, CT}}; }
+static std::vector<HIn> kem_enc_table_ins(const uint32_t *ki, const uint8_t *m) { return {{reinterpret_cast<const uint8_t *>(ki), size_t(4), false, false, true}, {m, 32, true}}; }
+static std::vector<HIn> kem_dec_table_ins(const uint32_t *ki, const uint8_t *ct, size_t CT) { return {{reinterpret_cast<const uint8_t *>(ki), size_t(4), false, false, true}, {ct, CT}}; }
+static std::vector<HOut> kem_enc_outs(uint8_t *ct, uint8_t *ss, uint8_t *status, size_t CT) { return {{ct, CT}, {ss, 32, true}, {status, 1}}; }
+static std::vector<HOut> kem_dec_outs(uint8_t *ss, uint8_t *status) { return {{ss, 32, true}, {status, 1}}; }
+static int kem_enc_chunk(int param, Chunk &c) { return circl_hip_mlkem_encaps_dev(param, c.in[0], c.in[1], c.out[0], c.out[1], c.out[2], c.cnt, c.ws, c.ws_bytes, c.st); }
+static int kem_dec_chunk(int param, Chunk &c) { return circl_hip_mlkem_decaps_dev(param, c.in[0], c.in[1], c.out[0], c.out[1], c.cnt, c.ws, c.ws_bytes, c.st); }
+static int kem_enc_table_chunk(const circl_hip_keytable *r, Chunk &c, const uint32_t *d_key_idx) {
+    return circl_hip_mlkem_encaps_table_dev(r, d_key_idx, c.in[1], c.out[0], c.out[1], c.out[2], c.cnt, c.ws, c.ws_bytes, c.st);
+}
+static int kem_dec_table_chunk(const circl_hip_keytable *r, Chunk &c, const uint32_t *d_key_idx) {
+    return circl_hip_mlkem_decaps_table_dev(r, d_key_idx, c.in[1], c.out[0], c.out[1], c.cnt, c.ws, c.ws_bytes, c.st);
+}
+static const uint32_t *key_idx_of(const Chunk &c) { return reinterpret_cast<const uint32_t *>(c.in[0]); }
 
 int circl_hip_mlkem_encaps(int param, const uint8_t *ek, const uint8_t *m, uint8_t *ct, uint8_t *ss, uint8_t *status,
                            size_t n, int device) {
     const size_t EK = circl_hip_mlkem_ek_size(param), CT = circl_hip_mlkem_ct_size(param);
     if (!EK) return CIRCL_HIP_EPARAM;
     return shard(n, device, [&](int dev, size_t lo, size_t cnt) {
-        const std::vector<HIn> ins = {{ek + lo * EK, EK}, {m + lo * 32, 32, true}};
-        const std::vector<HOut> outs = {{ct + lo * CT, CT}, {ss + lo * 32, 32, true}, {status ? status + lo : nullptr, 1}};
-        auto launch = [&](Chunk &c) { return circl_hip_mlkem_encaps_dev(param, c.in[0], c.in[1], c.out[0], c.out[1], c.out[2], c.cnt, c.ws, c.ws_bytes, c.st); };
+        const std::vector<HIn> ins = kem_enc_ins(ek + lo * EK, m + lo * 32, EK);
         // circl_hip_set_coalesce: the small calls of concurrent callers share launches -- a TLS server's shape: every handshake
         // encapsulates once, to a key of its own (kem/hybrid/hybrid.go:95-99 -> kem/mlkem/mlkem768/kyber.go:359-370)
         Coalescer *co = all_inputs_present(ins) ? call_coalescer(kCoKemEncaps, kem_k(param) - 2, dev) : nullptr;
-        return coalesce_or_pipeline(co, dev, cnt, ins, {}, outs, kem_ws_fn(), kem_opts(), launch);
+        return coalesce_or_pipeline(co, dev, cnt, ins, {}, kem_enc_outs(ct + lo * CT, ss + lo * 32, status ? status + lo : nullptr, CT), kem_ws_fn(), kem_opts(),
+                                    [&](Chunk &c) { return kem_enc_chunk(param, c); });
     });
 }
 
@@ -744,28 +691,32 @@ int circl_hip_mlkem_decaps(int param, const uint8_t *dk, const uint8_t *ct, uint
     const size_t DK = circl_hip_mlkem_dk_size(param), CT = circl_hip_mlkem_ct_size(param);
     if (!DK) return CIRCL_HIP_EPARAM;
     return shard(n, device, [&](int dev, size_t lo, size_t cnt) {
-        const std::vector<HIn> ins = {{dk + lo * DK, DK, true}, {ct + lo * CT, CT}};
-        const std::vector<HOut> outs = {{ss + lo * 32, 32, true}, {status ? status + lo : nullptr, 1}};
-        auto launch = [&](Chunk &c) { return circl_hip_mlkem_decaps_dev(param, c.in[0], c.in[1], c.out[0], c.out[1], c.cnt, c.ws, c.ws_bytes, c.st); };
+        const std::vector<HIn> ins = kem_dec_ins(dk + lo * DK, ct + lo * CT, DK, CT);
         Coalescer *co = all_inputs_present(ins) ? call_coalescer(kCoKemDecaps, kem_k(param) - 2, dev) : nullptr;  // (circl_hip_set_coalesce, as above)
-        return coalesce_or_pipeline(co, dev, cnt, ins, {}, outs, kem_ws_fn(), kem_opts(), launch);
+        return coalesce_or_pipeline(co, dev, cnt, ins, {}, kem_dec_outs(ss + lo * 32, status ? status + lo : nullptr), kem_ws_fn(), kem_opts(),
+                                    [&](Chunk &c) { return kem_dec_chunk(param, c); });
     });
 }
 
-int circl_hip_mlkem_keygen(int param, const uint8_t *seed64, uint8_t *ek, uint8_t *dk, size_t n, int device) {
+// ML-KEM and round-3 Kyber key generation differ in the *_keygen_dev they launch
+typedef int (*kem_keygen_dev_fn)(int, const uint8_t *, uint8_t *, uint8_t *, size_t, void *, size_t, void *);
+static int kem_keygen_host(kem_keygen_dev_fn keygen_dev, int param, const uint8_t *seed64, uint8_t *ek, uint8_t *dk, size_t n, int device) {
     const size_t EK = circl_hip_mlkem_ek_size(param), DK = circl_hip_mlkem_dk_size(param);
     if (!EK) return CIRCL_HIP_EPARAM;
     return shard(n, device, [&](int dev, size_t lo, size_t cnt) {
         return run_pipeline(dev, cnt, {{seed64 + lo * 64, 64, true}}, {}, {{ek + lo * EK, EK}, {dk + lo * DK, DK, true}}, kem_ws_fn(), kem_opts(),
-                            [&](Chunk &c) { return circl_hip_mlkem_keygen_dev(param, c.in[0], c.out[0], c.out[1], c.cnt, c.ws, c.ws_bytes, c.st); });
+                            [&](Chunk &c) { return keygen_dev(param, c.in[0], c.out[0], c.out[1], c.cnt, c.ws, c.ws_bytes, c.st); });
     });
+}
+int circl_hip_mlkem_keygen(int param, const uint8_t *seed64, uint8_t *ek, uint8_t *dk, size_t n, int device) {
+    return kem_keygen_host(circl_hip_mlkem_keygen_dev, param, seed64, ek, dk, n, device);
 }
 
 int circl_hip_mlkem_decaps_shared(int param, const uint8_t *dk, const uint8_t *ct, uint8_t *ss, uint8_t *status, size_t n, int device) {
     const size_t DK = circl_hip_mlkem_dk_size(param), CT = circl_hip_mlkem_ct_size(param);
     if (!DK) return CIRCL_HIP_EPARAM;
     return shard(n, device, [&](int dev, size_t lo, size_t cnt) {
-        return run_pipeline(dev, cnt, {{dk, DK, true, true}, {ct + lo * CT, CT}}, {}, {{ss + lo * 32, 32, true}, {status ? status + lo : nullptr, 1}},
+        return run_pipeline(dev, cnt, {{dk, DK, true, true}, {ct + lo * CT, CT}}, {}, kem_dec_outs(ss + lo * 32, status ? status + lo : nullptr),
                             kem_ws_fn(), kem_opts(), [&](Chunk &c) {
                                 return circl_hip_mlkem_decaps_shared_dev(param, c.in[0], c.in[1], c.out[0], c.out[1], c.cnt, c.ws, c.ws_bytes, c.st);
                             });
@@ -777,7 +728,7 @@ int circl_hip_mlkem_encaps_shared(int param, const uint8_t *ek, const uint8_t *m
     if (!EK) return CIRCL_HIP_EPARAM;
     return shard(n, device, [&](int dev, size_t lo, size_t cnt) {
         return run_pipeline(dev, cnt, {{ek, EK, false, true}, {m + lo * 32, 32, true}}, {},
-                            {{ct + lo * CT, CT}, {ss + lo * 32, 32, true}, {status ? status + lo : nullptr, 1}}, kem_ws_fn(), kem_opts(), [&](Chunk &c) {
+                            kem_enc_outs(ct + lo * CT, ss + lo * 32, status ? status + lo : nullptr, CT), kem_ws_fn(), kem_opts(), [&](Chunk &c) {
                                 return circl_hip_mlkem_encaps_shared_dev(param, c.in[0], c.in[1], c.out[0], c.out[1], c.out[2], c.cnt, c.ws, c.ws_bytes, c.st);
                             });
     });
@@ -794,7 +745,7 @@ int circl_hip_mlkem_encaps_keyed(int param, const uint8_t *ek_table, size_t nkey
     TRY(check_key_idx(key_idx, n, nkeys));
     return shard(n, device, [&](int dev, size_t lo, size_t cnt) {
         return run_pipeline(dev, cnt, {{ek_table, EK * nkeys, false, true}, {reinterpret_cast<const uint8_t *>(key_idx + lo), 4}, {m + lo * 32, 32, true}}, {},
-                            {{ct + lo * CT, CT}, {ss + lo * 32, 32, true}, {status ? status + lo : nullptr, 1}},
+                            kem_enc_outs(ct + lo * CT, ss + lo * 32, status ? status + lo : nullptr, CT),
                             [&](size_t c) { return circl_hip_mlkem_keyed_workspace_size(param, c, nkeys); }, kem_opts(), [&](Chunk &c) {
                                 return circl_hip_mlkem_encaps_keyed_dev(param, c.in[0], nkeys, reinterpret_cast<const uint32_t *>(c.in[1]), c.in[2], c.out[0],
                                                                         c.out[1], c.out[2], c.cnt, c.ws, c.ws_bytes, c.st);
@@ -810,7 +761,7 @@ int circl_hip_mlkem_decaps_keyed(int param, const uint8_t *dk_table, size_t nkey
     TRY(check_key_idx(key_idx, n, nkeys));
     return shard(n, device, [&](int dev, size_t lo, size_t cnt) {
         return run_pipeline(dev, cnt, {{dk_table, DK * nkeys, true, true}, {reinterpret_cast<const uint8_t *>(key_idx + lo), 4}, {ct + lo * CT, CT}}, {},
-                            {{ss + lo * 32, 32, true}, {status ? status + lo : nullptr, 1}},
+                            kem_dec_outs(ss + lo * 32, status ? status + lo : nullptr),
                             [&](size_t c) { return circl_hip_mlkem_keyed_workspace_size(param, c, nkeys); }, kem_opts(), [&](Chunk &c) {
                                 return circl_hip_mlkem_decaps_keyed_dev(param, c.in[0], nkeys, reinterpret_cast<const uint32_t *>(c.in[1]), c.in[2], c.out[0],
                                                                         c.out[1], c.cnt, c.ws, c.ws_bytes, c.st);
@@ -821,7 +772,6 @@ int circl_hip_mlkem_decaps_keyed(int param, const uint8_t *dk_table, size_t nkey
 // ---- key tables that live across calls ---------------------------------------------------------------------------------------
 static int kem_keytable_new_one(int param, int private_keys, const uint8_t *keys, size_t nkeys, int device, uint8_t *key_status,
                                 circl_hip_keytable **out) {
-    const int K = kem_k(param);
     HIP_TRY(hipSetDevice(physical_device(device)));
     circl_hip_keytable *t = new (std::nothrow) circl_hip_keytable();
     if (!t) return CIRCL_HIP_ENOMEM;
@@ -840,16 +790,9 @@ static int kem_keytable_new_one(int param, int private_keys, const uint8_t *keys
         if (private_keys) rc = upload_secret(t->d_keys, keys, t->row * nkeys, st);
         else if (hipMemcpyAsync(t->d_keys, keys, t->row * nkeys, hipMemcpyHostToDevice, st) != hipSuccess) rc = CIRCL_HIP_EHIP;
     }
-    if (rc == CIRCL_HIP_OK) rc = K == 2 ? kem_table_build<2>(t, st) : K == 3 ? kem_table_build<3>(t, st) : kem_table_build<4>(t, st);
-    if (rc == CIRCL_HIP_OK && key_status) {
-        const size_t G = K == 2 ? 16 : K == 3 ? 7 : 4, padded = (nkeys + G - 1) / G * G;  // (Geom<K>::G)
-        const uint8_t *ks = t->d_table + up256(padded * K * K * 512) + up256(nkeys * 32);
-        if (private_keys) {
-            if (hipMemcpyAsync(key_status, ks, nkeys, hipMemcpyDeviceToHost, st) != hipSuccess) rc = CIRCL_HIP_EHIP;
-        } else {
-            memset(key_status, 0, nkeys);  // a public key's canonicity is reported per item by the encapsulation (status 1)
-        }
-    }
+    if (rc == CIRCL_HIP_OK) rc = kem_with_k(param, [&](auto k) { return kem_table_build<k.value>(t, key_status, st); });
+    // (a public key's canonicity is reported per item by the encapsulation: status 1)
+    if (rc == CIRCL_HIP_OK && key_status && !private_keys) memset(key_status, 0, nkeys);
     if (rc == CIRCL_HIP_OK && hipStreamSynchronize(st) != hipSuccess) rc = CIRCL_HIP_EHIP;
     if (rc != CIRCL_HIP_OK) {
         (void)hipGetLastError();
@@ -872,24 +815,16 @@ int circl_hip_mlkem_encaps_table_dev(const circl_hip_keytable *t, const uint32_t
                                      uint8_t *d_status, size_t n, void *d_ws, size_t ws_bytes, void *stream) {
     t = keytable_here(t);
     if (!kem_table_ok(t, 0)) return CIRCL_HIP_EPARAM;
-    const int param = t->param;
-    KEM_DISPATCH(encaps_table_dev_impl<2>(t, d_key_idx, d_m, d_ct, d_ss, d_status, n, d_ws, ws_bytes, st),
-                 encaps_table_dev_impl<3>(t, d_key_idx, d_m, d_ct, d_ss, d_status, n, d_ws, ws_bytes, st),
-                 encaps_table_dev_impl<4>(t, d_key_idx, d_m, d_ct, d_ss, d_status, n, d_ws, ws_bytes, st));
+    return kem_dev_call(t->param, stream, [&](auto k, hipStream_t st) { return encaps_table_dev_impl<k.value>(t, d_key_idx, d_m, d_ct, d_ss, d_status, n, d_ws, ws_bytes, st); });
 }
 int circl_hip_mlkem_decaps_table_dev(const circl_hip_keytable *t, const uint32_t *d_key_idx, const uint8_t *d_ct, uint8_t *d_ss, uint8_t *d_status,
                                      size_t n, void *d_ws, size_t ws_bytes, void *stream) {
     t = keytable_here(t);
     if (!kem_table_ok(t, 1)) return CIRCL_HIP_EPARAM;
-    const int param = t->param;
-    KEM_DISPATCH(decaps_table_dev_impl<2>(t, d_key_idx, d_ct, d_ss, d_status, n, d_ws, ws_bytes, st),
-                 decaps_table_dev_impl<3>(t, d_key_idx, d_ct, d_ss, d_status, n, d_ws, ws_bytes, st),
-                 decaps_table_dev_impl<4>(t, d_key_idx, d_ct, d_ss, d_status, n, d_ws, ws_bytes, st));
+    return kem_dev_call(t->param, stream, [&](auto k, hipStream_t st) { return decaps_table_dev_impl<k.value>(t, d_key_idx, d_ct, d_ss, d_status, n, d_ws, ws_bytes, st); });
 }
 // host buffers: only the per-item data travel; the keys and what was parsed out of them are already on the table's device
-// (key_idx is the one OPTIONAL array: absent = entry 0 for every item; a NULL m / ct is CIRCL_HIP_EPARAM on every path)
-static std::vector<HIn> kem_enc_ins(const uint32_t *ki, const uint8_t *m) { return {{reinterpret_cast<const uint8_t *>(ki), size_t(4), false, false, true}, {m, 32, true}}; }
-static std::vector<HIn> kem_dec_ins(const uint32_t *ki, const uint8_t *ct, size_t CT) { return {{reinterpret_cast<const uint8_t *>(ki), size_t(4), false, false, true}, {ct, CT}}; }
+// (a NULL m / ct is CIRCL_HIP_EPARAM on every path)
 int circl_hip_mlkem_encaps_table(const circl_hip_keytable *t, const uint32_t *key_idx, const uint8_t *m, uint8_t *ct, uint8_t *ss, uint8_t *status,
                                  size_t n) {
     if (!kem_table_ok(t, 0)) return CIRCL_HIP_EPARAM;
@@ -897,11 +832,9 @@ int circl_hip_mlkem_encaps_table(const circl_hip_keytable *t, const uint32_t *ke
     if (n == 0) return CIRCL_HIP_OK;
     if (key_idx) TRY(check_key_idx(key_idx, n, t->nkeys));
     return table_shard(t, n, [&](const circl_hip_keytable *r, size_t lo, size_t cnt) {  // (a small call joins the table's cross-caller batch)
-        return table_coalesce_or_pipeline(r, cnt, kem_enc_ins(key_idx ? key_idx + lo : nullptr, m ? m + lo * 32 : nullptr), 0, {},
-                                          {{ct + lo * CT, CT}, {ss + lo * 32, 32, true}, {status ? status + lo : nullptr, 1}}, kem_ws_fn(), kem_opts(), kem_opts(),
-                                          [&](Chunk &c, const uint32_t *d_key_idx) {
-                                              return circl_hip_mlkem_encaps_table_dev(r, d_key_idx, c.in[1], c.out[0], c.out[1], c.out[2], c.cnt, c.ws, c.ws_bytes, c.st);
-                                          });
+        return table_coalesce_or_pipeline(r, cnt, kem_enc_table_ins(key_idx ? key_idx + lo : nullptr, m ? m + lo * 32 : nullptr), 0, {},
+                                          kem_enc_outs(ct + lo * CT, ss + lo * 32, status ? status + lo : nullptr, CT), kem_ws_fn(), kem_opts(), kem_opts(),
+                                          [&](Chunk &c, const uint32_t *d_key_idx) { return kem_enc_table_chunk(r, c, d_key_idx); });
     });
 }
 int circl_hip_mlkem_decaps_table(const circl_hip_keytable *t, const uint32_t *key_idx, const uint8_t *ct, uint8_t *ss, uint8_t *status, size_t n) {
@@ -910,11 +843,9 @@ int circl_hip_mlkem_decaps_table(const circl_hip_keytable *t, const uint32_t *ke
     if (n == 0) return CIRCL_HIP_OK;
     if (key_idx) TRY(check_key_idx(key_idx, n, t->nkeys));
     return table_shard(t, n, [&](const circl_hip_keytable *r, size_t lo, size_t cnt) {
-        return table_coalesce_or_pipeline(r, cnt, kem_dec_ins(key_idx ? key_idx + lo : nullptr, ct ? ct + lo * CT : nullptr, CT), 0, {},
-                                          {{ss + lo * 32, 32, true}, {status ? status + lo : nullptr, 1}}, kem_ws_fn(), kem_opts(), kem_opts(),
-                                          [&](Chunk &c, const uint32_t *d_key_idx) {
-                                              return circl_hip_mlkem_decaps_table_dev(r, d_key_idx, c.in[1], c.out[0], c.out[1], c.cnt, c.ws, c.ws_bytes, c.st);
-                                          });
+        return table_coalesce_or_pipeline(r, cnt, kem_dec_table_ins(key_idx ? key_idx + lo : nullptr, ct ? ct + lo * CT : nullptr, CT), 0, {},
+                                          kem_dec_outs(ss + lo * 32, status ? status + lo : nullptr), kem_ws_fn(), kem_opts(), kem_opts(),
+                                          [&](Chunk &c, const uint32_t *d_key_idx) { return kem_dec_table_chunk(r, c, d_key_idx); });
     });
 }
 // ---- the asynchronous form (include/circl_hip.h: circl_hip_keytable_async_start) ----
@@ -926,7 +857,7 @@ int circl_hip_mlkem_encaps_table_submit(const circl_hip_keytable *t, const uint3
     if (n == 0) return CIRCL_HIP_OK;
     if (key_idx) TRY(check_key_idx(key_idx, n, t->nkeys));
     return table_submit(t, ticket, [&](const circl_hip_keytable *, Coalescer *co, uint64_t *seq) {
-        return coalesce_submit(co, n, kem_enc_ins(key_idx, m), {}, {{ct, CT}, {ss, 32, true}, {status, 1}}, seq, false);
+        return coalesce_submit(co, n, kem_enc_table_ins(key_idx, m), {}, kem_enc_outs(ct, ss, status, CT), seq, false);
     });
 }
 int circl_hip_mlkem_decaps_table_submit(const circl_hip_keytable *t, const uint32_t *key_idx, const uint8_t *ct, uint8_t *ss, uint8_t *status, size_t n,
@@ -937,7 +868,7 @@ int circl_hip_mlkem_decaps_table_submit(const circl_hip_keytable *t, const uint3
     if (n == 0) return CIRCL_HIP_OK;
     if (key_idx) TRY(check_key_idx(key_idx, n, t->nkeys));
     return table_submit(t, ticket, [&](const circl_hip_keytable *, Coalescer *co, uint64_t *seq) {
-        return coalesce_submit(co, n, kem_dec_ins(key_idx, ct, CT), {}, {{ss, 32, true}, {status, 1}}, seq, false);
+        return coalesce_submit(co, n, kem_dec_table_ins(key_idx, ct, CT), {}, kem_dec_outs(ss, status), seq, false);
     });
 }
 }  // extern "C"
@@ -950,25 +881,21 @@ int kem_call_queue_start(bool decaps, int param, Coalescer *co, bool want_eventf
     if (!EK) return CIRCL_HIP_EPARAM;
     if (!decaps) {
         *sh = QueueShape{EK, 32, CT, 32, false, true};
-        return coalescer_async_start(co, {{nullptr, EK}, {nullptr, 32, true}}, {}, {{nullptr, CT}, {nullptr, 32, true}, {nullptr, 1}}, kem_ws_fn(), kem_opts(), [param](Chunk &c) {
-            return circl_hip_mlkem_encaps_dev(param, c.in[0], c.in[1], c.out[0], c.out[1], c.out[2], c.cnt, c.ws, c.ws_bytes, c.st);
-        }, want_eventfd);
+        return coalescer_async_start(co, kem_enc_ins(nullptr, nullptr, EK), {}, kem_enc_outs(nullptr, nullptr, nullptr, CT), kem_ws_fn(), kem_opts(),
+                                     [param](Chunk &c) { return kem_enc_chunk(param, c); }, want_eventfd);
     }
     *sh = QueueShape{DK, CT, 0, 32, true, false};
-    return coalescer_async_start(co, {{nullptr, DK, true}, {nullptr, CT}}, {}, {{nullptr, 32, true}, {nullptr, 1}}, kem_ws_fn(), kem_opts(), [param](Chunk &c) {
-        return circl_hip_mlkem_decaps_dev(param, c.in[0], c.in[1], c.out[0], c.out[1], c.cnt, c.ws, c.ws_bytes, c.st);
-    }, want_eventfd);
+    return coalescer_async_start(co, kem_dec_ins(nullptr, nullptr, DK, CT), {}, kem_dec_outs(nullptr, nullptr), kem_ws_fn(), kem_opts(),
+                                 [param](Chunk &c) { return kem_dec_chunk(param, c); }, want_eventfd);
 }
 // the queue of one ML-KEM table (part): its arrays and its launch, fixed for the queue's life (`r` outlives the queue: the table owns it)
 int kem_table_async_start(const circl_hip_keytable *r, Coalescer *co, bool want_eventfd) {
     const size_t CT = circl_hip_mlkem_ct_size(r->param);
     if (!r->private_keys)
-        return coalescer_async_start(co, kem_enc_ins(nullptr, nullptr), {}, {{nullptr, CT}, {nullptr, 32, true}, {nullptr, 1}}, kem_ws_fn(), kem_opts(), [r](Chunk &c) {
-            return circl_hip_mlkem_encaps_table_dev(r, reinterpret_cast<const uint32_t *>(c.in[0]), c.in[1], c.out[0], c.out[1], c.out[2], c.cnt, c.ws, c.ws_bytes, c.st);
-        }, want_eventfd);
-    return coalescer_async_start(co, kem_dec_ins(nullptr, nullptr, CT), {}, {{nullptr, 32, true}, {nullptr, 1}}, kem_ws_fn(), kem_opts(), [r](Chunk &c) {
-        return circl_hip_mlkem_decaps_table_dev(r, reinterpret_cast<const uint32_t *>(c.in[0]), c.in[1], c.out[0], c.out[1], c.cnt, c.ws, c.ws_bytes, c.st);
-    }, want_eventfd);
+        return coalescer_async_start(co, kem_enc_table_ins(nullptr, nullptr), {}, kem_enc_outs(nullptr, nullptr, nullptr, CT), kem_ws_fn(), kem_opts(),
+                                     [r](Chunk &c) { return kem_enc_table_chunk(r, c, key_idx_of(c)); }, want_eventfd);
+    return coalescer_async_start(co, kem_dec_table_ins(nullptr, nullptr, CT), {}, kem_dec_outs(nullptr, nullptr), kem_ws_fn(), kem_opts(),
+                                 [r](Chunk &c) { return kem_dec_table_chunk(r, c, key_idx_of(c)); }, want_eventfd);
 }
 }  // namespace host
 }  // namespace circl
@@ -987,35 +914,24 @@ int circl_hip_mlkem_public_from_private(int param, const uint8_t *dk, uint8_t *e
 
 int circl_hip_kyber_keygen_dev(int param, const uint8_t *d_seed64, uint8_t *d_ek, uint8_t *d_dk, size_t n, void *d_ws, size_t ws_bytes,
                                void *stream) {
-    KEM_DISPATCH((keygen_dev_impl<2, true>(d_seed64, d_ek, d_dk, n, d_ws, ws_bytes, st)),
-                 (keygen_dev_impl<3, true>(d_seed64, d_ek, d_dk, n, d_ws, ws_bytes, st)),
-                 (keygen_dev_impl<4, true>(d_seed64, d_ek, d_dk, n, d_ws, ws_bytes, st)));
+    return kem_dev_call(param, stream, [&](auto k, hipStream_t st) { return keygen_dev_impl<k.value, true>(d_seed64, d_ek, d_dk, n, d_ws, ws_bytes, st); });
 }
 int circl_hip_kyber_encaps_dev(int param, const uint8_t *d_ek, const uint8_t *d_seed32, uint8_t *d_ct, uint8_t *d_ss, size_t n, void *d_ws,
                                size_t ws_bytes, void *stream) {
-    KEM_DISPATCH((encaps_dev_impl<2, true>(d_ek, d_seed32, d_ct, d_ss, nullptr, n, d_ws, ws_bytes, st)),
-                 (encaps_dev_impl<3, true>(d_ek, d_seed32, d_ct, d_ss, nullptr, n, d_ws, ws_bytes, st)),
-                 (encaps_dev_impl<4, true>(d_ek, d_seed32, d_ct, d_ss, nullptr, n, d_ws, ws_bytes, st)));
+    return kem_dev_call(param, stream, [&](auto k, hipStream_t st) { return encaps_dev_impl<k.value, true>(d_ek, d_seed32, d_ct, d_ss, nullptr, n, d_ws, ws_bytes, st); });
 }
 int circl_hip_kyber_decaps_dev(int param, const uint8_t *d_dk, const uint8_t *d_ct, uint8_t *d_ss, size_t n, void *d_ws, size_t ws_bytes,
                                void *stream) {
-    KEM_DISPATCH((decaps_dev_impl<2, true>(d_dk, d_ct, d_ss, nullptr, n, d_ws, ws_bytes, st)),
-                 (decaps_dev_impl<3, true>(d_dk, d_ct, d_ss, nullptr, n, d_ws, ws_bytes, st)),
-                 (decaps_dev_impl<4, true>(d_dk, d_ct, d_ss, nullptr, n, d_ws, ws_bytes, st)));
+    return kem_dev_call(param, stream, [&](auto k, hipStream_t st) { return decaps_dev_impl<k.value, true>(d_dk, d_ct, d_ss, nullptr, n, d_ws, ws_bytes, st); });
 }
 int circl_hip_kyber_keygen(int param, const uint8_t *seed64, uint8_t *ek, uint8_t *dk, size_t n, int device) {
-    const size_t EK = circl_hip_mlkem_ek_size(param), DK = circl_hip_mlkem_dk_size(param);
-    if (!EK) return CIRCL_HIP_EPARAM;
-    return shard(n, device, [&](int dev, size_t lo, size_t cnt) {
-        return run_pipeline(dev, cnt, {{seed64 + lo * 64, 64, true}}, {}, {{ek + lo * EK, EK}, {dk + lo * DK, DK, true}}, kem_ws_fn(), kem_opts(),
-                            [&](Chunk &c) { return circl_hip_kyber_keygen_dev(param, c.in[0], c.out[0], c.out[1], c.cnt, c.ws, c.ws_bytes, c.st); });
-    });
+    return kem_keygen_host(circl_hip_kyber_keygen_dev, param, seed64, ek, dk, n, device);
 }
 int circl_hip_kyber_encaps(int param, const uint8_t *ek, const uint8_t *seed32, uint8_t *ct, uint8_t *ss, size_t n, int device) {
     const size_t EK = circl_hip_mlkem_ek_size(param), CT = circl_hip_mlkem_ct_size(param);
     if (!EK) return CIRCL_HIP_EPARAM;
     return shard(n, device, [&](int dev, size_t lo, size_t cnt) {
-        return run_pipeline(dev, cnt, {{ek + lo * EK, EK}, {seed32 + lo * 32, 32, true}}, {}, {{ct + lo * CT, CT}, {ss + lo * 32, 32, true}}, kem_ws_fn(),
+        return run_pipeline(dev, cnt, kem_enc_ins(ek + lo * EK, seed32 + lo * 32, EK), {}, {{ct + lo * CT, CT}, {ss + lo * 32, 32, true}}, kem_ws_fn(),
                             kem_opts(),
                             [&](Chunk &c) { return circl_hip_kyber_encaps_dev(param, c.in[0], c.in[1], c.out[0], c.out[1], c.cnt, c.ws, c.ws_bytes, c.st); });
     });
@@ -1024,7 +940,7 @@ int circl_hip_kyber_decaps(int param, const uint8_t *dk, const uint8_t *ct, uint
     const size_t DK = circl_hip_mlkem_dk_size(param), CT = circl_hip_mlkem_ct_size(param);
     if (!DK) return CIRCL_HIP_EPARAM;
     return shard(n, device, [&](int dev, size_t lo, size_t cnt) {
-        return run_pipeline(dev, cnt, {{dk + lo * DK, DK, true}, {ct + lo * CT, CT}}, {}, {{ss + lo * 32, 32, true}}, kem_ws_fn(), kem_opts(),
+        return run_pipeline(dev, cnt, kem_dec_ins(dk + lo * DK, ct + lo * CT, DK, CT), {}, {{ss + lo * 32, 32, true}}, kem_ws_fn(), kem_opts(),
                             [&](Chunk &c) { return circl_hip_kyber_decaps_dev(param, c.in[0], c.in[1], c.out[0], c.cnt, c.ws, c.ws_bytes, c.st); });
     });
 }

@@ -64,6 +64,21 @@ def test_mlkem_table_reports_a_non_canonical_public_key_per_item():
     assert st.tolist() == [0, 1, 0, 1, 0] and not ct[st == 1].any() and not ss[st == 1].any()
 
 
+@pytest.mark.parametrize("env_extra", [{}, {"CIRCL_HIP_KEM_CHAIN": "0", "CIRCL_HIP_KEM_CHAIN_ENCAPS": "0"}], ids=["one-launch", "three-launches"])
+def test_mlkem_table_layout_at_its_padding_edges(env_extra):
+    # a table's A^T rows are padded to whole groups of G entries (16 / 7 / 4) and H(ek) and the status bytes lie behind them: G - 1, G and
+    # G + 1 entries, the last entry and entry 0 in use, a private key with a broken stored hash, a non-canonical public key -- through
+    # the per-call key tables and the resident ones, with and without an index vector, on both bodies of the resident form (the worker)
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    env.update(env_extra)
+    r = subprocess.run([sys.executable, os.path.join(root, "tests", "kem_table_edges_worker.py")], cwd=root, env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "kem table edges ok" in r.stdout, r.stdout[-1500:] + r.stderr[-4000:]
+
+
 @pytest.mark.parametrize("param", [44, 65, 87, 3])
 def test_mldsa_table_matches_the_oracle_call_after_call(param):
     from circl_amd import hostapi
