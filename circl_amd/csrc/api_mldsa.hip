@@ -18,53 +18,105 @@ using circl::mlkem::KM_SHARED;
 
 bool is_r3(int param) { return param == 2 || param == 3 || param == 5; }
 
+// The one switch over the parameter set: f(std::integral_constant<int, MODE>{}) with MODE = 44 / 65 / 87 (ML-DSA) or 2 / 3 / 5 (round-3
+// Dilithium), `unknown` for any other param.
+template <class F, class R = decltype(std::declval<F &>()(std::integral_constant<int, 44>{}))>
+R dsa_with_mode(int param, F &&f, R unknown = CIRCL_HIP_EPARAM) {
+    switch (param) {
+    case 44: return f(std::integral_constant<int, 44>{});
+    case 65: return f(std::integral_constant<int, 65>{});
+    case 87: return f(std::integral_constant<int, 87>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 3: return f(std::integral_constant<int, 3>{});
+    case 5: return f(std::integral_constant<int, 5>{});
+    }
+    return unknown;
+}
+// ... behind what every *_dev entry point asks first: is there a device at all
+template <class F> int dsa_dev_call(int param, void *stream, F &&f) {
+    if (ndev() <= 0) return CIRCL_HIP_ENODEV;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    return dsa_with_mode(param, [&](auto m) -> int { return f(m, st); });
+}
+
+// The messages of a batch: ragged blobs with n + 1 absolute offsets each; no context blob = no contexts (and no offsets);
+// internal != 0: the message is M' already (Sign_internal / Verify_internal).
+struct DsaMsgs {
+    const uint8_t *msg_blob;
+    const uint64_t *msg_off;
+    const uint8_t *ctx_blob;
+    const uint64_t *ctx_off;
+    int internal;
+    DsaMsgs from(size_t lo) const { return {msg_blob, msg_off + lo, ctx_blob, ctx_blob ? ctx_off + lo : nullptr, internal}; }  // items [lo, ...)
+    // what mu is hashed over: round 3 has no M' framing, mu = CRH(tr || msg)
+    template <int MODE> DsaMsgs for_mu() const { return {msg_blob, msg_off, ctx_blob, ctx_off, circl::mldsa::DP<MODE>::NIST ? internal : 1}; }
+    // the host-buffer forms stage the two blobs of a chunk (blob 0: messages, blob 1: contexts) and launch on the staged ones
+    std::vector<HBlob> blobs() const { return {{msg_blob, msg_off}, {ctx_blob, ctx_blob ? ctx_off : nullptr}}; }
+    static DsaMsgs staged(const Chunk &c, int internal) { return {c.blob[0], c.off[0], c.blob[1], c.off[1], internal}; }
+};
+
 // ---- device-resident ML-DSA verify ------------------------------------------------------------
 
-// ML-DSA verify / keygen workspace: per-item intermediates, the ticket counter, and one 48 KB scratch slice
-// (the sampled matrix rows) per resident workgroup of the persistent kernel.
 int dsa_blocks_per_cu() { return kMaxBlocksPerCU; }
-template <int MODE> size_t mldsa_groups(size_t n) { return (n + circl::mldsa::DG<MODE>::IT - 1) / circl::mldsa::DG<MODE>::IT; }
-// scratch slices the workspace provides: enough for any visible device
-template <int MODE> size_t mldsa_scratch_blocks(size_t n) {
-    return std::min<size_t>(mldsa_groups<MODE>(n), (size_t)max_cu_count() * dsa_blocks_per_cu());
-}
-template <int MODE> size_t mldsa_item_ws_bytes(size_t n) {
-    using G = circl::mldsa::DG<MODE>;
-    return up256(n * G::MUW1) + up256(n * circl::mldsa::kBallStateBytes) + up256(n);
-}
 // up to here a lane per item leaves the SIMDs at or below one wavefront each: hash chains go on lane pairs (keccak_f1600_split)
 constexpr size_t kMidBatch = size_t(1) << 14;
 constexpr size_t kLongCtlBytes = (sizeof(circl::mldsa::LongCtl) + 255) & ~size_t(255);
-template <int MODE> size_t mldsa_ws_bytes(size_t n) {
-    return mldsa_item_ws_bytes<MODE>(n) + 256 + mldsa_scratch_blocks<MODE>(n) * circl::mldsa::DG<MODE>::SCRATCH_BYTES + 256 + kLongCtlBytes;  // + tr of a shared key + long-message list
-}
+// The carving of a ML-DSA verify / keygen / public-from-private workspace (one definition for the size query and for the launches):
+// per-item intermediates, the ticket counter, one 48 KB scratch slice (the sampled matrix rows) per resident workgroup of the
+// persistent kernel -- enough for any visible device --, tr of a shared key and the list of long messages.
+template <int MODE> struct DsaWs {
+    using G = circl::mldsa::DG<MODE>;
+    uint8_t *base;
+    size_t groups, slices;  // workgroups' worth of items (IT per group); scratch slices the workspace provides
+    size_t o_ball, o_fail, o_work, o_scratch, o_tr, o_long, total;
+    DsaWs(void *ws, size_t n) : base(static_cast<uint8_t *>(ws)), groups((n + G::IT - 1) / G::IT) {
+        slices = std::min<size_t>(groups, (size_t)max_cu_count() * dsa_blocks_per_cu());
+        size_t o = up256(n * G::MUW1);  // (item slot 0 lies at the base)
+        auto take = [&](size_t bytes) { const size_t at = o; o += bytes; return at; };
+        o_ball = take(up256(n * circl::mldsa::kBallStateBytes));
+        o_fail = take(up256(n));
+        o_work = take(256);
+        o_scratch = take(slices * G::SCRATCH_BYTES);
+        o_tr = take(256);
+        o_long = take(kLongCtlBytes);
+        total = o;
+    }
+    uint8_t *muw1() const { return base; }  // verify: mu || w1 per item; key generation: the expanded seeds
+    uint8_t *ball() const { return base + o_ball; }
+    uint8_t *fail() const { return base + o_fail; }
+    unsigned *work() const { return reinterpret_cast<unsigned *>(base + o_work); }
+    uint8_t *scratch() const { return base + o_scratch; }
+    uint8_t *tr() const { return base + o_tr; }
+    circl::mldsa::LongCtl *lctl() const { return reinterpret_cast<circl::mldsa::LongCtl *>(base + o_long); }
+    bool slice_per_group() const { return groups <= slices; }  // the one-launch routes write item t's rows into slice t / IT
+};
+template <int MODE> size_t mldsa_ws_bytes(size_t n) { return DsaWs<MODE>(nullptr, n).total; }
 // mu of the batch's long messages ahead of the per-lane kernels (mldsa_kernels.h, kLongMsg): scan, then two messages per wavefront.
 // The two halves are separate so that a small verification batch can run the second one beside its other kernels (SideStream).
-inline int mldsa_long_scan(const uint64_t *msg_off, const uint8_t *ctx_blob, const uint64_t *ctx_off, int internal, circl::mldsa::LongCtl *ctl, size_t n,
-                           hipStream_t st) {
+inline int mldsa_long_scan(const DsaMsgs &m, circl::mldsa::LongCtl *ctl, size_t n, hipStream_t st) {
     using namespace circl::mldsa;
     HIP_TRY(hipMemsetAsync(ctl, 0, 256, st));
-    hipLaunchKernelGGL(mldsa_long_scan_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, msg_off, ctx_blob, ctx_off, internal, n, ctl);
+    hipLaunchKernelGGL(mldsa_long_scan_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, m.msg_off, m.ctx_blob, m.ctx_off, m.internal, n, ctl);
     HIP_TRY(hipGetLastError());
     return CIRCL_HIP_OK;
 }
 template <int TRW>
-int mldsa_long_mu(const uint8_t *tr_base, size_t tr_stride, KeyIdx key_idx, const uint8_t *pk, size_t pk_stride, int pk_words,
-                  const uint8_t *msg_blob, const uint64_t *msg_off, const uint8_t *ctx_blob, const uint64_t *ctx_off, int internal, uint8_t *mu_out,
-                  size_t mu_stride, const circl::mldsa::LongCtl *ctl, size_t n, hipStream_t st) {
+int mldsa_long_mu(const uint8_t *tr_base, size_t tr_stride, KeyIdx key_idx, const uint8_t *pk, size_t pk_stride, int pk_words, const DsaMsgs &m,
+                  uint8_t *mu_out, size_t mu_stride, const circl::mldsa::LongCtl *ctl, size_t n, hipStream_t st) {
     using namespace circl::mldsa;
     const unsigned grid = (unsigned)std::min<size_t>((std::min<size_t>(n, kLongCap) + 1) / 2, (size_t)cu_count() * 8);
-    hipLaunchKernelGGL(mldsa_mu_long_kernel<TRW>, dim3(grid), dim3(64), 0, st, tr_base, tr_stride, key_idx, pk, pk_stride, pk_words, msg_blob, msg_off,
-                       ctx_blob, ctx_off, internal, mu_out, mu_stride, ctl);
+    hipLaunchKernelGGL(mldsa_mu_long_kernel<TRW>, dim3(grid), dim3(64), 0, st, tr_base, tr_stride, key_idx, pk, pk_stride, pk_words, m.msg_blob, m.msg_off,
+                       m.ctx_blob, m.ctx_off, m.internal, mu_out, mu_stride, ctl);
     HIP_TRY(hipGetLastError());
     return CIRCL_HIP_OK;
 }
-template <int TRW>
-int mldsa_long_prepass(const uint8_t *tr_base, size_t tr_stride, KeyIdx key_idx, const uint8_t *pk, size_t pk_stride, int pk_words,
-                       const uint8_t *msg_blob, const uint64_t *msg_off, const uint8_t *ctx_blob, const uint64_t *ctx_off, int internal, uint8_t *mu_out,
-                       size_t mu_stride, circl::mldsa::LongCtl *ctl, size_t n, hipStream_t st) {
-    if (int rc = mldsa_long_scan(msg_off, ctx_blob, ctx_off, internal, ctl, n, st)) return rc;
-    return mldsa_long_mu<TRW>(tr_base, tr_stride, key_idx, pk, pk_stride, pk_words, msg_blob, msg_off, ctx_blob, ctx_off, internal, mu_out, mu_stride, ctl, n, st);
+// ... both halves in a row, for a signing batch: tr lies in the private keys, 64 bytes in, `sk_stride` apart (0 = one key for all)
+template <int MODE>
+int mldsa_sign_long_prepass(const uint8_t *sk, size_t sk_stride, KeyIdx kx, const DsaMsgs &m, uint8_t *mr, circl::mldsa::LongCtl *ctl, size_t n,
+                            hipStream_t st) {
+    const DsaMsgs mm = m.for_mu<MODE>();
+    if (int rc = mldsa_long_scan(mm, ctl, n, st)) return rc;
+    return mldsa_long_mu<circl::mldsa::DP<MODE>::TR / 8>(sk + 64, sk_stride, kx, nullptr, 0, 0, mm, mr, 128, ctl, n, st);
 }
 // One of the library's auxiliary streams borrowed for the length of a call: begin() orders it after what the caller's stream
 // holds so far, join() orders the caller's stream after it; the destructor joins on every path that did not (error returns),
@@ -105,11 +157,25 @@ template <class Kern> unsigned dsa_resident_blocks(Kern kern, int lds_bytes) {
     const unsigned occ = resident_blocks(kern, lds_bytes);  // CUs of the current device * min(occupancy, kMaxBlocksPerCU)
     return std::min<unsigned>(occ, (unsigned)(cu_count() * dsa_blocks_per_cu()));
 }
-// key-table cache behind the verify workspace: packed A rows (whole groups of IT entries) and a 64-byte tr slot per entry
-template <int MODE> size_t mldsa_table_bytes(size_t nkeys) {
+// A public-key table: packed A rows (whole groups of IT entries), then a 64-byte tr slot per entry.  The ONE place that knows this
+// layout: the cache behind the verify workspace of the per-call key tables and the memory of the resident ones (keytable.h) are
+// both read through this view.
+template <int MODE> struct DsaTable {
     using G = circl::mldsa::DG<MODE>;
-    const size_t padded = (nkeys + G::IT - 1) / G::IT * G::IT;
-    return up256(padded * G::STREAMS * circl::mldsa::kPackedRowDwords * 4) + up256(nkeys * 64);
+    uint8_t *base;
+    size_t nkeys, padded;
+    DsaTable(void *b, size_t nk) : base(static_cast<uint8_t *>(b)), nkeys(nk), padded((nk + G::IT - 1) / G::IT * G::IT) {}
+    size_t rows_bytes() const { return up256(padded * G::STREAMS * circl::mldsa::kPackedRowDwords * 4); }
+    uint32_t *rows() const { return reinterpret_cast<uint32_t *>(base); }
+    uint8_t *tr() const { return base + rows_bytes(); }
+    size_t bytes() const { return rows_bytes() + up256(nkeys * 64); }  // (asked of a view without memory, too)
+};
+// the ONE pair of launches that fills a table: tr and ExpandA of every entry of `keys` (nkeys packed public keys on the device)
+template <int MODE> void dsa_table_fill(const DsaTable<MODE> &tb, const uint8_t *keys, hipStream_t st) {
+    using G = circl::mldsa::DG<MODE>;
+    using namespace circl::mldsa;
+    hipLaunchKernelGGL(mldsa_tr_table_kernel<MODE>, dim3((unsigned)((tb.nkeys + 255) / 256)), dim3(256), 0, st, keys, tb.tr(), tb.nkeys);
+    hipLaunchKernelGGL(mldsa_expand_keys_kernel<MODE>, dim3((unsigned)(tb.padded / G::IT)), dim3(64), G::LDS_FIFO, st, keys, tb.rows(), tb.nkeys);
 }
 
 // KM_ITEM: every item its own public key.  KM_SHARED: n signatures under ONE public key (the reference's parsed-key case,
@@ -126,8 +192,7 @@ inline size_t dsa_chain_batch(bool resident = true, int k = 6) {
     return lg <= 0 ? size_t(0) : size_t(1) << lg;
 }
 template <int MODE, int KM>
-int mldsa_verify_dev_impl(const uint8_t *pk, size_t nkeys, const uint32_t *key_idx, const uint8_t *sig, const uint8_t *msg_blob,
-                          const uint64_t *msg_off, const uint8_t *ctx_blob, const uint64_t *ctx_off, int internal, uint8_t *ok, size_t n,
+int mldsa_verify_dev_impl(const uint8_t *pk, size_t nkeys, const uint32_t *key_idx, const uint8_t *sig, const DsaMsgs &m, uint8_t *ok, size_t n,
                           void *ws, size_t ws_bytes, hipStream_t st, const circl_hip_keytable *cached = nullptr) {
     // cached (KM_KEYED only): a key table that lives across calls (keytable.h) -- pk, the expanded rows and tr come from it, the
     // workspace needs no table tail, and key_idx == nullptr means entry 0 for every item
@@ -136,75 +201,65 @@ int mldsa_verify_dev_impl(const uint8_t *pk, size_t nkeys, const uint32_t *key_i
     if (n == 0) return CIRCL_HIP_OK;
     if (KM == KM_KEYED && nkeys == 0) return CIRCL_HIP_EPARAM;
     if (cached) pk = cached->d_keys;
-    const size_t need = mldsa_ws_bytes<MODE>(n) + (KM == KM_KEYED && !cached ? mldsa_table_bytes<MODE>(nkeys) : 0);
+    const DsaWs<MODE> w(ws, n);
+    const size_t need = w.total + (KM == KM_KEYED && !cached ? DsaTable<MODE>(nullptr, nkeys).bytes() : 0);
     if (ws_bytes < need || !aligned<16>(ws, pk) || !aligned<4>(key_idx)) return CIRCL_HIP_EWORKSPACE;
+    // KM_KEYED: the resident table's memory, or the cache behind the per-item workspace, filled below
+    const DsaTable<MODE> tb(cached ? cached->d_table : w.base + w.total, nkeys);
     const KeyIdx kx{KM == KM_KEYED ? key_idx : nullptr, nkeys ? (uint32_t)(nkeys - 1) : 0u};  // a device index vector is bounded to the table on every read
-    uint8_t *muw1 = static_cast<uint8_t *>(ws);
-    uint8_t *ball = muw1 + up256(n * G::MUW1);
-    uint8_t *fail = ball + up256(n * kBallStateBytes);
-    unsigned *work = reinterpret_cast<unsigned *>(muw1 + mldsa_item_ws_bytes<MODE>(n));
-    uint8_t *scratch = reinterpret_cast<uint8_t *>(work) + 256;
-    uint8_t *tr = scratch + mldsa_scratch_blocks<MODE>(n) * G::SCRATCH_BYTES;  // shared key: 64 bytes behind the scratch slices
-    LongCtl *lctl = reinterpret_cast<LongCtl *>(tr + 256);
-    uint32_t *key_rows = nullptr;
+    uint8_t *muw1 = w.muw1(), *ball = w.ball(), *fail = w.fail();
+    LongCtl *lctl = w.lctl();
+    const uint32_t *key_rows = nullptr;
     const uint8_t *tr_arg = nullptr;
     if (KM == KM_KEYED && cached && n <= dsa_chain_batch()) {
         // a resident key table, a small batch: the whole verification of an item in ONE launch (mldsa_verify_chain_kernel)
-        const size_t padded = (nkeys + G::IT - 1) / G::IT * G::IT;
-        const uint32_t *rows = reinterpret_cast<const uint32_t *>(cached->d_table);
-        const uint8_t *key_tr = cached->d_table + up256(padded * G::STREAMS * kPackedRowDwords * 4);
         ProfScope ps(CIRCL_HIP_KERNEL_MLDSA_VERIFY, st);
         circl::TailFlag tail{nullptr, nullptr, 0};  // (the whole call is this ONE launch and verification holds no secret: a coalesced batch's flag may ride on it)
         take_tail_flag(&tail.flag, &tail.count, &tail.value);
-        hipLaunchKernelGGL(mldsa_verify_chain_kernel<MODE>, dim3((unsigned)n), dim3((DP<MODE>::K + 1) * 64), 0, st, pk, kx, rows, key_tr, sig, msg_blob,
-                           msg_off, ctx_blob, ctx_off, internal, ok, n, (uint8_t *)nullptr, (size_t)G::PK, tail);
+        hipLaunchKernelGGL(mldsa_verify_chain_kernel<MODE>, dim3((unsigned)n), dim3((DP<MODE>::K + 1) * 64), 0, st, pk, kx, tb.rows(), tb.tr(), sig,
+                           m.msg_blob, m.msg_off, m.ctx_blob, m.ctx_off, m.internal, ok, n, (uint8_t *)nullptr, (size_t)G::PK, tail);
         HIP_TRY(hipGetLastError());
         return CIRCL_HIP_OK;
     }
     // (the route writes item t's rows into scratch slice t / IT: only while the workspace holds a slice per IT items -- a
     // CIRCL_HIP_DSA_CHAIN_ITEM beyond the slices the workspace guarantees falls through to the scratch routes)
-    if ((KM == KM_ITEM || KM == KM_SHARED) && n <= dsa_chain_batch(false, DP<MODE>::K) && mldsa_groups<MODE>(n) <= mldsa_scratch_blocks<MODE>(n)) {
+    if ((KM == KM_ITEM || KM == KM_SHARED) && n <= dsa_chain_batch(false, DP<MODE>::K) && w.slice_per_group()) {
         // every item under its own, unparsed key (or all under ONE unparsed key: stride 0), a small batch: the same kernel with tr and
         // the matrix expansion inside the workgroup (the rows of item t in its part of scratch slice t / IT: the workspace holds a
         // slice per IT items at these sizes)
         ProfScope ps(CIRCL_HIP_KERNEL_MLDSA_VERIFY, st);
         hipLaunchKernelGGL((mldsa_verify_chain_kernel<MODE, false>), dim3((unsigned)n), dim3((DP<MODE>::K + 2) * 64), 0, st, pk, KeyIdx{},
-                           (const uint32_t *)nullptr, (const uint8_t *)nullptr, sig, msg_blob, msg_off, ctx_blob, ctx_off, internal, ok, n, scratch,
-                           KM == KM_SHARED ? size_t(0) : (size_t)G::PK);
+                           (const uint32_t *)nullptr, (const uint8_t *)nullptr, sig, m.msg_blob, m.msg_off, m.ctx_blob, m.ctx_off, m.internal, ok, n,
+                           w.scratch(), KM == KM_SHARED ? size_t(0) : (size_t)G::PK);
         HIP_TRY(hipGetLastError());
         return CIRCL_HIP_OK;
     }
     SideStream side;  // (declared ahead of every early return below: its destructor joins)
-    HIP_TRY(hipMemsetAsync(work, 0, 256, st));
+    HIP_TRY(hipMemsetAsync(w.work(), 0, 256, st));
     const unsigned hb = (unsigned)((n + 255) / 256);
     if (KM == KM_KEYED) {
-        const size_t padded = (nkeys + G::IT - 1) / G::IT * G::IT;
-        key_rows = reinterpret_cast<uint32_t *>(cached ? cached->d_table : muw1 + mldsa_ws_bytes<MODE>(n));
-        uint8_t *key_tr = reinterpret_cast<uint8_t *>(key_rows) + up256(padded * G::STREAMS * kPackedRowDwords * 4);
-        tr_arg = key_tr;
+        key_rows = tb.rows();
+        tr_arg = tb.tr();
         if (!cached) {
             ProfScope ps(CIRCL_HIP_KERNEL_MLDSA_KEYTABLE, st);
-            hipLaunchKernelGGL(mldsa_tr_table_kernel<MODE>, dim3((unsigned)((nkeys + 255) / 256)), dim3(256), 0, st, pk, key_tr, nkeys);
-            hipLaunchKernelGGL(mldsa_expand_keys_kernel<MODE>, dim3((unsigned)(padded / G::IT)), dim3(64), G::LDS_FIFO, st, pk, key_rows, nkeys);
+            dsa_table_fill(tb, pk, st);
         }
     }
     {
         ProfScope ps(CIRCL_HIP_KERNEL_MLDSA_HASH, st);
-        const int internal_eff = DP<MODE>::NIST ? internal : 1;  // round 3: mu = CRH(tr || msg)
-        if (int rc = mldsa_long_scan(msg_off, ctx_blob, ctx_off, internal_eff, lctl, n, st)) return rc;
+        const DsaMsgs mm = m.for_mu<MODE>();
+        if (int rc = mldsa_long_scan(mm, lctl, n, st)) return rc;
         // small batches: every mu comes from the cooperative pre-pass (kSmallMu), and nothing before the final hash reads it --
         // so tr and mu run on a side stream next to SampleInBall's sponge and the verify kernel (n=1: ~75 us off the chain)
         hipStream_t mu_st = st;
         if (n <= kSmallMu && side.begin(st)) mu_st = side.side;
         if (KM == KM_SHARED) {
-            hipLaunchKernelGGL(mldsa_tr_kernel<MODE>, dim3(1), dim3(64), 0, mu_st, pk, tr);
-            tr_arg = tr;
+            hipLaunchKernelGGL(mldsa_tr_kernel<MODE>, dim3(1), dim3(64), 0, mu_st, pk, w.tr());
+            tr_arg = w.tr();
         }
         {
-            const int rc = tr_arg ? mldsa_long_mu<DP<MODE>::TR / 8>(tr_arg, kx ? 64 : 0, kx, nullptr, 0, 0, msg_blob, msg_off, ctx_blob, ctx_off,
-                                                                    internal_eff, muw1, G::MUW1, lctl, n, mu_st)
-                                  : mldsa_long_mu<DP<MODE>::TR / 8>(nullptr, 0, KeyIdx{}, pk, G::PK, G::PK / 8, msg_blob, msg_off, ctx_blob, ctx_off, internal_eff,
-                                                                    muw1, G::MUW1, lctl, n, mu_st);
+            const int rc = tr_arg ? mldsa_long_mu<DP<MODE>::TR / 8>(tr_arg, kx ? 64 : 0, kx, nullptr, 0, 0, mm, muw1, G::MUW1, lctl, n, mu_st)
+                                  : mldsa_long_mu<DP<MODE>::TR / 8>(nullptr, 0, KeyIdx{}, pk, G::PK, G::PK / 8, mm, muw1, G::MUW1, lctl, n, mu_st);
             if (rc) return rc;
         }
         // (with the side stream open, prep never takes its own mu path: n <= kSmallMu means every mu is pre-made, or -- more than
@@ -216,15 +271,14 @@ int mldsa_verify_dev_impl(const uint8_t *pk, size_t nkeys, const uint32_t *key_i
             tr_arg = ball;
             tr_stride = kBallStateBytes;
         }
-        hipLaunchKernelGGL(mldsa_prep_kernel<MODE>, dim3(hb), dim3(256), 0, st, pk, sig, msg_blob, msg_off, ctx_blob, ctx_off, internal, muw1, ball,
-                           fail, n, tr_arg, kx, (const LongCtl *)lctl, tr_stride);
+        hipLaunchKernelGGL(mldsa_prep_kernel<MODE>, dim3(hb), dim3(256), 0, st, pk, sig, m.msg_blob, m.msg_off, m.ctx_blob, m.ctx_off, m.internal, muw1,
+                           ball, fail, n, tr_arg, kx, (const LongCtl *)lctl, tr_stride);
     }
     {
         ProfScope ps(CIRCL_HIP_KERNEL_MLDSA_VERIFY, st);
         auto kern = mldsa_verify_kernel<MODE, 0, KM>;
-        const unsigned vb = std::min<unsigned>((unsigned)mldsa_scratch_blocks<MODE>(n), dsa_resident_blocks(kern, G::LDS_V_TOTAL));
-        hipLaunchKernelGGL(kern, dim3(vb), dim3(64), G::LDS_V_TOTAL, st, pk, sig, muw1, (const uint8_t *)ball, fail, scratch, work, n, kx,
-                           (const uint32_t *)key_rows);
+        const unsigned vb = std::min<unsigned>((unsigned)w.slices, dsa_resident_blocks(kern, G::LDS_V_TOTAL));
+        hipLaunchKernelGGL(kern, dim3(vb), dim3(64), G::LDS_V_TOTAL, st, pk, sig, muw1, (const uint8_t *)ball, fail, w.scratch(), w.work(), n, kx, key_rows);
     }
     side.join();
     {
@@ -245,15 +299,15 @@ int mldsa_keygen_dev_impl(const uint8_t *seed32, uint8_t *pk, uint8_t *sk, size_
     using Kg = circl::mldsa::KG<MODE>;
     using namespace circl::mldsa;
     if (n == 0) return CIRCL_HIP_OK;
-    if (ws_bytes < mldsa_ws_bytes<MODE>(n) || !aligned<16>(ws, seed32, pk, sk))
+    const DsaWs<MODE> w(ws, n);
+    if (ws_bytes < w.total || !aligned<16>(ws, seed32, pk, sk))
         return CIRCL_HIP_EWORKSPACE;
-    uint8_t *es = static_cast<uint8_t *>(ws);
-    unsigned *work = reinterpret_cast<unsigned *>(es + mldsa_item_ws_bytes<MODE>(n));
-    uint8_t *scratch = reinterpret_cast<uint8_t *>(work) + 256;
+    uint8_t *es = w.muw1(), *scratch = w.scratch();
+    unsigned *work = w.work();
     // small batches: the whole key generation of an item in ONE launch, a workgroup of K wavefronts per key (mldsa_keygen_chain_kernel);
     // up to 2^CIRCL_HIP_DSA_KEYGEN_CHAIN keys (0: never), and only while the workspace holds a scratch slice per IT items
     static const size_t chain_keys = [] { const int lg = env_int("CIRCL_HIP_DSA_KEYGEN_CHAIN", 9, 0, 12); return lg <= 0 ? size_t(0) : size_t(1) << lg; }();
-    if (n <= chain_keys && mldsa_groups<MODE>(n) <= mldsa_scratch_blocks<MODE>(n)) {
+    if (n <= chain_keys && w.slice_per_group()) {
         ProfScope ps(CIRCL_HIP_KERNEL_MLDSA_KEYGEN, st);
         hipLaunchKernelGGL(mldsa_keygen_chain_kernel<MODE>, dim3((unsigned)n), dim3(DP<MODE>::K * 64), 0, st, seed32, es, pk, sk, scratch, n);
         HIP_TRY(hipGetLastError());
@@ -268,7 +322,7 @@ int mldsa_keygen_dev_impl(const uint8_t *seed32, uint8_t *pk, uint8_t *sk, size_
     {
         ProfScope ps(CIRCL_HIP_KERNEL_MLDSA_KEYGEN, st);
         auto kern = mldsa_keygen_kernel<MODE>;
-        const unsigned kb = std::min<unsigned>((unsigned)mldsa_scratch_blocks<MODE>(n), dsa_resident_blocks(kern, Kg::LDS_TOTAL));
+        const unsigned kb = std::min<unsigned>((unsigned)w.slices, dsa_resident_blocks(kern, Kg::LDS_TOTAL));
         hipLaunchKernelGGL(kern, dim3(kb), dim3(64), Kg::LDS_TOTAL, st, (const uint8_t *)es, pk, sk, scratch, work, n);
     }
     {
@@ -288,62 +342,45 @@ int mldsa_public_dev_impl(const uint8_t *sk, uint8_t *pk, size_t n, void *ws, si
     using Kg = circl::mldsa::KG<MODE>;
     using namespace circl::mldsa;
     if (n == 0) return CIRCL_HIP_OK;
-    if (ws_bytes < mldsa_ws_bytes<MODE>(n) || !aligned<16>(ws, sk, pk)) return CIRCL_HIP_EWORKSPACE;
-    unsigned *work = reinterpret_cast<unsigned *>(static_cast<uint8_t *>(ws) + mldsa_item_ws_bytes<MODE>(n));
-    uint8_t *scratch = reinterpret_cast<uint8_t *>(work) + 256;
-    HIP_TRY(hipMemsetAsync(work, 0, 256, st));
+    const DsaWs<MODE> w(ws, n);
+    if (ws_bytes < w.total || !aligned<16>(ws, sk, pk)) return CIRCL_HIP_EWORKSPACE;
+    HIP_TRY(hipMemsetAsync(w.work(), 0, 256, st));
     ProfScope ps(CIRCL_HIP_KERNEL_MLDSA_KEYGEN, st);
     auto kern = mldsa_keygen_kernel<MODE, true>;
-    const unsigned kb = std::min<unsigned>((unsigned)mldsa_scratch_blocks<MODE>(n), dsa_resident_blocks(kern, Kg::LDS_TOTAL));
-    hipLaunchKernelGGL(kern, dim3(kb), dim3(64), Kg::LDS_TOTAL, st, sk, pk, (uint8_t *)nullptr, scratch, work, n);
+    const unsigned kb = std::min<unsigned>((unsigned)w.slices, dsa_resident_blocks(kern, Kg::LDS_TOTAL));
+    hipLaunchKernelGGL(kern, dim3(kb), dim3(64), Kg::LDS_TOTAL, st, sk, pk, (uint8_t *)nullptr, w.scratch(), w.work(), n);
     HIP_TRY(hipGetLastError());
     return CIRCL_HIP_OK;
 }
 
-#define DSA_SWITCH(param, CALL)      \
-    switch (param) {                 \
-    case 44: return CALL(44);        \
-    case 65: return CALL(65);        \
-    case 87: return CALL(87);        \
-    case 2: return CALL(2);          \
-    case 3: return CALL(3);          \
-    case 5: return CALL(5);          \
-    }
-
+// the resident form of a public-key table (keytable.h): the table's own memory, filled once
 template <int MODE> int mldsa_table_build(circl_hip_keytable *t, hipStream_t st) {
-    using G = circl::mldsa::DG<MODE>;
-    using namespace circl::mldsa;
-    const size_t padded = (t->nkeys + G::IT - 1) / G::IT * G::IT;
-    uint32_t *key_rows = reinterpret_cast<uint32_t *>(t->d_table);
-    uint8_t *key_tr = t->d_table + up256(padded * G::STREAMS * kPackedRowDwords * 4);
-    hipLaunchKernelGGL(mldsa_tr_table_kernel<MODE>, dim3((unsigned)((t->nkeys + 255) / 256)), dim3(256), 0, st, (const uint8_t *)t->d_keys, key_tr, t->nkeys);
-    hipLaunchKernelGGL(mldsa_expand_keys_kernel<MODE>, dim3((unsigned)(padded / G::IT)), dim3(64), G::LDS_FIFO, st, (const uint8_t *)t->d_keys, key_rows, t->nkeys);
+    dsa_table_fill(DsaTable<MODE>(t->d_table, t->nkeys), t->d_keys, st);
     HIP_TRY(hipGetLastError());
     return CIRCL_HIP_OK;
 }
 
 template <int KM>
-int mldsa_verify_dev_any(int param, const uint8_t *pk, size_t nkeys, const uint32_t *key_idx, const uint8_t *sig, const uint8_t *msg_blob,
-                         const uint64_t *msg_off, const uint8_t *ctx_blob, const uint64_t *ctx_off, int internal, uint8_t *ok, size_t n, void *ws,
-                         size_t wsb, hipStream_t st, const circl_hip_keytable *cached = nullptr) {
-    if (ndev() <= 0) return CIRCL_HIP_ENODEV;
-#define CALL(M) mldsa_verify_dev_impl<M, KM>(pk, nkeys, key_idx, sig, msg_blob, msg_off, ctx_blob, ctx_off, internal, ok, n, ws, wsb, st, cached)
-    DSA_SWITCH(param, CALL)
-#undef CALL
-    return CIRCL_HIP_EPARAM;
+int mldsa_verify_dev_any(int param, const uint8_t *pk, size_t nkeys, const uint32_t *key_idx, const uint8_t *sig, const DsaMsgs &m, uint8_t *ok, size_t n,
+                         void *ws, size_t wsb, void *stream, const circl_hip_keytable *cached = nullptr) {
+    return dsa_dev_call(param, stream, [&](auto mode, hipStream_t st) {
+        return mldsa_verify_dev_impl<mode.value, KM>(pk, nkeys, key_idx, sig, m, ok, n, ws, wsb, st, cached);
+    });
+}
+
+// verification under entry d_key_idx[i] (nullptr: entry 0) of a resident table of public keys
+int mldsa_verify_table_dev(const circl_hip_keytable *t, const uint32_t *d_key_idx, const uint8_t *d_sig, const DsaMsgs &m, uint8_t *d_ok, size_t n, void *d_ws,
+                           size_t ws_bytes, void *stream) {
+    t = keytable_here(t);
+    if (!t || t->family != 2 || t->private_keys) return CIRCL_HIP_EPARAM;
+    return mldsa_verify_dev_any<KM_KEYED>(t->param, t->d_keys, t->nkeys, d_key_idx, d_sig, m, d_ok, n, d_ws, ws_bytes, stream, t);
 }
 
 size_t mldsa_ws_any(int param, size_t n) {
-#define CALL(M) mldsa_ws_bytes<M>(n)
-    DSA_SWITCH(param, CALL)
-#undef CALL
-    return 0;
+    return dsa_with_mode(param, [&](auto mode) { return mldsa_ws_bytes<mode.value>(n); }, size_t(0));
 }
 size_t mldsa_table_any(int param, size_t nkeys) {
-#define CALL(M) mldsa_table_bytes<M>(nkeys)
-    DSA_SWITCH(param, CALL)
-#undef CALL
-    return 0;
+    return dsa_with_mode(param, [&](auto mode) { return DsaTable<mode.value>(nullptr, nkeys).bytes(); }, size_t(0));
 }
 
 // host-side context rules (mldsa65/dilithium.go:63-65, :116-118; round 3: sign.ErrContextNotSupported)
@@ -378,27 +415,26 @@ PipeOpts dsa_verify_table_opts() {
 // Host-buffer verify on one device: pk / sig rows and the message / context blobs of a chunk are staged together; the
 // kernels keep using the caller's absolute offsets through rebased blob pointers.
 template <int KM>
-int mldsa_verify_host_one(int param, int dev, const uint8_t *pk, size_t nkeys, const uint32_t *key_idx, const uint8_t *sig, const uint8_t *msg_blob,
-                          const uint64_t *msg_off, const uint8_t *ctx_blob, const uint64_t *ctx_off, int internal, uint8_t *ok, size_t n) {
+int mldsa_verify_host_one(int param, int dev, const uint8_t *pk, size_t nkeys, const uint32_t *key_idx, const uint8_t *sig, const DsaMsgs &m, uint8_t *ok,
+                          size_t n) {
     const size_t PK = circl_hip_mldsa_pk_size(param), SIG = circl_hip_mldsa_sig_size(param);
     std::vector<HIn> ins;
     if (KM == KM_ITEM) ins.push_back({pk, PK});
     else ins.push_back({pk, PK * (KM == KM_KEYED ? nkeys : 1), false, true});
     ins.push_back({sig, SIG});
     if (KM == KM_KEYED) ins.push_back({reinterpret_cast<const uint8_t *>(key_idx), 4});
-    const std::vector<HBlob> blobs = {{msg_blob, msg_off}, {ctx_blob, ctx_blob ? ctx_off : nullptr}};
     const std::vector<HOut> outs = {{ok, 1}};
     auto ws_fn = [&](size_t c) { return mldsa_ws_any(param, c) + (KM == KM_KEYED ? mldsa_table_any(param, nkeys) : 0); };
     auto launch = [&](Chunk &c) {
-        return mldsa_verify_dev_any<KM>(param, c.in[0], nkeys, KM == KM_KEYED ? reinterpret_cast<const uint32_t *>(c.in[2]) : nullptr, c.in[1], c.blob[0], c.off[0],
-                                        c.blob[1], c.off[1], internal, c.out[0], c.cnt, c.ws, c.ws_bytes, c.st);
+        return mldsa_verify_dev_any<KM>(param, c.in[0], nkeys, KM == KM_KEYED ? reinterpret_cast<const uint32_t *>(c.in[2]) : nullptr, c.in[1],
+                                        DsaMsgs::staged(c, m.internal), c.out[0], c.cnt, c.ws, c.ws_bytes, c.st);
     };
     Coalescer *co = nullptr;
-    if (KM == KM_ITEM && msg_blob && all_inputs_present(ins)) {  // circl_hip_set_coalesce: every item brings its own key, so calls of different callers mix freely
+    if (KM == KM_ITEM && m.msg_blob && all_inputs_present(ins)) {  // circl_hip_set_coalesce: every item brings its own key, so calls of different callers mix freely
         const int slot = param == 44 ? 0 : param == 65 ? 1 : param == 87 ? 2 : -1;  // (round-3 Dilithium: no slot, never coalesced)
-        co = call_coalescer(internal ? kCoDsaVerifyInternal : kCoDsaVerify, slot, dev);
+        co = call_coalescer(m.internal ? kCoDsaVerifyInternal : kCoDsaVerify, slot, dev);
     }
-    return coalesce_or_pipeline(co, dev, n, ins, blobs, outs, ws_fn, dsa_opts(size_t(1) << 13, false), launch);
+    return coalesce_or_pipeline(co, dev, n, ins, m.blobs(), outs, ws_fn, dsa_opts(size_t(1) << 13, false), launch);
 }
 
 // ---- ML-DSA sign ------------------------------------------------------------------------------
@@ -486,45 +522,67 @@ template <int MODE> size_t mldsa_sign_ws_bytes(size_t n) {
     return std::max(whole, up256(SignLayout<MODE>(h0).total) + SignLayout<MODE>(n - h0).total);
 }
 
-// Phase-split signing: rounds over the list of unsigned items (mldsa_sign_batched.h), driven by the device: the host
-// enqueues a fixed schedule of rounds plus the persistent tail and reads nothing back, so the call is asynchronous.
-// A private key prepared once (circl_hip_mldsa_privkey_new): its entry point parks the table here for the length of its call, and the
-// round signer takes A and the transformed secrets from it instead of expanding them (thread-local: calls are per thread)
-thread_local const circl_hip_keytable *tl_sign_prepared = nullptr;
-// ... and, for a table of SEVERAL prepared keys, the device array that names every item's entry (nullptr: entry 0)
-thread_local const uint32_t *tl_sign_key_idx = nullptr;
-// The host-buffer signing entry points have checked every context on the host (check_contexts == CTX_OK) before anything reaches the
-// device: no item can be "dead" (mldsa_sign_prep_kernel), so the launch that zeroes dead items' signatures is not enqueued.  Set for the
-// length of the _dev call by the host path's launch callback, on the thread that makes it.
-thread_local bool tl_sign_ctx_ok = false;
-struct SignCtxOk {
-    bool prev;
-    SignCtxOk() : prev(tl_sign_ctx_ok) { tl_sign_ctx_ok = true; }
-    ~SignCtxOk() { tl_sign_ctx_ok = prev; }
+// The table of nkeys prepared private keys (circl_hip_mldsa_privkeys_new): [A: nkeys x K L packed rows][s1-hat, s2-hat, t0-hat: nkeys x
+// (L + 2 K) packed rows][set-up scratch].  The ONE place that knows this layout: the build and the round signer read through this view.
+template <int MODE> struct DsaPrivTable {
+    using B = circl::mldsa::SB<MODE>;
+    uint8_t *base;
+    size_t nkeys;
+    DsaPrivTable(void *b, size_t nk) : base(static_cast<uint8_t *>(b)), nkeys(nk) {}
+    size_t o_sec() const { return up256(nkeys * B::A_BYTES); }
+    size_t o_scratch() const { return o_sec() + up256(nkeys * B::SEC_BYTES); }
+    uint32_t *A() const { return reinterpret_cast<uint32_t *>(base); }
+    uint32_t *sec() const { return reinterpret_cast<uint32_t *>(base + o_sec()); }
+    uint32_t *scratch() const { return reinterpret_cast<uint32_t *>(base + o_scratch()); }  // (of the build alone: counters and lists of its launches)
+    size_t bytes() const { return o_scratch() + up256(12 * nkeys) + 1024; }  // (asked of a view without memory, too)
 };
 
+// Whose keys a batch is signed with.  sk: n packed private keys, or ONE for every item (shared), or -- prepared != nullptr, which implies
+// shared -- the rows of a table of private keys prepared once: the round signer takes A and the transformed secrets from the table
+// instead of expanding them, and key_idx is the device array that names every item's entry (nullptr: entry 0).
+// ctx_checked: the host-buffer signing entry points have checked every context on the host (check_contexts == CTX_OK) before anything
+// reaches the device: no item can be "dead" (mldsa_sign_prep_kernel), so the launch that zeroes dead items' signatures is not enqueued.
+struct SignKeys {
+    const uint8_t *sk;
+    bool shared;
+    const circl_hip_keytable *prepared;
+    const uint32_t *key_idx;
+    bool ctx_checked;
+    KeyIdx kx() const { return {key_idx, prepared ? (uint32_t)(prepared->nkeys - 1) : 0u}; }  // a device index vector is bounded to the table on every read
+    size_t sk_stride(size_t sk_bytes) const { return (shared && !key_idx) ? size_t(0) : sk_bytes; }
+    SignKeys from(size_t lo, size_t sk_bytes) const {  // items [lo, ...)
+        SignKeys h = *this;
+        if (!shared) h.sk += lo * sk_bytes;
+        if (key_idx) h.key_idx += lo;
+        return h;
+    }
+};
+
+// Phase-split signing: rounds over the list of unsigned items (mldsa_sign_batched.h), driven by the device: the host
+// enqueues a fixed schedule of rounds plus the persistent tail and reads nothing back, so the call is asynchronous.
 template <int MODE>
-int mldsa_sign_batched_part(const uint8_t *sk, const uint8_t *msg_blob, const uint64_t *msg_off, const uint8_t *ctx_blob,
-                            const uint64_t *ctx_off, const uint8_t *rnd, int internal, uint8_t *sig, size_t n, void *ws, hipStream_t st,
-                            bool shared) {
+int mldsa_sign_batched_part(const SignKeys &keys, const DsaMsgs &m, const uint8_t *rnd, uint8_t *sig, size_t n, void *ws, hipStream_t st) {
     using namespace circl::mldsa;
     constexpr int K = DP<MODE>::K, L = DP<MODE>::L;
     const SignLayout<MODE> lay(n);
     if (lay.E >= (size_t(1) << kEntryShift)) return CIRCL_HIP_EPARAM;
     const int cus = cu_count();
     uint8_t *base = static_cast<uint8_t *>(ws);
+    const uint8_t *sk = keys.sk;
+    const bool shared = keys.shared;
+    const circl_hip_keytable *prep = keys.prepared;
+    const KeyIdx kx = keys.kx();
+    const size_t sk_stride = keys.sk_stride(KG<MODE>::SK);
     SignState S;
     S.shared = shared ? 1u : 0u;
-    const circl_hip_keytable *prep = shared ? tl_sign_prepared : nullptr;
-    const uint32_t *key_idx = prep ? tl_sign_key_idx : nullptr;
-    const KeyIdx kx{key_idx, prep ? (uint32_t)(prep->nkeys - 1) : 0u};  // a device index vector is bounded to the table on every read
     S.key_idx = KeyIdx{};
     S.mr = base + lay.o_mr;
     S.A = reinterpret_cast<uint32_t *>(base + lay.o_A);
     S.sec = reinterpret_cast<uint32_t *>(base + lay.o_sec);
     if (prep) {
-        S.A = reinterpret_cast<uint32_t *>(prep->d_table);
-        S.sec = reinterpret_cast<uint32_t *>(prep->d_table + up256(prep->nkeys * SB<MODE>::A_BYTES));
+        const DsaPrivTable<MODE> pt(prep->d_table, prep->nkeys);
+        S.A = pt.A();
+        S.sec = pt.sec();
         S.shared = 2u;
         S.key_idx = kx;
     }
@@ -570,21 +628,19 @@ int mldsa_sign_batched_part(const uint8_t *sk, const uint8_t *msg_blob, const ui
     static const bool one_front = env_int("CIRCL_HIP_SIGN_FRONT", 1, 0, 1) != 0;
     if (one_front && n <= kSmallMu) {
         ProfScope ps(CIRCL_HIP_KERNEL_MLDSA_HASH, st);
-        hipLaunchKernelGGL(mldsa_sign_front_kernel<MODE>, dim3((unsigned)((n + 1) / 2)), dim3(64), 0, st, sk, (shared && !key_idx) ? size_t(0) : (size_t)KG<MODE>::SK,
-                           kx, msg_blob, msg_off, ctx_blob, ctx_off, rnd, internal, S.mr, n, dead, prep ? S.attempts : nullptr, prep ? S.best : nullptr,
+        hipLaunchKernelGGL(mldsa_sign_front_kernel<MODE>, dim3((unsigned)((n + 1) / 2)), dim3(64), 0, st, sk, sk_stride,
+                           kx, m.msg_blob, m.msg_off, m.ctx_blob, m.ctx_off, rnd, m.internal, S.mr, n, dead, prep ? S.attempts : nullptr, prep ? S.best : nullptr,
                            prep ? S.list[0] : nullptr, prep ? S.count : nullptr, k0);
     } else {
         ProfScope ps(CIRCL_HIP_KERNEL_MLDSA_HASH, st);
         LongCtl *lctl = reinterpret_cast<LongCtl *>(base + lay.o_long);
-        if (int rc = mldsa_long_prepass<DP<MODE>::TR / 8>(sk + 64, (shared && !key_idx) ? 0 : KG<MODE>::SK, kx, nullptr, 0, 0, msg_blob, msg_off, ctx_blob,
-                                                          ctx_off, DP<MODE>::NIST ? internal : 1, S.mr, 128, lctl, n, st))
-            return rc;
+        if (int rc = mldsa_sign_long_prepass<MODE>(sk, sk_stride, kx, m, S.mr, lctl, n, st)) return rc;
         // (a prepared key: the prep kernel also sets up the round signer's lists -- sign_secrets_kernel has nothing else to do then)
         if (prep)
-            hipLaunchKernelGGL(mldsa_sign_prep_kernel<MODE>, dim3(nb256), dim3(256), 0, st, sk, msg_blob, msg_off, ctx_blob, ctx_off, rnd, internal,
+            hipLaunchKernelGGL(mldsa_sign_prep_kernel<MODE>, dim3(nb256), dim3(256), 0, st, sk, m.msg_blob, m.msg_off, m.ctx_blob, m.ctx_off, rnd, m.internal,
                                S.mr, n, shared ? 1 : 0, dead, (const LongCtl *)lctl, kx, S.attempts, S.best, S.list[0], S.count, k0);
         else
-            hipLaunchKernelGGL(mldsa_sign_prep_kernel<MODE>, dim3(nb256), dim3(256), 0, st, sk, msg_blob, msg_off, ctx_blob, ctx_off, rnd, internal,
+            hipLaunchKernelGGL(mldsa_sign_prep_kernel<MODE>, dim3(nb256), dim3(256), 0, st, sk, m.msg_blob, m.msg_off, m.ctx_blob, m.ctx_off, rnd, m.internal,
                                S.mr, n, shared ? 1 : 0, dead, (const LongCtl *)lctl, kx);
     }
     if (!prep) {
@@ -652,7 +708,7 @@ int mldsa_sign_batched_part(const uint8_t *sk, const uint8_t *msg_blob, const ui
                            (uint32_t *)nullptr, (uint8_t *)nullptr, shared ? 1 : 0, (const uint32_t *)(S.count + fin), kx);
         // (an item is dead only when it brings a context the scheme refuses: impossible without contexts, for the internal form, and
         // after the host path's own check)
-        if (ctx_blob && !internal && !tl_sign_ctx_ok)
+        if (m.ctx_blob && !m.internal && !keys.ctx_checked)
             hipLaunchKernelGGL(mldsa_sign_zero_dead_kernel<MODE>, dim3(nb256), dim3(256), 0, st, sig, (const uint8_t *)dead, n);
     }
     // The workspace held rho'', the NTT-domain secrets, the accepted attempts' y next to c~ (z - y = c s1) and parked
@@ -673,12 +729,9 @@ int mldsa_sign_batched_part(const uint8_t *sk, const uint8_t *msg_blob, const ui
 }
 
 template <int MODE>
-int mldsa_sign_batched(const uint8_t *sk, const uint8_t *msg_blob, const uint64_t *msg_off, const uint8_t *ctx_blob,
-                       const uint64_t *ctx_off, const uint8_t *rnd, int internal, uint8_t *sig, size_t n, void *ws, hipStream_t st,
-                       bool shared) {
+int mldsa_sign_batched(const SignKeys &keys, const DsaMsgs &m, const uint8_t *rnd, uint8_t *sig, size_t n, void *ws, hipStream_t st) {
     static const bool no_split = getenv("CIRCL_HIP_SIGN_NOSPLIT") != nullptr;  // tuning aid
-    if (n < kSignSplitMin || no_split)
-        return mldsa_sign_batched_part<MODE>(sk, msg_blob, msg_off, ctx_blob, ctx_off, rnd, internal, sig, n, ws, st, shared);
+    if (n < kSignSplitMin || no_split) return mldsa_sign_batched_part<MODE>(keys, m, rnd, sig, n, ws, st);
     constexpr size_t SK = circl::mldsa::KG<MODE>::SK, SIG = circl::mldsa::DG<MODE>::SIG;
     hipStream_t aux[2];
     if (int rc = aux_streams(current_device(), aux)) return rc;
@@ -710,11 +763,8 @@ int mldsa_sign_batched(const uint8_t *sk, const uint8_t *msg_blob, const uint64_
     };
     for (int p = 0; p < 2; p++) {
         if (note(hipStreamWaitEvent(aux[p], fork, 0), "fork")) {
-            const uint32_t *kidx = tl_sign_key_idx;  // (a table of several prepared keys: this half's slice of the index array)
-            tl_sign_key_idx = kidx ? kidx + lo[p] : nullptr;
-            const int r = mldsa_sign_batched_part<MODE>(shared ? sk : sk + lo[p] * SK, msg_blob, msg_off + lo[p], ctx_blob, ctx_off ? ctx_off + lo[p] : nullptr,
-                                                        rnd + lo[p] * 32, internal, sig + lo[p] * SIG, cnt[p], wsp[p], aux[p], shared);
-            tl_sign_key_idx = kidx;
+            // (a table of several prepared keys: the half gets its slice of the index array)
+            const int r = mldsa_sign_batched_part<MODE>(keys.from(lo[p], SK), m.from(lo[p]), rnd + lo[p] * 32, sig + lo[p] * SIG, cnt[p], wsp[p], aux[p]);
             if (r != CIRCL_HIP_OK && rc == CIRCL_HIP_OK) rc = r;
         }
         // join on EVERY path: whatever was enqueued on the library's streams is ordered before the caller's later work (the
@@ -727,18 +777,17 @@ int mldsa_sign_batched(const uint8_t *sk, const uint8_t *msg_blob, const uint64_
 }
 
 template <int MODE>
-int mldsa_sign_dev_impl(const uint8_t *sk, const uint8_t *msg_blob, const uint64_t *msg_off, const uint8_t *ctx_blob,
-                        const uint64_t *ctx_off, const uint8_t *rnd, int internal, uint8_t *sig, size_t n, void *ws, size_t ws_bytes,
-                        hipStream_t st, bool shared = false) {
+int mldsa_sign_dev_impl(const SignKeys &keys, const DsaMsgs &m, const uint8_t *rnd, uint8_t *sig, size_t n, void *ws, size_t ws_bytes, hipStream_t st) {
     using S = circl::mldsa::SG<MODE>;
     using namespace circl::mldsa;
+    const uint8_t *sk = keys.sk;
+    const bool shared = keys.shared;
     if (n == 0) return CIRCL_HIP_OK;
     if (ws_bytes < mldsa_sign_ws_bytes<MODE>(n) || !aligned<16>(ws, sk, rnd) || rnd == nullptr)
         return CIRCL_HIP_EWORKSPACE;
-    if (n >= sign_batched_min()) return mldsa_sign_batched<MODE>(sk, msg_blob, msg_off, ctx_blob, ctx_off, rnd, internal, sig, n, ws, st, shared);
+    if (n >= sign_batched_min()) return mldsa_sign_batched<MODE>(keys, m, rnd, sig, n, ws, st);
     const SignLayout<MODE> lay(n);
-    const uint32_t *key_idx = (shared && tl_sign_prepared) ? tl_sign_key_idx : nullptr;
-    const KeyIdx kx{key_idx, key_idx ? (uint32_t)(tl_sign_prepared->nkeys - 1) : 0u};
+    const KeyIdx kx = keys.kx();
     uint8_t *base = static_cast<uint8_t *>(ws);
     uint8_t *mr = base + lay.o_mr, *dead = base + lay.o_dead, *scratch = base + lay.o_scratch;
     unsigned *work = reinterpret_cast<unsigned *>(base + lay.o_work);
@@ -746,11 +795,9 @@ int mldsa_sign_dev_impl(const uint8_t *sk, const uint8_t *msg_blob, const uint64
     {
         ProfScope ps(CIRCL_HIP_KERNEL_MLDSA_HASH, st);
         LongCtl *lctl = reinterpret_cast<LongCtl *>(base + lay.o_long);
-        if (int rc = mldsa_long_prepass<DP<MODE>::TR / 8>(sk + 64, (shared && !key_idx) ? 0 : KG<MODE>::SK, kx, nullptr, 0, 0, msg_blob, msg_off, ctx_blob,
-                                                          ctx_off, DP<MODE>::NIST ? internal : 1, mr, 128, lctl, n, st))
-            return rc;
-        hipLaunchKernelGGL(mldsa_sign_prep_kernel<MODE>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, sk, msg_blob,
-                           msg_off, ctx_blob, ctx_off, rnd, internal, mr, n, shared ? 1 : 0, dead, (const LongCtl *)lctl, kx);
+        if (int rc = mldsa_sign_long_prepass<MODE>(sk, keys.sk_stride(KG<MODE>::SK), kx, m, mr, lctl, n, st)) return rc;
+        hipLaunchKernelGGL(mldsa_sign_prep_kernel<MODE>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, sk, m.msg_blob, m.msg_off, m.ctx_blob,
+                           m.ctx_off, rnd, m.internal, mr, n, shared ? 1 : 0, dead, (const LongCtl *)lctl, kx);
     }
     {
         auto kern = mldsa_sign_kernel<MODE>;
@@ -761,7 +808,7 @@ int mldsa_sign_dev_impl(const uint8_t *sk, const uint8_t *msg_blob, const uint64
         hipLaunchKernelGGL(kern, dim3(blocks), dim3(64), S::LDS_TOTAL, st, sk, (const uint8_t *)mr, sig, scratch, work,
                            (const uint32_t *)nullptr, (const uint32_t *)nullptr, n, 1u, (uint32_t *)nullptr, (uint8_t *)nullptr, shared ? 1 : 0,
                            (const uint32_t *)nullptr, kx);
-        if (ctx_blob && !internal && !tl_sign_ctx_ok)
+        if (m.ctx_blob && !m.internal && !keys.ctx_checked)
             hipLaunchKernelGGL(mldsa_sign_zero_dead_kernel<MODE>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, sig, (const uint8_t *)dead, n);
     }
     HIP_TRY(hipMemsetAsync(mr, 0, up256(128 * n), st));  // rho'' and the NTT-domain secrets do not stay behind
@@ -770,43 +817,36 @@ int mldsa_sign_dev_impl(const uint8_t *sk, const uint8_t *msg_blob, const uint64
     return CIRCL_HIP_OK;
 }
 
-int mldsa_sign_dev_any(int param, const uint8_t *sk, const uint8_t *msg_blob, const uint64_t *msg_off, const uint8_t *ctx_blob,
-                       const uint64_t *ctx_off, const uint8_t *rnd, int internal, uint8_t *sig, size_t n, void *ws, size_t wsb,
-                       hipStream_t st, bool shared = false) {
-    if (ndev() <= 0) return CIRCL_HIP_ENODEV;
-#define CALL(M) mldsa_sign_dev_impl<M>(sk, msg_blob, msg_off, ctx_blob, ctx_off, rnd, internal, sig, n, ws, wsb, st, shared)
-    DSA_SWITCH(param, CALL)
-#undef CALL
-    return CIRCL_HIP_EPARAM;
+int mldsa_sign_dev_any(int param, const SignKeys &keys, const DsaMsgs &m, const uint8_t *rnd, uint8_t *sig, size_t n, void *ws, size_t wsb, void *stream) {
+    return dsa_dev_call(param, stream, [&](auto mode, hipStream_t st) { return mldsa_sign_dev_impl<mode.value>(keys, m, rnd, sig, n, ws, wsb, st); });
+}
+// signing with entry d_key_idx[i] (nullptr: entry 0) of a table of prepared private keys
+int mldsa_sign_table_dev(const circl_hip_keytable *t, const uint32_t *d_key_idx, const DsaMsgs &m, const uint8_t *d_rnd, uint8_t *d_sig, size_t n, void *d_ws,
+                         size_t ws_bytes, void *stream, bool ctx_checked) {
+    t = keytable_here(t);
+    if (!t || t->family != 2 || !t->private_keys || !aligned<4>(d_key_idx)) return CIRCL_HIP_EPARAM;
+    return mldsa_sign_dev_any(t->param, SignKeys{t->d_keys, true, t, d_key_idx, ctx_checked}, m, d_rnd, d_sig, n, d_ws, ws_bytes, stream);
 }
 
 size_t mldsa_sign_ws_any(int param, size_t n) {
-#define CALL(M) mldsa_sign_ws_bytes<M>(n)
-    DSA_SWITCH(param, CALL)
-#undef CALL
-    return 0;
+    return dsa_with_mode(param, [&](auto mode) { return mldsa_sign_ws_bytes<mode.value>(n); }, size_t(0));
+}
+size_t mldsa_privtable_any(int param, size_t nkeys) {
+    return dsa_with_mode(param, [&](auto mode) { return DsaPrivTable<mode.value>(nullptr, nkeys).bytes(); }, size_t(0));
 }
 
-// the table of nkeys prepared private keys: [A: nkeys x K L packed rows][s1-hat, s2-hat, t0-hat: nkeys x (L + 2 K) packed rows][set-up
-// scratch], made by the round signer's own set-up kernels (every key is an "item" of an unshared batch of nkeys)
-template <int MODE> int mldsa_privkey_build(circl_hip_keytable *t, const uint8_t *sk, hipStream_t st) {
+// the resident form of a table of prepared private keys, made by the round signer's own set-up kernels (every key is an "item" of an
+// unshared batch of nkeys)
+template <int MODE> int mldsa_privkey_build(circl_hip_keytable *t, hipStream_t st) {
     using namespace circl::mldsa;
-    using B = SB<MODE>;
     constexpr int K = DP<MODE>::K, L = DP<MODE>::L;
     const size_t nk = t->nkeys;
-    const size_t o_sec = up256(nk * B::A_BYTES), o_scr = o_sec + up256(nk * B::SEC_BYTES);
-    t->table_bytes = o_scr + up256(12 * nk) + 1024;
-    if (hipMalloc(reinterpret_cast<void **>(&t->d_keys), t->keys_bytes) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void **>(&t->d_table), t->table_bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        return CIRCL_HIP_ENOMEM;
-    }
-    if (int rc = upload_secret(t->d_keys, sk, KG<MODE>::SK * nk, st)) return rc;  // (through wiped page-locked staging)
-    uint32_t *scratch = reinterpret_cast<uint32_t *>(t->d_table + o_scr);
+    const DsaPrivTable<MODE> pt(t->d_table, nk);
+    uint32_t *scratch = pt.scratch();
     SignState S{};
     S.shared = 0u;
-    S.A = reinterpret_cast<uint32_t *>(t->d_table);
-    S.sec = reinterpret_cast<uint32_t *>(t->d_table + o_sec);
+    S.A = pt.A();
+    S.sec = pt.sec();
     S.count = scratch; S.kk = scratch + 2; S.chain_done = scratch + 8; S.attempts = scratch + 64; S.best = scratch + 64 + nk; S.list[0] = scratch + 64 + 2 * nk; S.list[1] = S.list[0];
     hipLaunchKernelGGL(sign_expand_a_kernel<MODE>, dim3((unsigned)((nk * K * L + 255) / 256)), dim3(256), 0, st, (const uint8_t *)t->d_keys, S, nk);
     hipLaunchKernelGGL(sign_secrets_kernel<MODE>, dim3((unsigned)nk), dim3(64), 0, st, (const uint8_t *)t->d_keys, S, nk, 1u);
@@ -814,40 +854,37 @@ template <int MODE> int mldsa_privkey_build(circl_hip_keytable *t, const uint8_t
     return CIRCL_HIP_OK;
 }
 
-int mldsa_sign_host(int param, const uint8_t *sk, const uint8_t *msg_blob, const uint64_t *msg_off, const uint8_t *ctx_blob,
-                    const uint64_t *ctx_off, const uint8_t *rnd, int internal, uint8_t *sig, size_t n, int device, bool shared = false) {
+// deterministic signing (rnd == nullptr) through the host-buffer forms: 32 zero bytes per item, one chunk's worth, re-staged with every chunk
+std::vector<uint8_t> zero_rnd(const uint8_t *rnd, size_t n, const PipeOpts &opts) {
+    return std::vector<uint8_t>(rnd ? size_t(0) : 32 * std::min(n, opts.chunk_items), 0);
+}
+
+int mldsa_sign_host(int param, const uint8_t *sk, const DsaMsgs &m, const uint8_t *rnd, uint8_t *sig, size_t n, int device, bool shared = false) {
     const size_t SK = circl_hip_mldsa_sk_size(param), SIG = circl_hip_mldsa_sig_size(param);
     if (!SK) return CIRCL_HIP_EPARAM;
     if (n == 0) return CIRCL_HIP_OK;
-    if (!internal && check_contexts(param, ctx_blob, ctx_off, n) != CTX_OK) return CIRCL_HIP_EPARAM;  // sign.ErrContextTooLong / ErrContextNotSupported
+    if (!m.internal && check_contexts(param, m.ctx_blob, m.ctx_off, n) != CTX_OK) return CIRCL_HIP_EPARAM;  // sign.ErrContextTooLong / ErrContextNotSupported
     const PipeOpts opts = dsa_opts(size_t(1) << 13, true, /*depth=*/3);  // (each chunk's workspace is ~60 KB per item)
-    std::vector<uint8_t> zeros;
-    if (!rnd) zeros.assign(32 * std::min(n, opts.chunk_items), 0);  // deterministic signing: 32 zero bytes per item
+    const std::vector<uint8_t> zeros = zero_rnd(rnd, n, opts);
     return shard(n, device, [&](int dev, size_t lo, size_t cnt) {
         std::vector<HIn> ins;
         ins.push_back(shared ? HIn{sk, SK, true, true} : HIn{sk + lo * SK, SK, true});
         ins.push_back(rnd ? HIn{rnd + lo * 32, 32, true} : HIn{zeros.data(), zeros.size(), false, true});
-        return run_pipeline(dev, cnt, ins, {{msg_blob, msg_off + lo}, {ctx_blob, ctx_blob ? ctx_off + lo : nullptr}}, {{sig + lo * SIG, SIG}},
-                            [&](size_t c) { return mldsa_sign_ws_any(param, c); }, opts, [&](Chunk &c) {
-                                SignCtxOk checked;  // (check_contexts above)
-                                return mldsa_sign_dev_any(param, c.in[0], c.blob[0], c.off[0], c.blob[1], c.off[1], c.in[1], internal, c.out[0], c.cnt, c.ws,
-                                                          c.ws_bytes, c.st, shared);
-                            });
+        return run_pipeline(dev, cnt, ins, m.from(lo).blobs(), {{sig + lo * SIG, SIG}}, [&](size_t c) { return mldsa_sign_ws_any(param, c); }, opts, [&](Chunk &c) {
+            const SignKeys keys{c.in[0], shared, nullptr, nullptr, /*ctx_checked=*/true};  // (check_contexts above)
+            return mldsa_sign_dev_any(param, keys, DsaMsgs::staged(c, m.internal), c.in[1], c.out[0], c.cnt, c.ws, c.ws_bytes, c.st);
+        });
     }, kHeavyOneDeviceMax);
 }
 
-int mldsa_verify_host(int param, const uint8_t *pk, const uint8_t *sig, const uint8_t *msg_blob, const uint64_t *msg_off,
-                      const uint8_t *ctx_blob, const uint64_t *ctx_off, int internal, uint8_t *ok, size_t n, int device, bool shared) {
+int mldsa_verify_host(int param, const uint8_t *pk, const uint8_t *sig, const DsaMsgs &m, uint8_t *ok, size_t n, int device, bool shared) {
     const size_t PK = circl_hip_mldsa_pk_size(param), SIG = circl_hip_mldsa_sig_size(param);
     if (!PK) return CIRCL_HIP_EPARAM;
     if (n == 0) return CIRCL_HIP_OK;
-    if (!internal && check_contexts(param, ctx_blob, ctx_off, n) == CTX_UNSUPPORTED) return CIRCL_HIP_EPARAM;  // round 3: sign.ErrContextNotSupported
+    if (!m.internal && check_contexts(param, m.ctx_blob, m.ctx_off, n) == CTX_UNSUPPORTED) return CIRCL_HIP_EPARAM;  // round 3: sign.ErrContextNotSupported
     return shard(n, device, [&](int dev, size_t lo, size_t cnt) {
-        if (shared)
-            return mldsa_verify_host_one<KM_SHARED>(param, dev, pk, 1, nullptr, sig + lo * SIG, msg_blob, msg_off + lo, ctx_blob,
-                                                    ctx_blob ? ctx_off + lo : nullptr, internal, ok + lo, cnt);
-        return mldsa_verify_host_one<KM_ITEM>(param, dev, pk + lo * PK, 0, nullptr, sig + lo * SIG, msg_blob, msg_off + lo, ctx_blob,
-                                              ctx_blob ? ctx_off + lo : nullptr, internal, ok + lo, cnt);
+        if (shared) return mldsa_verify_host_one<KM_SHARED>(param, dev, pk, 1, nullptr, sig + lo * SIG, m.from(lo), ok + lo, cnt);
+        return mldsa_verify_host_one<KM_ITEM>(param, dev, pk + lo * PK, 0, nullptr, sig + lo * SIG, m.from(lo), ok + lo, cnt);
     });
 }
 
@@ -874,31 +911,31 @@ size_t circl_hip_mldsa_keyed_workspace_size(int param, size_t n, size_t nkeys) {
 int circl_hip_mldsa_verify_dev(int param, const uint8_t *d_pk, const uint8_t *d_sig, const uint8_t *d_msg_blob,
                                const uint64_t *d_msg_off, const uint8_t *d_ctx_blob, const uint64_t *d_ctx_off, uint8_t *d_ok,
                                size_t n, void *d_ws, size_t ws_bytes, void *stream) {
-    return mldsa_verify_dev_any<KM_ITEM>(param, d_pk, 0, nullptr, d_sig, d_msg_blob, d_msg_off, d_ctx_blob, d_ctx_off, 0, d_ok, n, d_ws, ws_bytes,
-                                         static_cast<hipStream_t>(stream));
+    return mldsa_verify_dev_any<KM_ITEM>(param, d_pk, 0, nullptr, d_sig, {d_msg_blob, d_msg_off, d_ctx_blob, d_ctx_off, 0}, d_ok, n, d_ws, ws_bytes, stream);
 }
 int circl_hip_mldsa_verify_shared_dev(int param, const uint8_t *d_pk, const uint8_t *d_sig, const uint8_t *d_msg_blob,
                                       const uint64_t *d_msg_off, const uint8_t *d_ctx_blob, const uint64_t *d_ctx_off, uint8_t *d_ok,
                                       size_t n, void *d_ws, size_t ws_bytes, void *stream) {
-    return mldsa_verify_dev_any<KM_SHARED>(param, d_pk, 1, nullptr, d_sig, d_msg_blob, d_msg_off, d_ctx_blob, d_ctx_off, 0, d_ok, n, d_ws, ws_bytes,
-                                           static_cast<hipStream_t>(stream));
+    return mldsa_verify_dev_any<KM_SHARED>(param, d_pk, 1, nullptr, d_sig, {d_msg_blob, d_msg_off, d_ctx_blob, d_ctx_off, 0}, d_ok, n, d_ws, ws_bytes, stream);
 }
 int circl_hip_mldsa_verify_keyed_dev(int param, const uint8_t *d_pk_table, size_t nkeys, const uint32_t *d_key_idx, const uint8_t *d_sig,
                                      const uint8_t *d_msg_blob, const uint64_t *d_msg_off, const uint8_t *d_ctx_blob, const uint64_t *d_ctx_off,
                                      uint8_t *d_ok, size_t n, void *d_ws, size_t ws_bytes, void *stream) {
-    return mldsa_verify_dev_any<KM_KEYED>(param, d_pk_table, nkeys, d_key_idx, d_sig, d_msg_blob, d_msg_off, d_ctx_blob, d_ctx_off, 0, d_ok, n, d_ws,
-                                          ws_bytes, static_cast<hipStream_t>(stream));
+    return mldsa_verify_dev_any<KM_KEYED>(param, d_pk_table, nkeys, d_key_idx, d_sig, {d_msg_blob, d_msg_off, d_ctx_blob, d_ctx_off, 0}, d_ok, n, d_ws,
+                                          ws_bytes, stream);
 }
 
-// ---- a public-key table that lives across calls (keytable.h): A and tr of every entry, once ---------------------------------------
-static int mldsa_keytable_new_one(int param, const uint8_t *pks, size_t nkeys, int device, circl_hip_keytable **out) {
-    const size_t PK = circl_hip_mldsa_pk_size(param);
+// ---- key tables that live across calls (keytable.h) --------------------------------------------------------------------------------
+// public keys: A and tr of every entry, once; private keys: A and the NTT-domain secrets of the reference's parsed PrivateKey
+// (internal/dilithium.go:149-179)
+static int mldsa_table_new_one(int param, bool private_keys, const uint8_t *keys, size_t nkeys, int device, circl_hip_keytable **out) {
     HIP_TRY(hipSetDevice(physical_device(device)));
     circl_hip_keytable *t = new (std::nothrow) circl_hip_keytable();
     if (!t) return CIRCL_HIP_ENOMEM;
-    t->magic = kKeytableMagic; t->family = 2; t->param = param; t->device = device; t->private_keys = 0; t->nkeys = nkeys; t->row = PK;
-    t->keys_bytes = up256(PK * nkeys + 16);
-    t->table_bytes = mldsa_table_any(param, nkeys);
+    t->magic = kKeytableMagic; t->family = 2; t->param = param; t->device = device; t->private_keys = private_keys ? 1 : 0; t->nkeys = nkeys;
+    t->row = private_keys ? circl_hip_mldsa_sk_size(param) : circl_hip_mldsa_pk_size(param);
+    t->keys_bytes = up256(t->row * nkeys + 16);
+    t->table_bytes = private_keys ? mldsa_privtable_any(param, nkeys) : mldsa_table_any(param, nkeys);
     hipStream_t h2d = nullptr, d2h = nullptr, st = nullptr;
     int rc = pipeline_streams(device, &h2d, &d2h, &st);
     if (rc == CIRCL_HIP_OK && (hipMalloc(reinterpret_cast<void **>(&t->d_keys), t->keys_bytes) != hipSuccess ||
@@ -906,15 +943,12 @@ static int mldsa_keytable_new_one(int param, const uint8_t *pks, size_t nkeys, i
         (void)hipGetLastError();
         rc = CIRCL_HIP_ENOMEM;
     }
-    if (rc == CIRCL_HIP_OK && hipMemcpyAsync(t->d_keys, pks, PK * nkeys, hipMemcpyHostToDevice, st) != hipSuccess) rc = CIRCL_HIP_EHIP;
-    if (rc == CIRCL_HIP_OK) {
-#define CALL(M) mldsa_table_build<M>(t, st)
-        rc = [&]() -> int {
-            DSA_SWITCH(param, CALL)
-            return CIRCL_HIP_EPARAM;
-        }();
-#undef CALL
+    if (rc == CIRCL_HIP_OK) {  // (private rows: through wiped page-locked staging)
+        if (private_keys) rc = upload_secret(t->d_keys, keys, t->row * nkeys, st);
+        else if (hipMemcpyAsync(t->d_keys, keys, t->row * nkeys, hipMemcpyHostToDevice, st) != hipSuccess) rc = CIRCL_HIP_EHIP;
     }
+    if (rc == CIRCL_HIP_OK)
+        rc = dsa_with_mode(param, [&](auto mode) { return private_keys ? mldsa_privkey_build<mode.value>(t, st) : mldsa_table_build<mode.value>(t, st); });
     if (rc == CIRCL_HIP_OK && hipStreamSynchronize(st) != hipSuccess) rc = CIRCL_HIP_EHIP;
     if (rc != CIRCL_HIP_OK) {
         (void)hipGetLastError();
@@ -927,15 +961,12 @@ static int mldsa_keytable_new_one(int param, const uint8_t *pks, size_t nkeys, i
 int circl_hip_mldsa_keytable_new(int param, const uint8_t *pks, size_t nkeys, int device, circl_hip_keytable **out) {
     if (out) *out = nullptr;
     if (!circl_hip_mldsa_pk_size(param) || !pks || !out || nkeys == 0 || nkeys > 0xffffffffull) return CIRCL_HIP_EPARAM;
-    return keytable_replicate(device, [&](int dev, circl_hip_keytable **one) { return mldsa_keytable_new_one(param, pks, nkeys, dev, one); }, out);
+    return keytable_replicate(device, [&](int dev, circl_hip_keytable **one) { return mldsa_table_new_one(param, false, pks, nkeys, dev, one); }, out);
 }
 int circl_hip_mldsa_verify_table_dev(const circl_hip_keytable *t, const uint32_t *d_key_idx, const uint8_t *d_sig, const uint8_t *d_msg_blob,
                                      const uint64_t *d_msg_off, const uint8_t *d_ctx_blob, const uint64_t *d_ctx_off, uint8_t *d_ok, size_t n, void *d_ws,
                                      size_t ws_bytes, void *stream) {
-    t = keytable_here(t);
-    if (!t || t->family != 2 || t->private_keys) return CIRCL_HIP_EPARAM;
-    return mldsa_verify_dev_any<KM_KEYED>(t->param, t->d_keys, t->nkeys, d_key_idx, d_sig, d_msg_blob, d_msg_off, d_ctx_blob, d_ctx_off, 0, d_ok, n, d_ws,
-                                          ws_bytes, static_cast<hipStream_t>(stream), t);
+    return mldsa_verify_table_dev(t, d_key_idx, d_sig, {d_msg_blob, d_msg_off, d_ctx_blob, d_ctx_off, 0}, d_ok, n, d_ws, ws_bytes, stream);
 }
 int circl_hip_mldsa_verify_table(const circl_hip_keytable *t, const uint32_t *key_idx, const uint8_t *sig, const uint8_t *msg_blob, const uint64_t *msg_off,
                                  const uint8_t *ctx_blob, const uint64_t *ctx_off, uint8_t *ok, size_t n) {
@@ -945,14 +976,14 @@ int circl_hip_mldsa_verify_table(const circl_hip_keytable *t, const uint32_t *ke
     if (n == 0) return CIRCL_HIP_OK;
     if (key_idx) TRY(check_key_idx(key_idx, n, t->nkeys));
     if (check_contexts(param, ctx_blob, ctx_off, n) == CTX_UNSUPPORTED) return CIRCL_HIP_EPARAM;
+    const DsaMsgs m{msg_blob, msg_off, ctx_blob, ctx_off, 0};
     return table_shard(t, n, [&](const circl_hip_keytable *r, size_t lo, size_t cnt) {
         // a small call joins the table's cross-caller batch (absent contexts: empty rows), whose ONE launch may raise the completion flag itself
         return table_coalesce_or_pipeline(r, cnt, {{sig ? sig + lo * SIG : nullptr, SIG}, {reinterpret_cast<const uint8_t *>(key_idx ? key_idx + lo : nullptr), size_t(4), false, false, true}},
-                                          1, {{msg_blob, msg_off + lo}, {ctx_blob, ctx_blob ? ctx_off + lo : nullptr}}, {{ok + lo, 1}},
+                                          1, m.from(lo).blobs(), {{ok + lo, 1}},
                                           [&](size_t c) { return mldsa_ws_any(param, c); }, dsa_verify_table_opts(), dsa_opts(size_t(1) << 13, false),
                                           [&](Chunk &c, const uint32_t *d_key_idx) {
-                                              return circl_hip_mldsa_verify_table_dev(r, d_key_idx, c.in[0], c.blob[0], c.off[0], c.blob[1], c.off[1], c.out[0], c.cnt, c.ws,
-                                                                                      c.ws_bytes, c.st);
+                                              return mldsa_verify_table_dev(r, d_key_idx, c.in[0], DsaMsgs::staged(c, 0), c.out[0], c.cnt, c.ws, c.ws_bytes, c.st);
                                           });
     });
 }
@@ -970,7 +1001,7 @@ int circl_hip_mldsa_verify_table_submit(const circl_hip_keytable *t, const uint3
     if (check_contexts(param, ctx_blob, ctx_off, n) == CTX_UNSUPPORTED) return CIRCL_HIP_EPARAM;
     return table_submit(t, ticket, [&](const circl_hip_keytable *, Coalescer *co, uint64_t *seq) {
         return coalesce_submit(co, n, {{sig, SIG}, {reinterpret_cast<const uint8_t *>(key_idx), size_t(4), false, false, true}},
-                               {{msg_blob, msg_off}, {ctx_blob, ctx_blob ? ctx_off : nullptr}}, {{ok, 1}}, seq, false);
+                               DsaMsgs{msg_blob, msg_off, ctx_blob, ctx_off, 0}.blobs(), {{ok, 1}}, seq, false);
     });
 }
 }  // extern "C"
@@ -981,44 +1012,19 @@ int dsa_table_async_start(const circl_hip_keytable *r, Coalescer *co, bool want_
     const size_t SIG = circl_hip_mldsa_sig_size(param);
     return coalescer_async_start(co, {{nullptr, SIG}, {nullptr, size_t(4), false, false, true}}, {{nullptr, nullptr}, {nullptr, nullptr}}, {{nullptr, 1}},
                                  [param](size_t c) { return mldsa_ws_any(param, c); }, dsa_verify_table_opts(), [r](Chunk &c) {
-                                     return circl_hip_mldsa_verify_table_dev(r, reinterpret_cast<const uint32_t *>(c.in[1]), c.in[0], c.blob[0], c.off[0], c.blob[1], c.off[1],
-                                                                             c.out[0], c.cnt, c.ws, c.ws_bytes, c.st);
+                                     return mldsa_verify_table_dev(r, reinterpret_cast<const uint32_t *>(c.in[1]), c.in[0], DsaMsgs::staged(c, 0), c.out[0], c.cnt,
+                                                                   c.ws, c.ws_bytes, c.st);
                                  }, want_eventfd);
 }
 }  // namespace host
 }  // namespace circl
 extern "C" {
 
-// ---- private keys prepared once: A and the NTT-domain secrets of the reference's parsed PrivateKey (internal/dilithium.go:149-179) ----
-static int mldsa_privkeys_new_one(int param, const uint8_t *sks, size_t nkeys, int device, circl_hip_keytable **out) {
-    const size_t SK = circl_hip_mldsa_sk_size(param);
-    HIP_TRY(hipSetDevice(physical_device(device)));
-    circl_hip_keytable *t = new (std::nothrow) circl_hip_keytable();
-    if (!t) return CIRCL_HIP_ENOMEM;
-    t->magic = kKeytableMagic; t->family = 2; t->param = param; t->device = device; t->private_keys = 1; t->nkeys = nkeys; t->row = SK;
-    t->keys_bytes = up256(SK * nkeys + 16);
-    hipStream_t h2d = nullptr, d2h = nullptr, st = nullptr;
-    int rc = pipeline_streams(device, &h2d, &d2h, &st);
-#define CALL(M) mldsa_privkey_build<M>(t, sks, st)
-    if (rc == CIRCL_HIP_OK)
-        rc = [&]() -> int {
-            DSA_SWITCH(param, CALL)
-            return CIRCL_HIP_EPARAM;
-        }();
-#undef CALL
-    if (rc == CIRCL_HIP_OK && hipStreamSynchronize(st) != hipSuccess) rc = CIRCL_HIP_EHIP;
-    if (rc != CIRCL_HIP_OK) {
-        (void)hipGetLastError();
-        circl_hip_keytable_free(t);
-        return rc;
-    }
-    *out = t;
-    return CIRCL_HIP_OK;
-}
+// ---- private keys prepared once ------------------------------------------------------------------------------------------------------
 int circl_hip_mldsa_privkeys_new(int param, const uint8_t *sks, size_t nkeys, int device, circl_hip_keytable **out) {
     if (out) *out = nullptr;
     if (!circl_hip_mldsa_sk_size(param) || !sks || !out || nkeys == 0 || nkeys >= (size_t(1) << 26)) return CIRCL_HIP_EPARAM;
-    return keytable_replicate(device, [&](int dev, circl_hip_keytable **one) { return mldsa_privkeys_new_one(param, sks, nkeys, dev, one); }, out);
+    return keytable_replicate(device, [&](int dev, circl_hip_keytable **one) { return mldsa_table_new_one(param, true, sks, nkeys, dev, one); }, out);
 }
 int circl_hip_mldsa_privkey_new(int param, const uint8_t *sk, int device, circl_hip_keytable **out) {
     return circl_hip_mldsa_privkeys_new(param, sk, 1, device, out);
@@ -1026,14 +1032,7 @@ int circl_hip_mldsa_privkey_new(int param, const uint8_t *sk, int device, circl_
 int circl_hip_mldsa_sign_table_keyed_dev(const circl_hip_keytable *t, const uint32_t *d_key_idx, const uint8_t *d_msg_blob, const uint64_t *d_msg_off,
                                          const uint8_t *d_ctx_blob, const uint64_t *d_ctx_off, const uint8_t *d_rnd, int internal, uint8_t *d_sig, size_t n,
                                          void *d_ws, size_t ws_bytes, void *stream) {
-    t = keytable_here(t);
-    if (!t || t->family != 2 || !t->private_keys || !aligned<4>(d_key_idx)) return CIRCL_HIP_EPARAM;
-    struct Park {  // (restored on every path)
-        Park(const circl_hip_keytable *p, const uint32_t *k) { tl_sign_prepared = p; tl_sign_key_idx = k; }
-        ~Park() { tl_sign_prepared = nullptr; tl_sign_key_idx = nullptr; }
-    } park(t, d_key_idx);
-    return mldsa_sign_dev_any(t->param, t->d_keys, d_msg_blob, d_msg_off, d_ctx_blob, d_ctx_off, d_rnd, internal, d_sig, n, d_ws, ws_bytes,
-                              static_cast<hipStream_t>(stream), true);
+    return mldsa_sign_table_dev(t, d_key_idx, {d_msg_blob, d_msg_off, d_ctx_blob, d_ctx_off, internal}, d_rnd, d_sig, n, d_ws, ws_bytes, stream, false);
 }
 int circl_hip_mldsa_sign_table_dev(const circl_hip_keytable *t, const uint8_t *d_msg_blob, const uint64_t *d_msg_off, const uint8_t *d_ctx_blob,
                                    const uint64_t *d_ctx_off, const uint8_t *d_rnd, int internal, uint8_t *d_sig, size_t n, void *d_ws, size_t ws_bytes,
@@ -1049,17 +1048,15 @@ int circl_hip_mldsa_sign_table_keyed(const circl_hip_keytable *t, const uint32_t
     if (key_idx) TRY(check_key_idx(key_idx, n, t->nkeys));
     if (check_contexts(param, ctx_blob, ctx_off, n) != CTX_OK) return CIRCL_HIP_EPARAM;  // sign.ErrContextTooLong / ErrContextNotSupported
     const PipeOpts opts = dsa_opts(size_t(1) << 13, true, /*depth=*/3);
-    std::vector<uint8_t> zeros;
-    if (!rnd) zeros.assign(32 * std::min(n, opts.chunk_items), 0);  // deterministic signing: 32 zero bytes per item
+    const std::vector<uint8_t> zeros = zero_rnd(rnd, n, opts);
+    const DsaMsgs m{msg_blob, msg_off, ctx_blob, ctx_off, 0};
     return table_shard(t, n, [&](const circl_hip_keytable *r, size_t lo, size_t cnt) {
         // an absent rnd is rows of zeros in a cross-caller batch and ONE row of zeros for the whole call, re-staged with every chunk, in the pipeline
         return table_coalesce_or_pipeline(r, cnt, {{rnd ? rnd + lo * 32 : nullptr, size_t(32), true, false, true}, {reinterpret_cast<const uint8_t *>(key_idx ? key_idx + lo : nullptr), size_t(4), false, false, true}},
-                                          1, {{msg_blob, msg_off + lo}, {ctx_blob, ctx_blob ? ctx_off + lo : nullptr}}, {{sig + lo * SIG, SIG}},
+                                          1, m.from(lo).blobs(), {{sig + lo * SIG, SIG}},
                                           [&](size_t c) { return mldsa_sign_ws_any(param, c); }, opts, opts,
-                                          [&](Chunk &c, const uint32_t *d_key_idx) {
-                                              SignCtxOk checked;  // (check_contexts above, by every caller of a batch)
-                                              return circl_hip_mldsa_sign_table_keyed_dev(r, d_key_idx, c.blob[0], c.off[0], c.blob[1], c.off[1], c.in[0], 0, c.out[0], c.cnt,
-                                                                                          c.ws, c.ws_bytes, c.st);
+                                          [&](Chunk &c, const uint32_t *d_key_idx) {  // (ctx_checked: check_contexts above, by every caller of a batch)
+                                              return mldsa_sign_table_dev(r, d_key_idx, DsaMsgs::staged(c, 0), c.in[0], c.out[0], c.cnt, c.ws, c.ws_bytes, c.st, true);
                                           }, {{size_t(0), HIn{zeros.data(), zeros.size(), false, true}}});
     }, kHeavyOneDeviceMax);
 }
@@ -1070,15 +1067,15 @@ int circl_hip_mldsa_sign_table(const circl_hip_keytable *t, const uint8_t *msg_b
 
 int circl_hip_mldsa_verify(int param, const uint8_t *pk, const uint8_t *sig, const uint8_t *msg_blob, const uint64_t *msg_off,
                            const uint8_t *ctx_blob, const uint64_t *ctx_off, uint8_t *ok, size_t n, int device) {
-    return mldsa_verify_host(param, pk, sig, msg_blob, msg_off, ctx_blob, ctx_off, 0, ok, n, device, false);
+    return mldsa_verify_host(param, pk, sig, {msg_blob, msg_off, ctx_blob, ctx_off, 0}, ok, n, device, false);
 }
 int circl_hip_mldsa_verify_internal(int param, const uint8_t *pk, const uint8_t *sig, const uint8_t *msg_blob,
                                     const uint64_t *msg_off, uint8_t *ok, size_t n, int device) {
-    return mldsa_verify_host(param, pk, sig, msg_blob, msg_off, nullptr, nullptr, 1, ok, n, device, false);
+    return mldsa_verify_host(param, pk, sig, {msg_blob, msg_off, nullptr, nullptr, 1}, ok, n, device, false);
 }
 int circl_hip_mldsa_verify_shared(int param, const uint8_t *pk, const uint8_t *sig, const uint8_t *msg_blob, const uint64_t *msg_off,
                                   const uint8_t *ctx_blob, const uint64_t *ctx_off, uint8_t *ok, size_t n, int device) {
-    return mldsa_verify_host(param, pk, sig, msg_blob, msg_off, ctx_blob, ctx_off, 0, ok, n, device, true);
+    return mldsa_verify_host(param, pk, sig, {msg_blob, msg_off, ctx_blob, ctx_off, 0}, ok, n, device, true);
 }
 int circl_hip_mldsa_verify_keyed(int param, const uint8_t *pk_table, size_t nkeys, const uint32_t *key_idx, const uint8_t *sig,
                                  const uint8_t *msg_blob, const uint64_t *msg_off, const uint8_t *ctx_blob, const uint64_t *ctx_off, uint8_t *ok,
@@ -1089,9 +1086,9 @@ int circl_hip_mldsa_verify_keyed(int param, const uint8_t *pk_table, size_t nkey
     if (nkeys == 0 || nkeys > 0xffffffffull) return CIRCL_HIP_EPARAM;
     TRY(check_key_idx(key_idx, n, nkeys));
     if (check_contexts(param, ctx_blob, ctx_off, n) == CTX_UNSUPPORTED) return CIRCL_HIP_EPARAM;
+    const DsaMsgs m{msg_blob, msg_off, ctx_blob, ctx_off, 0};
     return shard(n, device, [&](int dev, size_t lo, size_t cnt) {
-        return mldsa_verify_host_one<KM_KEYED>(param, dev, pk_table, nkeys, key_idx + lo, sig + lo * SIG, msg_blob, msg_off + lo, ctx_blob,
-                                               ctx_blob ? ctx_off + lo : nullptr, 0, ok + lo, cnt);
+        return mldsa_verify_host_one<KM_KEYED>(param, dev, pk_table, nkeys, key_idx + lo, sig + lo * SIG, m.from(lo), ok + lo, cnt);
     });
 }
 
@@ -1100,26 +1097,18 @@ int circl_hip_mldsa_verify_keyed(int param, const uint8_t *pk_table, size_t nkey
 // fallback of the block-parallel form.
 int circl_hip_mldsa_sample_in_ball(int param, const uint8_t *ctilde, uint32_t *polys, size_t n, int sequential, int device) {
     using namespace circl::mldsa;
-    const size_t CT = param == 44 ? 32 : param == 65 ? 48 : param == 87 ? 64 : (param == 2 || param == 3 || param == 5) ? 32 : 0;
+    const size_t CT = (param == 44 || is_r3(param)) ? 32 : param == 65 ? 48 : param == 87 ? 64 : 0;
     if (!CT) return CIRCL_HIP_EPARAM;
     uint8_t *po = reinterpret_cast<uint8_t *>(polys);
     PipeOpts o;
     o.chunk_items = host_chunk_items(size_t(1) << 14);
     return shard(n, device, [&](int dev, size_t lo, size_t cnt) {
         return run_pipeline(dev, cnt, {{ctilde + lo * CT, CT}}, {}, {{po + lo * 1024, 1024}}, kNoWs, o, [&](Chunk &c) {
-#define CALL(M) hipLaunchKernelGGL(mldsa_sample_in_ball_kernel<M>, dim3((unsigned)c.cnt), dim3(64), 0, c.st, (const uint8_t *)c.in[0], \
-                                   reinterpret_cast<uint32_t *>(c.out[0]), sequential)
-            int rc = CIRCL_HIP_OK;
-            switch (param) {
-            case 44: CALL(44); break;
-            case 65: CALL(65); break;
-            case 87: CALL(87); break;
-            case 2: CALL(2); break;
-            case 3: CALL(3); break;
-            case 5: CALL(5); break;
-            default: rc = CIRCL_HIP_EPARAM;
-            }
-#undef CALL
+            const int rc = dsa_with_mode(param, [&](auto mode) -> int {
+                hipLaunchKernelGGL(mldsa_sample_in_ball_kernel<mode.value>, dim3((unsigned)c.cnt), dim3(64), 0, c.st, (const uint8_t *)c.in[0],
+                                   reinterpret_cast<uint32_t *>(c.out[0]), sequential);
+                return CIRCL_HIP_OK;
+            });
             HIP_TRY(hipGetLastError());
             return rc;
         });
@@ -1128,21 +1117,11 @@ int circl_hip_mldsa_sample_in_ball(int param, const uint8_t *ctilde, uint32_t *p
 
 int circl_hip_mldsa_keygen_dev(int param, const uint8_t *d_seed32, uint8_t *d_pk, uint8_t *d_sk, size_t n, void *d_ws, size_t ws_bytes,
                                void *stream) {
-    if (ndev() <= 0) return CIRCL_HIP_ENODEV;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-#define CALL(M) mldsa_keygen_dev_impl<M>(d_seed32, d_pk, d_sk, n, d_ws, ws_bytes, st)
-    DSA_SWITCH(param, CALL)
-#undef CALL
-    return CIRCL_HIP_EPARAM;
+    return dsa_dev_call(param, stream, [&](auto mode, hipStream_t st) { return mldsa_keygen_dev_impl<mode.value>(d_seed32, d_pk, d_sk, n, d_ws, ws_bytes, st); });
 }
 
 int circl_hip_mldsa_public_from_private_dev(int param, const uint8_t *d_sk, uint8_t *d_pk, size_t n, void *d_ws, size_t ws_bytes, void *stream) {
-    if (ndev() <= 0) return CIRCL_HIP_ENODEV;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-#define CALL(M) mldsa_public_dev_impl<M>(d_sk, d_pk, n, d_ws, ws_bytes, st)
-    DSA_SWITCH(param, CALL)
-#undef CALL
-    return CIRCL_HIP_EPARAM;
+    return dsa_dev_call(param, stream, [&](auto mode, hipStream_t st) { return mldsa_public_dev_impl<mode.value>(d_sk, d_pk, n, d_ws, ws_bytes, st); });
 }
 int circl_hip_mldsa_public_from_private(int param, const uint8_t *sk, uint8_t *pk, size_t n, int device) {
     const size_t PK = circl_hip_mldsa_pk_size(param), SK = circl_hip_mldsa_sk_size(param);
@@ -1168,27 +1147,27 @@ size_t circl_hip_mldsa_sign_workspace_size(int param, size_t n) { return mldsa_s
 int circl_hip_mldsa_sign_dev(int param, const uint8_t *d_sk, const uint8_t *d_msg_blob, const uint64_t *d_msg_off,
                              const uint8_t *d_ctx_blob, const uint64_t *d_ctx_off, const uint8_t *d_rnd, int internal, uint8_t *d_sig,
                              size_t n, void *d_ws, size_t ws_bytes, void *stream) {
-    return mldsa_sign_dev_any(param, d_sk, d_msg_blob, d_msg_off, d_ctx_blob, d_ctx_off, d_rnd, internal, d_sig, n, d_ws, ws_bytes,
-                              static_cast<hipStream_t>(stream));
+    return mldsa_sign_dev_any(param, SignKeys{d_sk, false, nullptr, nullptr, false}, {d_msg_blob, d_msg_off, d_ctx_blob, d_ctx_off, internal}, d_rnd, d_sig, n,
+                              d_ws, ws_bytes, stream);
 }
 int circl_hip_mldsa_sign_shared_dev(int param, const uint8_t *d_sk, const uint8_t *d_msg_blob, const uint64_t *d_msg_off,
                                     const uint8_t *d_ctx_blob, const uint64_t *d_ctx_off, const uint8_t *d_rnd, int internal, uint8_t *d_sig,
                                     size_t n, void *d_ws, size_t ws_bytes, void *stream) {
-    return mldsa_sign_dev_any(param, d_sk, d_msg_blob, d_msg_off, d_ctx_blob, d_ctx_off, d_rnd, internal, d_sig, n, d_ws, ws_bytes,
-                              static_cast<hipStream_t>(stream), true);
+    return mldsa_sign_dev_any(param, SignKeys{d_sk, true, nullptr, nullptr, false}, {d_msg_blob, d_msg_off, d_ctx_blob, d_ctx_off, internal}, d_rnd, d_sig, n,
+                              d_ws, ws_bytes, stream);
 }
 
 int circl_hip_mldsa_sign(int param, const uint8_t *sk, const uint8_t *msg_blob, const uint64_t *msg_off, const uint8_t *ctx_blob,
                          const uint64_t *ctx_off, const uint8_t *rnd, uint8_t *sig, size_t n, int device) {
-    return mldsa_sign_host(param, sk, msg_blob, msg_off, ctx_blob, ctx_off, rnd, 0, sig, n, device);
+    return mldsa_sign_host(param, sk, {msg_blob, msg_off, ctx_blob, ctx_off, 0}, rnd, sig, n, device);
 }
 int circl_hip_mldsa_sign_shared(int param, const uint8_t *sk, const uint8_t *msg_blob, const uint64_t *msg_off, const uint8_t *ctx_blob,
                                 const uint64_t *ctx_off, const uint8_t *rnd, uint8_t *sig, size_t n, int device) {
-    return mldsa_sign_host(param, sk, msg_blob, msg_off, ctx_blob, ctx_off, rnd, 0, sig, n, device, true);
+    return mldsa_sign_host(param, sk, {msg_blob, msg_off, ctx_blob, ctx_off, 0}, rnd, sig, n, device, true);
 }
 int circl_hip_mldsa_sign_internal(int param, const uint8_t *sk, const uint8_t *msg_blob, const uint64_t *msg_off, const uint8_t *rnd,
                                   uint8_t *sig, size_t n, int device) {
-    return mldsa_sign_host(param, sk, msg_blob, msg_off, nullptr, nullptr, rnd, 1, sig, n, device);
+    return mldsa_sign_host(param, sk, {msg_blob, msg_off, nullptr, nullptr, 1}, rnd, sig, n, device);
 }
 
 }  // extern "C"

@@ -110,6 +110,70 @@ def test_mldsa_device_index_vector_is_bounded_to_the_table(param, n):
     verifier.close()
 
 
+SPLIT_N = (1 << 16) + 37                                                      # >= 2^16 items: signed as two halves side by side, the first of 32832
+
+
+def _sign_split_batch():
+    """SPLIT_N deterministic ML-DSA-44 signatures of 32-byte messages through a table of NKEYS prepared keys and a device index
+    vector (circl_hip_mldsa_sign_table_keyed_dev: the host form chunks at 2^13 items and never reaches the split)
+    -> (pk, sk, bounded, msgs, signatures)"""
+    import ctypes as C
+    import torch
+    from circl_amd import _native as nat, device as cdev, hostapi
+    L = nat.lib()
+    n = SPLIT_N
+    rng = np.random.default_rng(4400 + n)
+    pk, sk = orc.mldsa_keygen(44, rng.integers(0, 256, (NKEYS, 32), dtype=np.uint8))
+    idx, bounded = _indices(rng, n)
+    msgs = rng.integers(0, 256, (n, 32), dtype=np.uint8)
+    d_msg = _cuda(np.concatenate([msgs.reshape(-1), np.zeros(16, np.uint8)]))
+    d_idx = _cuda(idx)
+    eng = cdev.MLDSADevice(44, n, sign=True)
+    signer = hostapi.KeyTable("mldsa-private", 44, sk)
+    sig = torch.empty(n * eng.SIG + 16, dtype=torch.uint8, device="cuda")[:n * eng.SIG].view(n, eng.SIG)
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    rc = L.circl_hip_mldsa_sign_table_keyed_dev(signer.handle, d_idx.data_ptr(), d_msg.data_ptr(), eng.off.data_ptr(), None, None, eng.rnd0.data_ptr(), 0,
+                                                sig.data_ptr(), n, eng.sws.data_ptr(), eng.swsb, stream)
+    nat.check(rc, "mldsa_sign_table_keyed_dev")
+    torch.cuda.synchronize()
+    got = sig.cpu().numpy().copy()
+    signer.close()
+    return pk, sk, bounded, msgs, got
+
+
+def _sign_split_digest():
+    import hashlib
+    return hashlib.sha256(_sign_split_batch()[4].tobytes()).hexdigest()
+
+
+def test_mldsa_split_signing_gives_each_half_its_slice_of_the_index_vector():
+    # each half of a split batch signs with ITS slice of the index vector (and of the keys' rows, messages, rnd): every signature
+    # verifies under the key its index names -- out-of-range indices bounded in both halves --, the items on the two sides of the cut
+    # (32831 | 32832) and at both ends are the oracle's bytes, and the unsplit route (a process of its own: the knob is read once)
+    # signs the same SPLIT_N signatures
+    import hashlib
+    import os
+    import subprocess
+    import sys
+    import torch
+    from circl_amd import device as cdev, hostapi
+    n = SPLIT_N
+    pk, sk, bounded, msgs, got = _sign_split_batch()
+    verifier = hostapi.KeyTable("mldsa-public", 44, pk)
+    eng = cdev.MLDSADevice(44, n)
+    ok = eng.verify_table(verifier, _cuda(got), _cuda(np.concatenate([msgs.reshape(-1), np.zeros(16, np.uint8)])), _cuda(bounded))
+    torch.cuda.synchronize()
+    assert bool(ok.all())
+    verifier.close()
+    edge = np.array([0, 32831, 32832, n - 1])
+    assert (got[edge] == orc.mldsa_sign(44, sk[bounded[edge]], [bytes(r) for r in msgs[edge]], ctxs=[b""] * len(edge))).all()
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, CIRCL_HIP_SIGN_NOSPLIT="1")
+    code = "import sys; sys.path[:0] = [%r, %r]; import test_gpu_keyidx as t; print('digest', t._sign_split_digest())" % (root, os.path.join(root, "tests"))
+    r = subprocess.run([sys.executable, "-c", code], cwd=root, env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "digest " + hashlib.sha256(got.tobytes()).hexdigest() in r.stdout, r.stdout[-1500:] + r.stderr[-4000:]
+
+
 @pytest.mark.parametrize("scheme_name", ["xwing", "x25519mlkem768"])
 def test_hybrid_device_index_vector_is_bounded_to_the_table(scheme_name):
     import ctypes as C

@@ -109,6 +109,22 @@ def test_mldsa_table_matches_the_oracle_call_after_call(param):
     t.close()
 
 
+@pytest.mark.parametrize("env_extra", [{}, {"CIRCL_HIP_DSA_CHAIN": "0", "CIRCL_HIP_DSA_CHAIN_ITEM": "0"}], ids=["one-launch", "scratch-route"])
+def test_mldsa_table_layout_at_its_padding_edges(env_extra):
+    # a public-key table's packed A rows are padded to whole groups of IT entries (4 / 2 / 1, Dilithium3: 2) and a 64-byte tr slot per
+    # entry lies behind them: IT - 1, IT and IT + 1 entries, the last entry and entry 0 in use, a long message (tr through the pre-pass),
+    # contexts -- through the per-call key table and the resident one, with and without an index vector, on both bodies of the resident
+    # form; and tables of prepared private keys of the same sizes signing like the oracle (the worker)
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    env.update(env_extra)
+    r = subprocess.run([sys.executable, os.path.join(root, "tests", "dsa_table_edges_worker.py")], cwd=root, env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "dsa table edges ok" in r.stdout, r.stdout[-1500:] + r.stderr[-4000:]
+
+
 @pytest.mark.parametrize("param", [44, 65, 87, 3])
 def test_mldsa_prepared_private_key_signs_like_the_oracle(param):
     # the parsed PrivateKey of the reference keeps A and the NTT-domain s1, s2, t0 (internal/dilithium.go:149-179): prepared once

@@ -1,4 +1,5 @@
-"""Not a test: ML-DSA signing latency of very small batches (which route: CIRCL_HIP_SIGN_BATCHED_MIN).   python tools/dsa_sign_small.py [param]"""
+"""Not a test: ML-DSA signing latency of very small batches (which route: CIRCL_HIP_SIGN_BATCHED_MIN).   python tools/dsa_sign_small.py [param]
+(CIRCL_SIGN_SMALL_NS=1,512: these batch sizes instead of 1 .. 32)"""
 import os
 import sys
 import time
@@ -10,7 +11,7 @@ from circl_amd import device as cdev  # noqa: E402
 
 param = int(sys.argv[1]) if len(sys.argv) > 1 else 65
 out = []
-for n in (1, 2, 4, 8, 16, 32):
+for n in ([int(x) for x in os.environ["CIRCL_SIGN_SMALL_NS"].split(",")] if os.environ.get("CIRCL_SIGN_SMALL_NS") else (1, 2, 4, 8, 16, 32)):
     eng = cdev.MLDSADevice(param, n, "cuda", sign=True)
     g = torch.Generator(device="cuda").manual_seed(1)
     pk, sk = eng.keygen(torch.randint(0, 256, (n, 32), dtype=torch.uint8, device="cuda", generator=g))
