@@ -59,7 +59,10 @@ SYMBOLS = [
     "circl_hip_hpke_context_size",
 ] + [f + d for f in ("circl_hip_hpke_setup_sender", "circl_hip_hpke_setup_receiver", "circl_hip_hpke_seal", "circl_hip_hpke_open", "circl_hip_hpke_export",
                      "circl_hip_hpke_seal_single", "circl_hip_hpke_open_single", "circl_hip_hpke_export_single", "circl_hip_hpke_export_single_receiver")
-     for d in ("", "_dev")]
+     for d in ("", "_dev")] + [f + d for f in ("circl_hip_ristretto255_hash_to_group", "circl_hip_ristretto255_hash_to_scalar", "circl_hip_ristretto255_scalar_mult",
+                               "circl_hip_oprf_derive_keypair", "circl_hip_oprf_blind", "circl_hip_oprf_evaluate", "circl_hip_oprf_finalize",
+                               "circl_hip_oprf_full_evaluate")
+                  for d in ("", "_dev")]
 
 OK, EPARAM, ENODEV, EHIP, ENOMEM, EWORKSPACE, EBUSY, EAGAIN = 0, -1, -2, -3, -4, -5, -6, -7
 ALL_DEVICES = -1
@@ -260,6 +263,13 @@ def lib():
                            ("export_single", setup + [vp, vp, sz, vp, vp, vp]), ("export_single_receiver", setup + [vp, vp, sz, vp, vp])):
             getattr(L, "circl_hip_hpke_" + name).argtypes = args + [sz, i]
             getattr(L, "circl_hip_hpke_" + name + "_dev").argtypes = args + [sz, vp]
+        u32 = C.c_uint32
+        for name, args in (("ristretto255_hash_to_group", [vp, vp, vp, sz, vp]), ("ristretto255_hash_to_scalar", [vp, vp, vp, sz, vp]),
+                           ("ristretto255_scalar_mult", [vp, sz, vp, u32, vp, vp]), ("oprf_derive_keypair", [i, vp, vp, vp, vp, vp, vp]),
+                           ("oprf_blind", [i, vp, vp, vp, vp, vp]), ("oprf_evaluate", [vp, sz, vp, vp, vp]),
+                           ("oprf_finalize", [vp, vp, vp, vp, vp, vp]), ("oprf_full_evaluate", [i, vp, sz, vp, vp, vp, vp])):
+            getattr(L, "circl_hip_" + name).argtypes = args + [sz, i]
+            getattr(L, "circl_hip_" + name + "_dev").argtypes = args + [sz, vp]
         for f in ("seed", "eseed", "pk", "sk", "ct", "ss"):
             fn = getattr(L, "circl_hip_hybrid_%s_size" % f)
             fn.restype, fn.argtypes = sz, [i]

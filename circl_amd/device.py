@@ -17,7 +17,9 @@ KERNELS = {"mlkem_hash": 0, "mlkem_encrypt": 1, "mlkem_decrypt": 2, "mlkem_keyge
            "ed25519_keygen": 12, "ed25519_sign": 13, "ed25519_verify": 14, "sha512": 15,
            "x448": 16, "ed448_keygen": 17, "ed448_sign": 18, "ed448_verify": 19,
            "frodo_keygen": 20, "frodo_encaps": 21, "frodo_decaps": 22,
-           "hpke_x25519": 23, "hpke_x448": 24, "sha256": 25, "hpke_setup": 26, "hpke_aead": 27, "hpke_export": 28}
+           "hpke_x25519": 23, "hpke_x448": 24, "sha256": 25, "hpke_setup": 26, "hpke_aead": 27, "hpke_export": 28,
+           "oprf_hash_to_group": 29, "oprf_hash_to_scalar": 30, "oprf_scalar_mult": 31, "oprf_derive_keypair": 32, "oprf_blind": 33, "oprf_evaluate": 34,
+           "oprf_finalize": 35, "oprf_full_evaluate": 36}
 
 
 def _stream():
@@ -490,4 +492,77 @@ class HpkeSuiteDevice:
         out, ok = self._out(n, length), self._out(n)
         nat.check(self.L.circl_hip_hpke_export_single_receiver_dev(*self._setup(mode, (skR, pkR, enc, pkS), info, psk, psk_id), *_rag_args(exporter_context),
                                                                    length, _chk(out), _chk(ok), n, _stream()), "hpke_export_single_receiver_dev")
+        return out, ok
+
+
+class OprfDevice:
+    """ristretto255 and base-mode OPRF (suite ristretto255-SHA512) on resident tensors (circl_hip_ristretto255_*_dev, circl_hip_oprf_*_dev),
+    on torch's current stream.  Elements, scalars, keys and blinds are (n, 32) uint8 tensors, OPRF outputs (n, 64); ragged inputs are Ragged
+    objects (or None: every item empty).  A key or scalar of shape (32,) or (1, 32) is shared by the batch.  Failed items have ok = 0 and zero
+    rows."""
+
+    def __init__(self, device="cuda"):
+        self.device = device
+        self.L = nat.lib()
+
+    def _out(self, *shape):
+        return torch.empty(shape, dtype=torch.uint8, device=self.device)
+
+    @staticmethod
+    def _scalars(t, n):
+        """(pointer, stride) of n scalar rows, or of one row shared by the batch"""
+        shared = t.numel() == 32 and n != 1
+        assert shared or t.shape == (n, 32), (t.shape, n)
+        return _chk(t, 32), 0 if shared else 32
+
+    def _hash(self, fn, msgs, n, dst):
+        import numpy as np
+        d = np.frombuffer(bytes(dst) + b"\0", np.uint8)      # the tag is host bytes in both forms
+        out = self._out(n, 32)
+        nat.check(fn(*_rag_args(msgs), d.ctypes.data_as(C.c_void_p), len(dst), _chk(out), n, _stream()), "ristretto255_hash_dev")
+        return out
+
+    def hash_to_group(self, msgs, n, dst):
+        return self._hash(self.L.circl_hip_ristretto255_hash_to_group_dev, msgs, n, dst)
+
+    def hash_to_scalar(self, msgs, n, dst):
+        return self._hash(self.L.circl_hip_ristretto255_hash_to_scalar_dev, msgs, n, dst)
+
+    def scalar_mult(self, scalars, elems=None, invert=False, n=None):
+        n = elems.shape[0] if elems is not None else (scalars.shape[0] if n is None else n)
+        out, ok = self._out(n, 32), self._out(n)
+        nat.check(self.L.circl_hip_ristretto255_scalar_mult_dev(*self._scalars(scalars, n), None if elems is None else _chk(elems, 32), 1 if invert else 0,
+                                                                _chk(out), _chk(ok), n, _stream()), "ristretto255_scalar_mult_dev")
+        return out, ok
+
+    def derive_keypair(self, mode, seeds, infos=None):
+        n = seeds.shape[0]
+        sk, pk, ok = self._out(n, 32), self._out(n, 32), self._out(n)
+        nat.check(self.L.circl_hip_oprf_derive_keypair_dev(mode, _chk(seeds, 32), *_rag_args(infos), _chk(sk), _chk(pk), _chk(ok), n, _stream()),
+                  "oprf_derive_keypair_dev")
+        return sk, pk, ok
+
+    def blind(self, mode, inputs, blinds):
+        n = blinds.shape[0]
+        out, ok = self._out(n, 32), self._out(n)
+        nat.check(self.L.circl_hip_oprf_blind_dev(mode, *_rag_args(inputs), _chk(blinds, 32), _chk(out), _chk(ok), n, _stream()), "oprf_blind_dev")
+        return out, ok
+
+    def evaluate(self, sk, blinded):
+        n = blinded.shape[0]
+        out, ok = self._out(n, 32), self._out(n)
+        nat.check(self.L.circl_hip_oprf_evaluate_dev(*self._scalars(sk, n), _chk(blinded, 32), _chk(out), _chk(ok), n, _stream()), "oprf_evaluate_dev")
+        return out, ok
+
+    def finalize(self, inputs, blinds, evaluated):
+        n = blinds.shape[0]
+        out, ok = self._out(n, 64), self._out(n)
+        nat.check(self.L.circl_hip_oprf_finalize_dev(*_rag_args(inputs), _chk(blinds, 32), _chk(evaluated, 32), _chk(out), _chk(ok), n, _stream()),
+                  "oprf_finalize_dev")
+        return out, ok
+
+    def full_evaluate(self, mode, sk, inputs, n):
+        out, ok = self._out(n, 64), self._out(n)
+        nat.check(self.L.circl_hip_oprf_full_evaluate_dev(mode, *self._scalars(sk, n), *_rag_args(inputs), _chk(out), _chk(ok), n, _stream()),
+                  "oprf_full_evaluate_dev")
         return out, ok

@@ -1132,3 +1132,93 @@ class HpkeSuite:
         out, ok = np.empty((n, max(length, 0)), np.uint8), np.empty(n, np.uint8)
         nat.check(self.L.circl_hip_hpke_export_single_receiver(*args, _po(eb), _po(eo), length, _p(out), _p(ok), n, self.device), "hpke_export_single_receiver")
         return out, ok
+
+
+# ---- ristretto255 (group/ristretto255.go) and base-mode OPRF (oprf/keys.go, client.go, server.go; RFC 9497, ristretto255-SHA512) ----
+OPRF_MODE_OPRF, OPRF_MODE_VOPRF, OPRF_MODE_POPRF = range(3)
+R255_INVERT = 1
+
+
+def _scalar_rows(x, n=None):
+    """(rows, stride): one 32-byte scalar (bytes or a (32,) / (1, 32) array with n given) is shared by the batch, stride 0"""
+    a = _u8(x, 32)
+    if n is not None and len(a) == 1 and n != 1:
+        return a, 0
+    if n is not None and len(a) != n:
+        raise ValueError("need 1 or %d scalar rows, got %d" % (n, len(a)))
+    return a, 32
+
+
+def ristretto255_hash_to_group(msgs, dst, device=0):
+    """Ristretto255.HashToElement(msg_i, dst) -> (n, 32); one dst of 1..255 bytes for the batch"""
+    n = len(msgs)
+    (mb, mo), d, out = _blob(msgs), np.frombuffer(bytes(dst) + b"\0", np.uint8), np.empty((n, 32), np.uint8)
+    nat.check(nat.lib().circl_hip_ristretto255_hash_to_group(_p(mb), _p(mo), _p(d), len(dst), _p(out), n, device), "ristretto255_hash_to_group")
+    return out
+
+
+def ristretto255_hash_to_scalar(msgs, dst, device=0):
+    """Ristretto255.HashToScalar(msg_i, dst) -> (n, 32)"""
+    n = len(msgs)
+    (mb, mo), d, out = _blob(msgs), np.frombuffer(bytes(dst) + b"\0", np.uint8), np.empty((n, 32), np.uint8)
+    nat.check(nat.lib().circl_hip_ristretto255_hash_to_scalar(_p(mb), _p(mo), _p(d), len(dst), _p(out), n, device), "ristretto255_hash_to_scalar")
+    return out
+
+
+def ristretto255_scalar_mult(scalars, elems=None, invert=False, n=None, device=0):
+    """scalar_i elem_i (elems None: the generator; invert: by scalar_i^-1) -> (out (n, 32), ok (n,)).  One scalar row with n (or with
+    several elems) is shared by the batch.  ok = 0 and a zero row for an element that does not decode, a scalar >= L, an inverse of 0."""
+    elems = None if elems is None else _u8(elems, 32)
+    n = len(elems) if elems is not None else n
+    sc, stride = _scalar_rows(scalars, n)
+    n = len(sc) if n is None else n
+    out, ok = np.empty((n, 32), np.uint8), np.empty(n, np.uint8)
+    nat.check(nat.lib().circl_hip_ristretto255_scalar_mult(_p(sc), stride, _po(elems), R255_INVERT if invert else 0, _p(out), _p(ok), n, device),
+              "ristretto255_scalar_mult")
+    return out, ok
+
+
+def oprf_derive_keypair(mode, seeds, infos=None, device=0):
+    """oprf.DeriveKey(suite, mode, seed_i, info_i) -> (sk (n, 32), pk (n, 32), ok (n,))"""
+    seeds = _u8(seeds, 32)
+    n = len(seeds)
+    (ib, io), sk, pk, ok = _rag(infos, n), np.empty((n, 32), np.uint8), np.empty((n, 32), np.uint8), np.empty(n, np.uint8)
+    nat.check(nat.lib().circl_hip_oprf_derive_keypair(mode, _p(seeds), _po(ib), _po(io), _p(sk), _p(pk), _p(ok), n, device), "oprf_derive_keypair")
+    return sk, pk, ok
+
+
+def oprf_blind(mode, inputs, blinds, device=0):
+    """Client.DeterministicBlind: blind_i HashToGroup(input_i) -> (blinded (n, 32), ok (n,)); the caller draws the blinds"""
+    blinds = _u8(blinds, 32)
+    n = len(blinds)
+    (ib, io), out, ok = _rag(inputs, n), np.empty((n, 32), np.uint8), np.empty(n, np.uint8)
+    nat.check(nat.lib().circl_hip_oprf_blind(mode, _po(ib), _po(io), _p(blinds), _p(out), _p(ok), n, device), "oprf_blind")
+    return out, ok
+
+
+def oprf_evaluate(sk, blinded, device=0):
+    """base-mode Server.Evaluate: sk blinded_i -> (evaluated (n, 32), ok (n,)); sk = one key for the batch (32 bytes) or (n, 32) rows"""
+    blinded = _u8(blinded, 32)
+    n = len(blinded)
+    (key, stride), out, ok = _scalar_rows(sk, n), np.empty((n, 32), np.uint8), np.empty(n, np.uint8)
+    nat.check(nat.lib().circl_hip_oprf_evaluate(_p(key), stride, _p(blinded), _p(out), _p(ok), n, device), "oprf_evaluate")
+    return out, ok
+
+
+def oprf_finalize(inputs, blinds, evaluated, device=0):
+    """base-mode Client.Finalize -> (outputs (n, 64), ok (n,))"""
+    blinds, evaluated = _u8(blinds, 32), _u8(evaluated, 32)
+    n = len(blinds)
+    if len(evaluated) != n:
+        raise ValueError("oprf_finalize: %d blinds, %d evaluated elements" % (n, len(evaluated)))
+    (ib, io), out, ok = _rag(inputs, n), np.empty((n, 64), np.uint8), np.empty(n, np.uint8)
+    nat.check(nat.lib().circl_hip_oprf_finalize(_po(ib), _po(io), _p(blinds), _p(evaluated), _p(out), _p(ok), n, device), "oprf_finalize")
+    return out, ok
+
+
+def oprf_full_evaluate(mode, sk, inputs, device=0):
+    """Server.FullEvaluate (mode 0) / VerifiableServer.FullEvaluate (mode 1) -> (outputs (n, 64), ok (n,)); sk as in oprf_evaluate"""
+    n = len(inputs)
+    (key, stride), (ib, io), out, ok = _scalar_rows(sk, n), _blob(inputs), np.empty((n, 64), np.uint8), np.empty(n, np.uint8)
+    nat.check(nat.lib().circl_hip_oprf_full_evaluate(mode, _p(key), stride, _p(ib), _p(io), _p(out), _p(ok), n, device), "oprf_full_evaluate")
+    return out, ok

@@ -896,6 +896,66 @@ int circl_hip_hpke_export_single_receiver_dev(CIRCL_HIP_HPKE_RECEIVER_, const ui
 #undef CIRCL_HIP_HPKE_OPEN_
 #undef CIRCL_HIP_HPKE_ROWS_
 
+/* ---- ristretto255 (group/ristretto255.go; RFC 9496) and base-mode OPRF (oprf/keys.go, client.go, server.go; RFC 9497, suite
+ * ristretto255-SHA512) --------------------------------------------------------------------------------------------------------
+ * One item per lane, one launch per call, no workspace.  Elements and scalars are rows of 32 bytes (the canonical encodings),
+ * OPRF outputs rows of 64.  Ragged arguments (messages, infos, inputs) are a blob and n + 1 uint64_t offsets; a NULL blob means that
+ * every item's is empty (its offsets are then not read); a blob without offsets is CIRCL_HIP_EPARAM.
+ * DECODING IS STRICT RFC 9496: an element encoding with s >= p, with bit 255 set, a negative s, a non-square, a negative t or
+ * y = 0 is refused, and so is a scalar >= L.  The reference reduces s >= p and ignores bit 255 (its own test comments out the two
+ * vectors); this is the one place where an item the reference accepts gets ok = 0.
+ *   hash_to_group / hash_to_scalar:  Ristretto255.HashToElement / HashToScalar(msg_i, dst): expand_message_xmd (RFC 9380, SHA-512,
+ *                    64 bytes), ONE dst for the batch, given as HOST bytes in both forms, 1 <= dst_len <= 255 (else
+ *                    CIRCL_HIP_EPARAM; RFC 9380's rule for a longer tag is out of scope).
+ *   scalar_mult:     out_i = scalar_i elem_i; scalar_stride = 32, or 0 for one scalar for the batch; elems == NULL: the generator
+ *                    (fixed-base comb); flags & 1: by the scalar's inverse (other flag bits: CIRCL_HIP_EPARAM).  ok = 0 where the
+ *                    element does not decode, the scalar is >= L or an inverse of zero is asked.  The identity is accepted here.
+ *   derive_keypair:  DeriveKey(mode, seed_i, info_i), modes 0 (OPRF), 1 (VOPRF), 2 (POPRF); ok = 0 for an info over 65535 bytes or
+ *                    where no counter gives a non-zero scalar.
+ *   blind:           Client.DeterministicBlind, the same in modes 0, 1, 2 up to the tag: blinded_i = blind_i HashToGroup(input_i).
+ *                    The library has no RNG: the caller draws the blinds.  ok = 0 for a blind that is zero or >= L, an input over
+ *                    65535 bytes (RFC 9497 forbids it; the reference would truncate its length) or an identity element.
+ *   evaluate:        base-mode Server.Evaluate: evaluated_i = sk blinded_i; sk_stride = 32, or 0 for the server's ONE key (staged
+ *                    once per chunk, never copied n times).  ok = 0 where the blinded element does not decode or is the identity
+ *                    (DeserializeElement), or the key is zero or >= L.
+ *   finalize:        base-mode Client.Finalize: SHA-512(I2OSP(len, 2) || input_i || I2OSP(32, 2) || blind_i^-1 evaluated_i ||
+ *                    "Finalize"); ok = 0 as for blind and evaluate.
+ *   full_evaluate:   Server.FullEvaluate (mode 0) / VerifiableServer.FullEvaluate (mode 1) in ONE kernel: neither the hashed point nor
+ *                    the evaluated element reaches memory.  Mode 2 needs the info tweak: CIRCL_HIP_EPARAM.
+ * evaluate and finalize take no mode: they are base mode; the verifiable forms (with their proofs) are not served yet.
+ * ok[i] = 0 means every output row of item i is all zero.  ok may be NULL.  Any other mode, stride or flag is CIRCL_HIP_EPARAM,
+ * reported before a device is looked for.  Keys, blinds, seeds, inputs and outputs are wiped from the host forms' staging; the _dev
+ * forms want 4-byte aligned rows and 8-byte aligned offsets (CIRCL_HIP_EWORKSPACE otherwise).  n == 0 is CIRCL_HIP_OK. */
+#define CIRCL_HIP_OPRF_MODE_OPRF 0
+#define CIRCL_HIP_OPRF_MODE_VOPRF 1
+#define CIRCL_HIP_OPRF_MODE_POPRF 2
+#define CIRCL_HIP_R255_INVERT 1u /* scalar_mult flags */
+int circl_hip_ristretto255_hash_to_group(const uint8_t *msg_blob, const uint64_t *msg_off, const uint8_t *dst, size_t dst_len, uint8_t *out, size_t n, int device);
+int circl_hip_ristretto255_hash_to_scalar(const uint8_t *msg_blob, const uint64_t *msg_off, const uint8_t *dst, size_t dst_len, uint8_t *out, size_t n, int device);
+int circl_hip_ristretto255_scalar_mult(const uint8_t *scalars, size_t scalar_stride, const uint8_t *elems, uint32_t flags, uint8_t *out, uint8_t *ok, size_t n,
+                                       int device);
+int circl_hip_oprf_derive_keypair(int mode, const uint8_t *seeds, const uint8_t *info_blob, const uint64_t *info_off, uint8_t *sk, uint8_t *pk, uint8_t *ok,
+                                  size_t n, int device);
+int circl_hip_oprf_blind(int mode, const uint8_t *input_blob, const uint64_t *input_off, const uint8_t *blinds, uint8_t *blinded, uint8_t *ok, size_t n, int device);
+int circl_hip_oprf_evaluate(const uint8_t *sk, size_t sk_stride, const uint8_t *blinded, uint8_t *evaluated, uint8_t *ok, size_t n, int device);
+int circl_hip_oprf_finalize(const uint8_t *input_blob, const uint64_t *input_off, const uint8_t *blinds, const uint8_t *evaluated, uint8_t *out, uint8_t *ok,
+                            size_t n, int device);
+int circl_hip_oprf_full_evaluate(int mode, const uint8_t *sk, size_t sk_stride, const uint8_t *input_blob, const uint64_t *input_off, uint8_t *out, uint8_t *ok,
+                                 size_t n, int device);
+/* the device-resident forms: the same arguments as device pointers (dst stays host bytes), on the caller's stream */
+int circl_hip_ristretto255_hash_to_group_dev(const uint8_t *msg_blob, const uint64_t *msg_off, const uint8_t *dst, size_t dst_len, uint8_t *out, size_t n, void *stream);
+int circl_hip_ristretto255_hash_to_scalar_dev(const uint8_t *msg_blob, const uint64_t *msg_off, const uint8_t *dst, size_t dst_len, uint8_t *out, size_t n, void *stream);
+int circl_hip_ristretto255_scalar_mult_dev(const uint8_t *scalars, size_t scalar_stride, const uint8_t *elems, uint32_t flags, uint8_t *out, uint8_t *ok, size_t n,
+                                       void *stream);
+int circl_hip_oprf_derive_keypair_dev(int mode, const uint8_t *seeds, const uint8_t *info_blob, const uint64_t *info_off, uint8_t *sk, uint8_t *pk, uint8_t *ok,
+                                  size_t n, void *stream);
+int circl_hip_oprf_blind_dev(int mode, const uint8_t *input_blob, const uint64_t *input_off, const uint8_t *blinds, uint8_t *blinded, uint8_t *ok, size_t n, void *stream);
+int circl_hip_oprf_evaluate_dev(const uint8_t *sk, size_t sk_stride, const uint8_t *blinded, uint8_t *evaluated, uint8_t *ok, size_t n, void *stream);
+int circl_hip_oprf_finalize_dev(const uint8_t *input_blob, const uint64_t *input_off, const uint8_t *blinds, const uint8_t *evaluated, uint8_t *out, uint8_t *ok,
+                            size_t n, void *stream);
+int circl_hip_oprf_full_evaluate_dev(int mode, const uint8_t *sk, size_t sk_stride, const uint8_t *input_blob, const uint64_t *input_off, uint8_t *out, uint8_t *ok,
+                                 size_t n, void *stream);
+
 /* ---- kernel-level profiling (used by bench.py for the roofline figures) --------------------
  * While enabled, every *_dev call brackets each kernel it enqueues with HIP events recorded on
  * the caller's stream.  circl_hip_profile_read synchronises the pending events, returns the
@@ -929,7 +989,15 @@ int circl_hip_hpke_export_single_receiver_dev(CIRCL_HIP_HPKE_RECEIVER_, const ui
 #define CIRCL_HIP_KERNEL_HPKE_SETUP 26     /* HPKE setup (DHKEM + key schedule) and the single-shot forms */
 #define CIRCL_HIP_KERNEL_HPKE_AEAD 27      /* HPKE Seal / Open on context rows (ChaCha20-Poly1305) */
 #define CIRCL_HIP_KERNEL_HPKE_EXPORT 28    /* HPKE Export on context rows              */
-#define CIRCL_HIP_KERNEL_COUNT 29
+#define CIRCL_HIP_KERNEL_OPRF_HASH_TO_GROUP 29   /* ristretto255 HashToElement      */
+#define CIRCL_HIP_KERNEL_OPRF_HASH_TO_SCALAR 30  /* ristretto255 HashToScalar       */
+#define CIRCL_HIP_KERNEL_OPRF_SCALAR_MULT 31     /* ristretto255 scalar multiplication */
+#define CIRCL_HIP_KERNEL_OPRF_DERIVE_KEYPAIR 32  /* OPRF DeriveKey                  */
+#define CIRCL_HIP_KERNEL_OPRF_BLIND 33           /* OPRF DeterministicBlind         */
+#define CIRCL_HIP_KERNEL_OPRF_EVALUATE 34        /* OPRF Evaluate (base mode)       */
+#define CIRCL_HIP_KERNEL_OPRF_FINALIZE 35        /* OPRF Finalize (base mode)       */
+#define CIRCL_HIP_KERNEL_OPRF_FULL_EVALUATE 36   /* OPRF FullEvaluate               */
+#define CIRCL_HIP_KERNEL_COUNT 37
 int circl_hip_profile_enable(int on);
 int circl_hip_profile_read(int kernel, double *total_ms, uint64_t *launches);
 /* The VALU issue rates this chip sustains, measured live (bench.py prices the kernels' VALU time against them instead of against
