@@ -432,9 +432,12 @@ static void absorb_msg(orc_sponge *h, const uint8_t *msg, size_t msglen, const u
     orc_sponge_absorb(h, msg, msglen);
 }
 
-/* dilithium.go:340-470 SignTo */
-int orc_mldsa_sign(int param, const uint8_t *skbuf, const uint8_t *msg, size_t msglen,
-                   const uint8_t *ctx, size_t ctxlen, const uint8_t rnd[32], int internal, uint8_t *sig) {
+/* dilithium.go:340-470 SignTo.  With `attempts` set it also reports how many attempts the rejection loop took and, for each
+ * rejected one, the first check that rejected it (causes[a], at most `cap` of them): 1 = |w0 - c s2| (:419), 2 = |z| (:432),
+ * 3 = |c t0| (:444), 4 = more than omega hints (:461-462) -- the order of the checks below. */
+static int sign_loop(int param, const uint8_t *skbuf, const uint8_t *msg, size_t msglen,
+                     const uint8_t *ctx, size_t ctxlen, const uint8_t rnd[32], int internal, uint8_t *sig,
+                     uint32_t *attempts, uint8_t *causes, size_t cap) {
     dparams P;
     if (dil_params(param, &P)) return -1;
     if (ctxlen > 255) return -2;
@@ -455,6 +458,7 @@ int orc_mldsa_sign(int param, const uint8_t *skbuf, const uint8_t *msg, size_t m
 
     dpoly y[7], yh[7], z[7], w[8], w0[8], w1[8], w0mcs2[8], ct0[8], hint[8], ch, tmp;
     uint16_t ynonce = 0;
+#define SIGN_REJECT(why) do { if (causes && (size_t)(attempt - 1) < cap) causes[attempt - 1] = (why); } while (0)
     for (int attempt = 1;; attempt++) {
         if (attempt >= 576) return -3;
         for (int i = 0; i < P.l; i++) dpoly_legamma1(&y[i], rhop, (uint16_t)(ynonce + i), &P);
@@ -483,7 +487,7 @@ int orc_mldsa_sign(int param, const uint8_t *skbuf, const uint8_t *msg, size_t m
             dpoly_normalize(&w0mcs2[i]);
             bad |= dpoly_exceeds(&w0mcs2[i], P.gamma2 - P_BETA(&P));
         }
-        if (bad) continue;
+        if (bad) { SIGN_REJECT(1); continue; }
         for (int i = 0; i < P.l; i++) {
             dpoly_mulhat(&z[i], &ch, &sk.s1h[i]);
             dpoly_invntt(&z[i]);
@@ -491,14 +495,14 @@ int orc_mldsa_sign(int param, const uint8_t *skbuf, const uint8_t *msg, size_t m
             dpoly_normalize(&z[i]);
             bad |= dpoly_exceeds(&z[i], P_GAMMA1(&P) - P_BETA(&P));
         }
-        if (bad) continue;
+        if (bad) { SIGN_REJECT(2); continue; }
         for (int i = 0; i < P.k; i++) {
             dpoly_mulhat(&ct0[i], &ch, &sk.t0h[i]);
             dpoly_invntt(&ct0[i]);
             dpoly_normalize_le2q(&ct0[i]);
             bad |= dpoly_exceeds(&ct0[i], P.gamma2);
         }
-        if (bad) continue;
+        if (bad) { SIGN_REJECT(3); continue; }
         uint32_t pop = 0;
         for (int i = 0; i < P.k; i++) {
             dpoly_add(&tmp, &w0mcs2[i], &ct0[i]);
@@ -509,15 +513,32 @@ int orc_mldsa_sign(int param, const uint8_t *skbuf, const uint8_t *msg, size_t m
                 pop += hb;
             }
         }
-        if (pop > (uint32_t)P.omega) continue;
+        if (pop > (uint32_t)P.omega) { SIGN_REJECT(4); continue; }
+        if (attempts) *attempts = (uint32_t)attempt;
         break;
     }
+#undef SIGN_REJECT
     /* dilithium.go:84-88 unpackedSignature.Pack */
     memcpy(sig, ct, (size_t)P.ctilde);
     uint8_t *o = sig + P.ctilde;
     for (int i = 0; i < P.l; i++, o += P_LEGAMMA1_SZ(&P)) pack_legamma1(o, &z[i], &P);
     pack_hint(o, hint, &P);
     return 0;
+}
+
+int orc_mldsa_sign(int param, const uint8_t *skbuf, const uint8_t *msg, size_t msglen,
+                   const uint8_t *ctx, size_t ctxlen, const uint8_t rnd[32], int internal, uint8_t *sig) {
+    return sign_loop(param, skbuf, msg, msglen, ctx, ctxlen, rnd, internal, sig, NULL, NULL, 0);
+}
+
+/* The same loop and the same signature as orc_mldsa_sign, plus its trace: *attempts = the number of the accepted attempt (1 = the
+ * first one passed), causes[0 .. *attempts - 2] = the check that rejected each earlier attempt (1..4, see sign_loop).  -3 as in
+ * orc_mldsa_sign when the loop gives up; then *attempts is not written. */
+int orc_mldsa_sign_trace(int param, const uint8_t *skbuf, const uint8_t *msg, size_t msglen,
+                         const uint8_t *ctx, size_t ctxlen, const uint8_t rnd[32], int internal, uint8_t *sig,
+                         uint32_t *attempts, uint8_t *causes, size_t cap) {
+    if (!attempts) return -1;
+    return sign_loop(param, skbuf, msg, msglen, ctx, ctxlen, rnd, internal, sig, attempts, causes, cap);
 }
 
 /* dilithium.go:114-126 PublicKey.Unpack + :273-332 Verify (+ :90-105 sig.Unpack) */

@@ -72,6 +72,11 @@ int orc_mldsa_keygen(int param, const uint8_t seed[32], uint8_t *pk, uint8_t *sk
  * ACVP vectors use); internal = 0: M' = 0 || len(ctx) || ctx || msg. */
 int orc_mldsa_sign(int param, const uint8_t *sk, const uint8_t *msg, size_t msglen,
                    const uint8_t *ctx, size_t ctxlen, const uint8_t rnd[32], int internal, uint8_t *sig);
+/* orc_mldsa_sign with its trace: *attempts = the accepted attempt's number (from 1), causes[a] = which check rejected attempt a + 1
+ * (1 |w0 - c s2|, 2 |z|, 3 |c t0|, 4 hint weight), at most cap entries */
+int orc_mldsa_sign_trace(int param, const uint8_t *sk, const uint8_t *msg, size_t msglen,
+                         const uint8_t *ctx, size_t ctxlen, const uint8_t rnd[32], int internal, uint8_t *sig,
+                         uint32_t *attempts, uint8_t *causes, size_t cap);
 int orc_mldsa_verify(int param, const uint8_t *pk, const uint8_t *msg, size_t msglen,
                      const uint8_t *ctx, size_t ctxlen, int internal, const uint8_t *sig, size_t siglen);
 int orc_mldsa_keygen_batch(int param, const uint8_t *seed, uint8_t *pk, uint8_t *sk, size_t n, int threads);

@@ -321,6 +321,7 @@ def mldsa_sign(param, sk, msgs, ctxs=None, rnd=None, threads=None):
     _, SK, SIG = DSA_SIZES[param]
     sk = _u8(sk).reshape(-1, SK)
     n = len(sk)
+    assert len(msgs) == n
     mb, mo = _blob(msgs)
     cb, co = _blob(ctxs if ctxs is not None else [b""] * n)
     rnd = np.zeros((n, 32), np.uint8) if rnd is None else _u8(rnd).reshape(n, 32)
@@ -335,6 +336,7 @@ def mldsa_verify(param, pk, sig, msgs, ctxs=None, threads=None):
     pk = _u8(pk).reshape(-1, PK)
     sig = _u8(sig).reshape(-1, SIG)
     n = len(pk)
+    assert len(msgs) == n and len(sig) == n
     mb, mo = _blob(msgs)
     cb, co = _blob(ctxs if ctxs is not None else [b""] * n)
     ok = np.zeros(n, np.uint8)
@@ -350,6 +352,26 @@ def mldsa_sign_one(param, sk, msg, ctx=b"", rnd=bytes(32), internal=False):
     r = lib().orc_mldsa_sign(param, _p(sk), _p(msg_a), C.c_size_t(len(msg)), _p(ctx_a), C.c_size_t(len(ctx)), _p(rnd), C.c_int(int(internal)), _p(sig))
     assert r == 0, r
     return sig.tobytes()
+
+
+SIGN_CAUSES = {1: "w0-cs2", 2: "z", 3: "ct0", 4: "hints"}  # the order of the checks in oracle/dilithium.c sign_loop
+
+
+def mldsa_sign_trace(param, sk, msg, ctx=b"", rnd=bytes(32), internal=False):
+    """mldsa_sign_one with the rejection loop's trace -> (sig, attempts, causes): attempts = the number of the accepted attempt,
+    causes = the check (a key of SIGN_CAUSES) that rejected each of the attempts - 1 earlier ones.  None when the oracle gives up."""
+    _, SK, SIG = DSA_SIZES[param]
+    sk = _u8(bytes(sk)); msg_a = _u8(bytes(msg) + b"\0"); ctx_a = _u8(bytes(ctx) + b"\0"); rnd = _u8(bytes(rnd))
+    assert len(sk) == SK
+    sig = np.zeros(SIG, np.uint8)
+    att = C.c_uint32(0)
+    causes = np.zeros(576, np.uint8)
+    r = lib().orc_mldsa_sign_trace(param, _p(sk), _p(msg_a), C.c_size_t(len(msg)), _p(ctx_a), C.c_size_t(len(ctx)), _p(rnd), C.c_int(int(internal)), _p(sig),
+                                   C.byref(att), _p(causes), C.c_size_t(len(causes)))
+    if r == -3:
+        return None
+    assert r == 0, r
+    return sig.tobytes(), int(att.value), causes[:att.value - 1].tolist()
 
 
 def mldsa_verify_one(param, pk, msg, sig, ctx=b"", internal=False):
