@@ -882,18 +882,18 @@ int coalescer_async_start(Coalescer *co, const std::vector<HIn> &ins, const std:
     return CIRCL_HIP_OK;
 }
 
-int coalesce_submit(Coalescer *co, size_t n, const std::vector<HIn> &ins, const std::vector<HBlob> &blobs, const std::vector<HOut> &outs, uint64_t *seq,
-                    bool may_wait) {
+namespace {
+// A call into the queue of an asynchronous coalescer.  kNotCoalesced: it cannot join (admissible) -- what that means is the caller's to
+// say: a *_submit entry point has no other path and refuses (coalesce_submit), a blocking call takes the pipeline (coalesce_run).
+int submit_call(Coalescer *co, size_t n, const std::vector<HIn> &ins, const std::vector<HBlob> &blobs, const std::vector<HOut> &outs, uint64_t *seq,
+                bool may_wait) {
     if (seq) *seq = 0;
     if (!co || !co->async || !seq) return CIRCL_HIP_EPARAM;
     if (n == 0) return CIRCL_HIP_OK;  // (ticket 0 is always done)
     if (n > co->call_max) { g_err = "more items than a submitted call may hold (max_items / 4)"; return CIRCL_HIP_EPARAM; }
     ActiveCall guard(co);
     size_t bb[kMaxBlobs] = {0, 0};
-    if (int rc = admissible(co, n, ins, blobs, outs, bb)) {
-        if (rc == kNotCoalesced) { g_err = "this call cannot join the table's queue (a message beyond a quarter of the blob area, or other arrays than the queue's)"; return CIRCL_HIP_EPARAM; }
-        return rc;
-    }
+    if (int rc = admissible(co, n, ins, blobs, outs, bb)) return rc;
     size_t pos = 0, bpos[kMaxBlobs] = {0, 0};
     bool opened = false;
     CoBatch *b = reserve(co, n, bb, pos, bpos, opened, may_wait);
@@ -908,6 +908,16 @@ int coalesce_submit(Coalescer *co, size_t n, const std::vector<HIn> &ins, const 
     if (opened) wake_dispatcher(co);
     *seq = ticket;
     return CIRCL_HIP_OK;
+}
+}  // namespace
+
+// what the *_submit entry points of the C ABI call: a call that cannot join the queue is refused
+int coalesce_submit(Coalescer *co, size_t n, const std::vector<HIn> &ins, const std::vector<HBlob> &blobs, const std::vector<HOut> &outs, uint64_t *seq,
+                    bool may_wait) {
+    const int rc = submit_call(co, n, ins, blobs, outs, seq, may_wait);
+    if (rc != kNotCoalesced) return rc;
+    g_err = "this call cannot join the table's queue (a message beyond a quarter of the blob area, or other arrays than the queue's)";
+    return CIRCL_HIP_EPARAM;
 }
 int coalescer_state(const Coalescer *co, uint64_t seq) {
     if (!co || !co->async) return CIRCL_HIP_EPARAM;
@@ -949,8 +959,8 @@ int coalesce_run(Coalescer *co, size_t n, const std::vector<HIn> &ins, const std
     if (!co || n > co->call_max || blobs.size() > (size_t)kMaxBlobs || outs.size() > (size_t)kMaxOuts || ragged_or_padded(blobs, outs)) return kNotCoalesced;
     if (co->async) {  // a blocking call through a table whose queue is asynchronous: submit, then wait for the ticket
         uint64_t seq = 0;
-        const int rc = coalesce_submit(co, n, ins, blobs, outs, &seq, true);
-        if (rc != CIRCL_HIP_OK) return rc;
+        const int rc = submit_call(co, n, ins, blobs, outs, &seq, true);
+        if (rc != CIRCL_HIP_OK) return rc;  // (kNotCoalesced among them: a call too long for the queue is the pipeline's, as without a queue)
         const int s = coalescer_wait(co, seq, -1);
         return s == 1 ? CIRCL_HIP_OK : s;
     }

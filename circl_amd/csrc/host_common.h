@@ -225,7 +225,8 @@ int coalesce_run(Coalescer *co, size_t n, const std::vector<HIn> &ins, const std
 // every call) and starts its dispatcher thread; coalesce_submit copies a call's rows in, records where its results go and returns a
 // ticket sequence number at once (CIRCL_HIP_EAGAIN when every batch is busy and may_wait is false); coalescer_state: 1 done, 0 pending,
 // < 0 the batch failed; coalescer_wait blocks the ONE thread that calls it until the ticket is done or timeout_us passed (< 0: no limit).
-// coalesce_run on such a coalescer is submit + wait.
+// coalesce_run on such a coalescer is submit + wait.  A call that cannot join the queue (too many blob bytes, other arrays than the queue's)
+// is CIRCL_HIP_EPARAM from coalesce_submit, which has no other path, and kNotCoalesced from coalesce_run, whose caller has the pipeline.
 int coalescer_async_start(Coalescer *co, const std::vector<HIn> &ins, const std::vector<HBlob> &blobs, const std::vector<HOut> &outs,
                           const std::function<size_t(size_t)> &ws_bytes, const PipeOpts &opts, const std::function<int(Chunk &)> &launch, bool want_eventfd);
 int coalesce_submit(Coalescer *co, size_t n, const std::vector<HIn> &ins, const std::vector<HBlob> &blobs, const std::vector<HOut> &outs, uint64_t *seq,

@@ -286,7 +286,9 @@ int circl_hip_keytable_set_coalesce(circl_hip_keytable *table, size_t max_items,
  *       ticket says which: the top byte).
  *   circl_hip_keytable_async_stop(table): flushes and finishes every submitted call, stops the dispatchers, frees the queues
  *       (CIRCL_HIP_EBUSY while a call is inside the table: a *_submit, a circl_hip_poll, a thread blocked in circl_hip_wait); circl_hip_keytable_free does the same on the way.
- * The blocking *_table calls keep working on such a table (they submit and wait), so one table can serve both kinds of caller. */
+ * The blocking *_table calls keep working on such a table (they submit and wait), so one table can serve both kinds of caller.
+ * A blocking call that is too large for a batch (more than max_items / 4 items, or messages beyond a quarter of a batch's blob
+ * area) runs on its own, through the ordinary path, as it does on a table without a queue; only *_submit refuses such a call. */
 int circl_hip_keytable_close(circl_hip_keytable *table);
 int circl_hip_keytable_async_start(circl_hip_keytable *table, size_t max_items, uint32_t max_wait_us, int want_eventfd);
 int circl_hip_keytable_async_stop(circl_hip_keytable *table);
