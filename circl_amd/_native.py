@@ -61,8 +61,9 @@ SYMBOLS = [
                      "circl_hip_hpke_seal_single", "circl_hip_hpke_open_single", "circl_hip_hpke_export_single", "circl_hip_hpke_export_single_receiver")
      for d in ("", "_dev")] + [f + d for f in ("circl_hip_ristretto255_hash_to_group", "circl_hip_ristretto255_hash_to_scalar", "circl_hip_ristretto255_scalar_mult",
                                "circl_hip_oprf_derive_keypair", "circl_hip_oprf_blind", "circl_hip_oprf_evaluate", "circl_hip_oprf_finalize",
-                               "circl_hip_oprf_full_evaluate")
-                  for d in ("", "_dev")]
+                               "circl_hip_oprf_full_evaluate", "circl_hip_dleq_prove", "circl_hip_dleq_verify", "circl_hip_oprf_poprf_tweak",
+                               "circl_hip_oprf_poprf_finalize", "circl_hip_oprf_poprf_full_evaluate")
+                  for d in ("", "_dev")] + ["circl_hip_dleq_workspace_size"]
 
 OK, EPARAM, ENODEV, EHIP, ENOMEM, EWORKSPACE, EBUSY, EAGAIN = 0, -1, -2, -3, -4, -5, -6, -7
 ALL_DEVICES = -1
@@ -268,6 +269,17 @@ def lib():
                            ("ristretto255_scalar_mult", [vp, sz, vp, u32, vp, vp]), ("oprf_derive_keypair", [i, vp, vp, vp, vp, vp, vp]),
                            ("oprf_blind", [i, vp, vp, vp, vp, vp]), ("oprf_evaluate", [vp, sz, vp, vp, vp]),
                            ("oprf_finalize", [vp, vp, vp, vp, vp, vp]), ("oprf_full_evaluate", [i, vp, sz, vp, vp, vp, vp])):
+            getattr(L, "circl_hip_" + name).argtypes = args + [sz, i]
+            getattr(L, "circl_hip_" + name + "_dev").argtypes = args + [sz, vp]
+        dleq = [vp, sz, vp, vp, vp]      # kA and its stride, B, kB, req_off
+        tail = [vp, sz, u32]             # dst, dst_len, flags
+        L.circl_hip_dleq_workspace_size.restype, L.circl_hip_dleq_workspace_size.argtypes = sz, [sz, sz]
+        L.circl_hip_dleq_prove.argtypes = [vp, sz] + dleq + [vp] + tail + [vp, vp, sz, i]
+        L.circl_hip_dleq_prove_dev.argtypes = [vp, sz] + dleq + [vp] + tail + [vp, vp, sz, sz, vp, sz, vp]
+        L.circl_hip_dleq_verify.argtypes = dleq + [vp] + tail + [vp, sz, i]
+        L.circl_hip_dleq_verify_dev.argtypes = dleq + [vp] + tail + [vp, sz, sz, vp, sz, vp]
+        for name, args in (("oprf_poprf_tweak", [vp, sz, vp, sz, vp, vp, vp, vp, vp, vp]), ("oprf_poprf_finalize", [vp] * 8),
+                           ("oprf_poprf_full_evaluate", [vp, sz] + [vp] * 6)):
             getattr(L, "circl_hip_" + name).argtypes = args + [sz, i]
             getattr(L, "circl_hip_" + name + "_dev").argtypes = args + [sz, vp]
         for f in ("seed", "eseed", "pk", "sk", "ct", "ss"):

@@ -19,7 +19,8 @@ KERNELS = {"mlkem_hash": 0, "mlkem_encrypt": 1, "mlkem_decrypt": 2, "mlkem_keyge
            "frodo_keygen": 20, "frodo_encaps": 21, "frodo_decaps": 22,
            "hpke_x25519": 23, "hpke_x448": 24, "sha256": 25, "hpke_setup": 26, "hpke_aead": 27, "hpke_export": 28,
            "oprf_hash_to_group": 29, "oprf_hash_to_scalar": 30, "oprf_scalar_mult": 31, "oprf_derive_keypair": 32, "oprf_blind": 33, "oprf_evaluate": 34,
-           "oprf_finalize": 35, "oprf_full_evaluate": 36}
+           "oprf_finalize": 35, "oprf_full_evaluate": 36, "dleq_composite": 37, "dleq_finish": 38, "oprf_poprf_tweak": 39,
+           "oprf_poprf_finalize": 40, "oprf_poprf_full_evaluate": 41}
 
 
 def _stream():
@@ -566,3 +567,100 @@ class OprfDevice:
         nat.check(self.L.circl_hip_oprf_full_evaluate_dev(mode, *self._scalars(sk, n), *_rag_args(inputs), _chk(out), _chk(ok), n, _stream()),
                   "oprf_full_evaluate_dev")
         return out, ok
+
+    # ---- batch DLEQ proofs and the verifiable modes (circl_hip_dleq_*_dev, circl_hip_oprf_poprf_*_dev) ----
+    @staticmethod
+    def _ctx(mode):
+        return b"OPRFV1-" + bytes([mode]) + b"-ristretto255-SHA512"
+
+    def _requests(self, req_off):
+        """(offsets on the device as an int64 tensor, n_req, n_elems, elements per request as a device tensor) of host offsets"""
+        import numpy as np
+        off = np.ascontiguousarray(req_off, dtype=np.int64)
+        off_d = torch.from_numpy(off).to(self.device)
+        return off_d, len(off) - 1, int(off[-1] - off[0]), off_d[1:] - off_d[:-1]
+
+    def _dleq(self, verify, k, kA, B, kB, req_off, r, proofs, dst, flags):
+        import numpy as np
+        off_d, n, n_el, _ = self._requests(req_off)
+        d = np.frombuffer(bytes(dst) + b"\0", np.uint8)
+        wsb = self.L.circl_hip_dleq_workspace_size(n, n_el)
+        ws, ok = self._out(max(wsb, 256)), self._out(n)
+        tail = (d.ctypes.data_as(C.c_void_p), len(dst), flags)
+        common = (*self._scalars(kA, n), _chk(B, 32), _chk(kB, 32), off_d.data_ptr())
+        if verify:
+            nat.check(self.L.circl_hip_dleq_verify_dev(*common, _chk(proofs, 64), *tail, _chk(ok), n, n_el, _chk(ws), wsb, _stream()), "dleq_verify_dev")
+            return ok
+        proofs = self._out(n, 64)
+        nat.check(self.L.circl_hip_dleq_prove_dev(*self._scalars(k, n), *common, _chk(r, 32), *tail, _chk(proofs), _chk(ok), n, n_el, _chk(ws), wsb,
+                                                  _stream()), "dleq_prove_dev")
+        return proofs, ok
+
+    def dleq_prove(self, k, kA, B, kB, req_off, r, dst, flags=0):
+        """req_off: n_req + 1 HOST offsets in elements -> (proofs (n_req, 64), ok (n_req,))"""
+        return self._dleq(False, k, kA, B, kB, req_off, r, None, dst, flags)
+
+    def dleq_verify(self, kA, B, kB, req_off, proofs, dst, flags=0):
+        return self._dleq(True, None, kA, B, kB, req_off, None, proofs, dst, flags)
+
+    def poprf_tweak(self, infos, n, sk=None, pkS=None):
+        """with sk -> (t, t_inv, t G, ok); with pkS -> (tweaked key, ok)"""
+        assert (sk is None) != (pkS is None)
+        t, tinv, tw, ok = self._out(n, 32), self._out(n, 32), self._out(n, 32), self._out(n)
+        if pkS is None:
+            nat.check(self.L.circl_hip_oprf_poprf_tweak_dev(*self._scalars(sk, n), None, 0, *_rag_args(infos), _chk(t), _chk(tinv), _chk(tw), _chk(ok), n,
+                                                            _stream()), "oprf_poprf_tweak_dev")
+            return t, tinv, tw, ok
+        nat.check(self.L.circl_hip_oprf_poprf_tweak_dev(None, 0, *self._scalars(pkS, n), *_rag_args(infos), None, None, _chk(tw), _chk(ok), n, _stream()),
+                  "oprf_poprf_tweak_dev")
+        return tw, ok
+
+    def poprf_finalize(self, inputs, infos, blinds, evaluated):
+        n = blinds.shape[0]
+        out, ok = self._out(n, 64), self._out(n)
+        nat.check(self.L.circl_hip_oprf_poprf_finalize_dev(*_rag_args(inputs), *_rag_args(infos), _chk(blinds, 32), _chk(evaluated, 32), _chk(out), _chk(ok), n,
+                                                           _stream()), "oprf_poprf_finalize_dev")
+        return out, ok
+
+    def poprf_full_evaluate(self, sk, inputs, infos, n):
+        out, ok = self._out(n, 64), self._out(n)
+        nat.check(self.L.circl_hip_oprf_poprf_full_evaluate_dev(*self._scalars(sk, n), *_rag_args(inputs), *_rag_args(infos), _chk(out), _chk(ok), n,
+                                                                _stream()), "oprf_poprf_full_evaluate_dev")
+        return out, ok
+
+    def evaluate_verifiable(self, mode, sk, blinded, req_off, r, info=b""):
+        """The verifiable server's Evaluate of modes 1 and 2 for n_req requests under one key (and one info) -> (evaluated, proofs, ok per
+        request); a failed request has a zero proof row and zero evaluated rows."""
+        assert mode in (1, 2)
+        _, n, n_el, counts = self._requests(req_off)
+        if mode == 1:
+            k = sk.reshape(1, 32)
+            kA, key_ok = self.scalar_mult(k, n=1)
+            evaluated, _ = self.evaluate(k, blinded)
+            B, kB = blinded, evaluated
+        else:
+            k, tinv, kA, key_ok = self.poprf_tweak(Ragged([info], self.device), 1, sk=sk.reshape(1, 32))
+            evaluated, _ = self.evaluate(tinv, blinded)
+            B, kB = evaluated, blinded
+        proofs, ok = self.dleq_prove(k, kA, B, kB, req_off, r, self._ctx(mode), 1)
+        ok = ok & key_ok[0]
+        proofs = proofs * ok[:, None]
+        return evaluated * torch.repeat_interleave(ok, counts)[:, None], proofs, ok
+
+    def finalize_verifiable(self, mode, pkS, inputs, blinds, blinded, evaluated, req_off, proofs, info=b""):
+        """The verifiable client's Finalize of modes 1 and 2 -> (outputs (n_elems, 64), ok per request); the outputs of EVERY element of a request
+        whose proof or any element failed are zero.  inputs: a Ragged of n_elems items."""
+        assert mode in (1, 2)
+        off_d, n, n_el, counts = self._requests(req_off)
+        shared = lambda t: t.reshape(1, 32)
+        if mode == 1:
+            ok = self.dleq_verify(shared(pkS), blinded, evaluated, req_off, proofs, self._ctx(mode), 1)
+            out, item_ok = self.finalize(inputs, blinds, evaluated)
+        else:
+            tweaked, key_ok = self.poprf_tweak(Ragged([info], self.device), 1, pkS=pkS.reshape(1, 32))
+            ok = self.dleq_verify(shared(tweaked), evaluated, blinded, req_off, proofs, self._ctx(mode), 1) & key_ok[0]
+            out, item_ok = self.poprf_finalize(inputs, Ragged([info] * n_el, self.device), blinds, evaluated)
+        failed = torch.zeros(n, dtype=torch.int64, device=self.device)
+        failed.index_add_(0, torch.repeat_interleave(torch.arange(n, device=self.device), counts), (item_ok == 0).to(torch.int64))
+        ok = ok & (failed == 0).to(torch.uint8)
+        return out * torch.repeat_interleave(ok, counts)[:, None], ok

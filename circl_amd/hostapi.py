@@ -1222,3 +1222,140 @@ def oprf_full_evaluate(mode, sk, inputs, device=0):
     (key, stride), (ib, io), out, ok = _scalar_rows(sk, n), _blob(inputs), np.empty((n, 64), np.uint8), np.empty(n, np.uint8)
     nat.check(nat.lib().circl_hip_oprf_full_evaluate(mode, _p(key), stride, _p(ib), _p(io), _p(out), _p(ok), n, device), "oprf_full_evaluate")
     return out, ok
+
+
+# ---- batch DLEQ proofs (zk/dleq, the ...RFC9497 forms) and the verifiable modes of OPRF (VOPRF, POPRF) --------------------------------
+DLEQ_NO_IDENTITY = 1
+
+
+def oprf_context_string(mode):
+    return b"OPRFV1-" + bytes([mode]) + b"-ristretto255-SHA512"
+
+
+def _req_off(req_off):
+    off = np.ascontiguousarray(req_off, dtype=np.uint64)
+    if off.ndim != 1 or len(off) < 1:
+        raise ValueError("req_off: need n_req + 1 offsets")
+    return off, len(off) - 1
+
+
+def _elems(x, off):
+    a = _u8(x, 32) if len(x) else np.zeros((0, 32), np.uint8)
+    if len(a) != int(off[-1]):
+        raise ValueError("%d element rows, the offsets end at %d" % (len(a), int(off[-1])))
+    return a if len(a) else np.zeros((1, 32), np.uint8)      # (an address even for a call of empty requests)
+
+
+def dleq_prove(k, kA, B, kB, req_off, r, dst, flags=0, device=0):
+    """ProveBatchWithRandomnessRFC9497 per request -> (proofs (n_req, 64), ok (n_req,)).  Request g owns element rows req_off[g] .. req_off[g+1]
+    of B and kB; k and kA: one row for the call or n_req rows; r: n_req rows drawn by the caller; dst: the caller's tag (0 .. 242 bytes)."""
+    off, n = _req_off(req_off)
+    (key, ks), (pub, ps), r, B, kB = _scalar_rows(k, n), _scalar_rows(kA, n), _u8(r, 32), _elems(B, off), _elems(kB, off)
+    if len(r) != n:
+        raise ValueError("dleq_prove: %d requests, %d rows of randomness" % (n, len(r)))
+    d, proofs, ok = np.frombuffer(bytes(dst) + b"\0", np.uint8), np.empty((n, 64), np.uint8), np.empty(n, np.uint8)
+    nat.check(nat.lib().circl_hip_dleq_prove(_p(key), ks, _p(pub), ps, _p(B), _p(kB), _p(off), _p(r), _p(d), len(dst), flags, _p(proofs), _p(ok), n, device),
+              "dleq_prove")
+    return proofs, ok
+
+
+def dleq_verify(kA, B, kB, req_off, proofs, dst, flags=0, device=0):
+    """VerifyBatchRFC9497 per request -> ok (n_req,), the verdicts"""
+    off, n = _req_off(req_off)
+    (pub, ps), proofs, B, kB = _scalar_rows(kA, n), _u8(proofs, 64), _elems(B, off), _elems(kB, off)
+    if len(proofs) != n:
+        raise ValueError("dleq_verify: %d requests, %d proofs" % (n, len(proofs)))
+    d, ok = np.frombuffer(bytes(dst) + b"\0", np.uint8), np.empty(n, np.uint8)
+    nat.check(nat.lib().circl_hip_dleq_verify(_p(pub), ps, _p(B), _p(kB), _p(off), _p(proofs), _p(d), len(dst), flags, _p(ok), n, device), "dleq_verify")
+    return ok
+
+
+def oprf_poprf_tweak(infos, sk=None, pkS=None, device=0):
+    """mode 2.  With sk (secretFromInfo) -> (t, t_inv, t G, ok); with pkS (pointFromInfo) -> (tweaked key, ok).  One key or n rows."""
+    n = len(infos)
+    if (sk is None) == (pkS is None):
+        raise ValueError("oprf_poprf_tweak: give sk or pkS")
+    (ib, io), ok = _blob(infos), np.empty(n, np.uint8)
+    key, stride = _scalar_rows(sk if pkS is None else pkS, n)
+    t, tinv, tw = (np.empty((n, 32), np.uint8) for _ in range(3))
+    if pkS is None:
+        nat.check(nat.lib().circl_hip_oprf_poprf_tweak(_p(key), stride, None, 0, _p(ib), _p(io), _p(t), _p(tinv), _p(tw), _p(ok), n, device), "oprf_poprf_tweak")
+        return t, tinv, tw, ok
+    nat.check(nat.lib().circl_hip_oprf_poprf_tweak(None, 0, _p(key), stride, _p(ib), _p(io), None, None, _p(tw), _p(ok), n, device), "oprf_poprf_tweak")
+    return tw, ok
+
+
+def oprf_poprf_finalize(inputs, infos, blinds, evaluated, device=0):
+    """PartialObliviousClient.Finalize without the proof -> (outputs (n, 64), ok (n,))"""
+    blinds, evaluated = _u8(blinds, 32), _u8(evaluated, 32)
+    n = len(blinds)
+    if len(evaluated) != n:
+        raise ValueError("oprf_poprf_finalize: %d blinds, %d evaluated elements" % (n, len(evaluated)))
+    (ib, io), (fb, fo), out, ok = _rag(inputs, n), _rag(infos, n), np.empty((n, 64), np.uint8), np.empty(n, np.uint8)
+    nat.check(nat.lib().circl_hip_oprf_poprf_finalize(_po(ib), _po(io), _po(fb), _po(fo), _p(blinds), _p(evaluated), _p(out), _p(ok), n, device),
+              "oprf_poprf_finalize")
+    return out, ok
+
+
+def oprf_poprf_full_evaluate(sk, inputs, infos, device=0):
+    """PartialObliviousServer.FullEvaluate -> (outputs (n, 64), ok (n,)); sk as in oprf_evaluate"""
+    n = len(inputs)
+    (key, stride), (ib, io), (fb, fo), out, ok = _scalar_rows(sk, n), _blob(inputs), _rag(infos, n), np.empty((n, 64), np.uint8), np.empty(n, np.uint8)
+    nat.check(nat.lib().circl_hip_oprf_poprf_full_evaluate(_p(key), stride, _p(ib), _p(io), _po(fb), _po(fo), _p(out), _p(ok), n, device),
+              "oprf_poprf_full_evaluate")
+    return out, ok
+
+
+def _per_element(off, rows):
+    """the per-request rows repeated for every element of their request"""
+    return np.repeat(rows, np.diff(off.astype(np.int64)), axis=0)
+
+
+def oprf_evaluate_verifiable(mode, sk, blinded, req_off, r, info=b"", device=0):
+    """VerifiableServer.Evaluate (mode 1) / PartialObliviousServer.Evaluate (mode 2) for n_req requests under ONE key (and one info) ->
+    (evaluated (n_elems, 32), proofs (n_req, 64), ok (n_req,)).  r: the proof randomness, one row per request, drawn by the caller.  A request
+    with a failed element or proof has ok = 0, a zero proof row and zero evaluated rows."""
+    if mode not in (OPRF_MODE_VOPRF, OPRF_MODE_POPRF):
+        raise ValueError("oprf_evaluate_verifiable: mode 1 or 2")
+    off, n = _req_off(req_off)
+    blinded = _elems(blinded, off)[:int(off[-1])]
+    if mode == OPRF_MODE_VOPRF:
+        k = _u8(sk, 32)[:1]
+        kA, key_ok = ristretto255_scalar_mult(k, n=1, device=device)
+        evaluated, _ = oprf_evaluate(k, blinded, device) if len(blinded) else (blinded, None)
+        B, kB = blinded, evaluated
+    else:
+        k, tinv, kA, key_ok = oprf_poprf_tweak([info], sk=sk, device=device)
+        evaluated, _ = oprf_evaluate(tinv, blinded, device) if len(blinded) else (blinded, None)
+        B, kB = evaluated, blinded
+    proofs, ok = dleq_prove(k, kA, B, kB, off, r, oprf_context_string(mode), DLEQ_NO_IDENTITY, device)
+    ok &= key_ok[0]
+    proofs[ok == 0] = 0
+    evaluated = np.array(evaluated, copy=True)
+    evaluated[_per_element(off, ok) == 0] = 0
+    return evaluated, proofs, ok
+
+
+def oprf_finalize_verifiable(mode, pkS, inputs, blinds, blinded, evaluated, req_off, proofs, info=b"", device=0):
+    """VerifiableClient.Finalize (mode 1) / PartialObliviousClient.Finalize (mode 2) -> (outputs (n_elems, 64), ok (n_req,)).  The outputs of
+    EVERY element of a request whose proof or any element failed are zero."""
+    if mode not in (OPRF_MODE_VOPRF, OPRF_MODE_POPRF):
+        raise ValueError("oprf_finalize_verifiable: mode 1 or 2")
+    off, n = _req_off(req_off)
+    n_el = int(off[-1])
+    blinded, evaluated, blinds = _elems(blinded, off)[:n_el], _elems(evaluated, off)[:n_el], _u8(blinds, 32) if n_el else np.zeros((0, 32), np.uint8)
+    if len(inputs) != n_el or len(blinds) != n_el:
+        raise ValueError("oprf_finalize_verifiable: %d elements, %d inputs, %d blinds" % (n_el, len(inputs), len(blinds)))
+    if mode == OPRF_MODE_VOPRF:
+        ok = dleq_verify(pkS, blinded, evaluated, off, proofs, oprf_context_string(mode), DLEQ_NO_IDENTITY, device)
+        out, item_ok = oprf_finalize(inputs, blinds, evaluated, device) if n_el else (np.zeros((0, 64), np.uint8), np.zeros(0, np.uint8))
+    else:
+        tweaked, key_ok = oprf_poprf_tweak([info], pkS=pkS, device=device)
+        ok = dleq_verify(tweaked, evaluated, blinded, off, proofs, oprf_context_string(mode), DLEQ_NO_IDENTITY, device) & key_ok[0]
+        out, item_ok = oprf_poprf_finalize(inputs, [info] * n_el, blinds, evaluated, device) if n_el else (np.zeros((0, 64), np.uint8), np.zeros(0, np.uint8))
+    failed = np.zeros(n, np.int64)      # elements of each request that finalize refused
+    np.add.at(failed, _per_element(off, np.arange(n)), item_ok == 0)
+    ok = ok & (failed == 0).astype(np.uint8)
+    out = np.array(out, copy=True)
+    out[_per_element(off, ok) == 0] = 0
+    return out, ok

@@ -1,4 +1,4 @@
-// circl/oprf.hpp -- the ristretto255 group and the proof-free part of OPRF (suite ristretto255-SHA512) on top of the HIP batch engine,
+// circl/oprf.hpp -- the ristretto255 group and OPRF, VOPRF and POPRF (suite ristretto255-SHA512) on top of the HIP batch engine,
 // shaped like the reference's group.Ristretto255 (group/ristretto255.go) and oprf package (oprf/keys.go, client.go, server.go), over
 // batches:
 //
@@ -9,11 +9,15 @@
 //   oprf::Server(key).Evaluate(request)                                         -> Evaluation           (base mode)
 //   oprf::Client(mode).Finalize(finalizeData, evaluation)                       -> n outputs of 64 bytes (base mode)
 //   oprf::Server(key).FullEvaluate(inputs) / oprf::VerifiableServer(key).FullEvaluate(inputs)   -> n outputs
-// The library has no random number generator: the caller draws the blinds (the reference's Blind is DeterministicBlind on blinds it
+//   oprf::VerifiableServer(key).Evaluate(request, r) / oprf::PartialObliviousServer(key).Evaluate(request, info, r)  -> Evaluation with its proof
+//   oprf::VerifiableClient(pkS).Finalize(finalizeData, evaluation) / oprf::PartialObliviousClient(pkS).Finalize(.., info)  -> n outputs
+//   oprf::PartialObliviousServer(key).FullEvaluate(inputs, info)                                        -> n outputs
+// A verifiable call is ONE request (the reference's batch under one proof, 1 to 65535 elements); r is the proof's randomness.
+// The library has no random number generator: the caller draws the blinds and r (the reference's Blind is DeterministicBlind on blinds it
 // draws).  As in the reference, a call fails as a whole: an input the protocol refuses throws ErrInvalidInput, a zero or
 // non-canonical scalar or key ErrInvalidScalar, an element that does not decode or is the identity ErrInvalidElement.  Decoding is
-// strict RFC 9496 (include/circl_hip.h).  The verifiable modes' Evaluate / Finalize (with their DLEQ proofs) are not served yet.
-// Everything runs on the GPU behind circl_hip_ristretto255_* and circl_hip_oprf_*.  Link with -lcirclhip.
+// strict RFC 9496 (include/circl_hip.h).  A proof that does not verify throws ErrInvalidProof and no output leaves the call.
+// Everything runs on the GPU behind circl_hip_ristretto255_*, circl_hip_oprf_* and circl_hip_dleq_*.  Link with -lcirclhip.
 #pragma once
 #include <cstdint>
 #include <string>
@@ -40,6 +44,9 @@ struct ErrInvalidElement : kem::Error {
 };
 struct ErrBatchSize : kem::Error {
     ErrBatchSize() : kem::Error("oprf: the batch's arrays differ in their number of items") {}
+};
+struct ErrInvalidProof : kem::Error {
+    ErrInvalidProof() : kem::Error("oprf: the proof does not verify") {}
 };
 struct ErrModeNotServed : kem::Error {
     ErrModeNotServed() : kem::Error("oprf: this operation of the verifiable modes needs a proof and is not served") {}
@@ -169,6 +176,7 @@ struct EvaluationRequest {
 };
 struct Evaluation {
     List Elements;
+    Bytes Proof;  // c || s, 64 bytes: the verifiable modes; empty in base mode
 };
 struct FinalizeData {
     List inputs, blinds;
@@ -261,10 +269,139 @@ public:
     }
 };
 
-// server.go VerifiableServer: FullEvaluate only (its Evaluate carries a proof)
+namespace detail {
+inline Bytes context_string(Mode mode) {
+    const std::string s = std::string("OPRFV1-") + char(mode) + "-ristretto255-SHA512";
+    return Bytes(s.begin(), s.end());
+}
+// one request of n element pairs proven under k (kA = k G): the proof, or ErrInvalidElement / ErrInvalidScalar
+inline Bytes prove(Mode mode, const Bytes &k, const Bytes &kA, const Bytes &B, const Bytes &kB, size_t n, const Bytes &r, int device) {
+    if (r.size() != 32) throw ErrInvalidScalar();
+    const uint64_t off[2] = {0, n};
+    const Bytes ctx = context_string(mode);
+    Bytes proof(64), ok(1);
+    check(circl_hip_dleq_prove(k.data(), 0, kA.data(), 0, B.data(), kB.data(), off, r.data(), ctx.data(), ctx.size(), CIRCL_HIP_DLEQ_NO_IDENTITY, proof.data(),
+                               ok.data(), 1, device));
+    if (!ok[0]) {
+        if (!scalar_usable(k) || !scalar_usable(r)) throw ErrInvalidScalar();
+        throw ErrInvalidElement();
+    }
+    return proof;
+}
+inline bool verify(Mode mode, const Bytes &kA, const Bytes &B, const Bytes &kB, size_t n, const Bytes &proof, int device) {
+    if (proof.size() != 64 || kA.size() != 32) return false;
+    const uint64_t off[2] = {0, n};
+    const Bytes ctx = context_string(mode);
+    Bytes ok(1);
+    check(circl_hip_dleq_verify(kA.data(), 0, B.data(), kB.data(), off, proof.data(), ctx.data(), ctx.size(), CIRCL_HIP_DLEQ_NO_IDENTITY, ok.data(), 1, device));
+    return ok[0] != 0;
+}
+// base-mode evaluation of n elements under the scalar k
+inline Bytes evaluate(const Bytes &k, const Bytes &el, size_t n, int device) {
+    Bytes out(32 * n), ok(n);
+    check(circl_hip_oprf_evaluate(k.data(), 0, el.data(), out.data(), ok.data(), n, device));
+    if (!all_ok(ok)) {
+        if (!scalar_usable(k)) throw ErrInvalidScalar();
+        throw ErrInvalidElement();
+    }
+    return out;
+}
+}  // namespace detail
+
+// server.go VerifiableServer: Evaluate = the base evaluation and one proof for the request
 class VerifiableServer : public ServerBase {
 public:
     explicit VerifiableServer(PrivateKey key, int device = 0) : ServerBase(VerifiableMode, std::move(key), device) {}
+    Evaluation Evaluate(const EvaluationRequest &req, const Bytes &r) const {
+        const size_t n = req.Elements.size();
+        if (n == 0) throw ErrInvalidInput();
+        const Bytes el = detail::rows(req.Elements, n), out = detail::evaluate(key_.k, el, n, device_);
+        return Evaluation{detail::unrows(out, 32), detail::prove(VerifiableMode, key_.k, key_.pub, el, out, n, r, device_)};
+    }
+};
+
+// server.go PartialObliviousServer: the key is tweaked by the info; the proof is under t = sk + m with the roles of the elements swapped
+class PartialObliviousServer : public ServerBase {
+public:
+    explicit PartialObliviousServer(PrivateKey key, int device = 0) : ServerBase(PartialObliviousMode, std::move(key), device) {}
+    Evaluation Evaluate(const EvaluationRequest &req, const Bytes &info, const Bytes &r) const {
+        const size_t n = req.Elements.size();
+        if (n == 0) throw ErrInvalidInput();
+        const detail::Ragged inf(List{info});
+        Bytes t(32), tinv(32), tg(32), ok(1);
+        detail::check(circl_hip_oprf_poprf_tweak(key_.k.data(), 0, nullptr, 0, inf.blob(), inf.offs(), t.data(), tinv.data(), tg.data(), ok.data(), 1, device_));
+        if (!ok[0]) throw ErrInvalidInput();  // ErrInverseZero, an info over 65535 bytes, an unusable key
+        const Bytes el = detail::rows(req.Elements, n), out = detail::evaluate(tinv, el, n, device_);
+        Evaluation e{detail::unrows(out, 32), detail::prove(PartialObliviousMode, t, tg, out, el, n, r, device_)};
+        detail::wipe(t);
+        detail::wipe(tinv);
+        return e;
+    }
+    List FullEvaluate(const List &inputs, const Bytes &info) const {
+        const size_t n = inputs.size();
+        Bytes out(64 * n), ok(n);
+        const detail::Ragged in(inputs), inf(List(n, info));
+        detail::check(circl_hip_oprf_poprf_full_evaluate(key_.k.data(), 0, in.blob(), in.offs(), inf.blob(), inf.offs(), out.data(), ok.data(), n, device_));
+        if (!detail::all_ok(ok)) {
+            detail::wipe(out);
+            throw ErrInvalidInput();
+        }
+        List r = detail::unrows(out, 64);
+        detail::wipe(out);
+        return r;
+    }
+
+private:
+    using ServerBase::FullEvaluate;  // (the form without an info is not POPRF's)
+};
+
+// client.go VerifiableClient: Finalize verifies the proof first; nothing is returned unless it holds
+class VerifiableClient : public Client {
+public:
+    explicit VerifiableClient(PublicKey pkS, int device = 0) : Client(VerifiableMode, device), pk_(std::move(pkS)), dev_(device) {}
+    List Finalize(const FinalizeData &f, const Evaluation &e) const {
+        const size_t n = f.inputs.size();
+        if (n == 0 || e.Elements.size() != n || f.evalReq.Elements.size() != n) throw ErrBatchSize();
+        const Bytes bl = detail::rows(f.evalReq.Elements, n), ev = detail::rows(e.Elements, n);
+        if (!detail::verify(VerifiableMode, pk_.e, bl, ev, n, e.Proof, dev_)) throw ErrInvalidProof();
+        return Client(BaseMode, dev_).Finalize(f, e);  // the same hash as base mode
+    }
+
+private:
+    PublicKey pk_;
+    int dev_;
+};
+
+// client.go PartialObliviousClient
+class PartialObliviousClient : public Client {
+public:
+    explicit PartialObliviousClient(PublicKey pkS, int device = 0) : Client(PartialObliviousMode, device), pk_(std::move(pkS)), dev_(device) {}
+    List Finalize(const FinalizeData &f, const Evaluation &e, const Bytes &info) const {
+        const size_t n = f.inputs.size();
+        if (n == 0 || e.Elements.size() != n || f.evalReq.Elements.size() != n) throw ErrBatchSize();
+        if (pk_.e.size() != 32) throw ErrInvalidElement();
+        const detail::Ragged one(List{info});
+        Bytes tweaked(32), ok1(1);
+        detail::check(circl_hip_oprf_poprf_tweak(nullptr, 0, pk_.e.data(), 0, one.blob(), one.offs(), nullptr, nullptr, tweaked.data(), ok1.data(), 1, dev_));
+        if (!ok1[0]) throw ErrInvalidInput();  // ErrInvalidInfo
+        const Bytes bl = detail::rows(f.evalReq.Elements, n), ev = detail::rows(e.Elements, n);
+        if (!detail::verify(PartialObliviousMode, tweaked, ev, bl, n, e.Proof, dev_)) throw ErrInvalidProof();
+        Bytes b = detail::rows(f.blinds, n), out(64 * n), ok(n);
+        const detail::Ragged in(f.inputs), inf(List(n, info));
+        detail::check(circl_hip_oprf_poprf_finalize(in.blob(), in.offs(), inf.blob(), inf.offs(), b.data(), ev.data(), out.data(), ok.data(), n, dev_));
+        detail::wipe(b);
+        if (!detail::all_ok(ok)) {
+            detail::wipe(out);
+            throw ErrInvalidElement();
+        }
+        List r = detail::unrows(out, 64);
+        detail::wipe(out);
+        return r;
+    }
+
+private:
+    PublicKey pk_;
+    int dev_;
 };
 
 }  // namespace oprf

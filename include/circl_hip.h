@@ -924,7 +924,7 @@ int circl_hip_hpke_export_single_receiver_dev(CIRCL_HIP_HPKE_RECEIVER_, const ui
  *                    "Finalize"); ok = 0 as for blind and evaluate.
  *   full_evaluate:   Server.FullEvaluate (mode 0) / VerifiableServer.FullEvaluate (mode 1) in ONE kernel: neither the hashed point nor
  *                    the evaluated element reaches memory.  Mode 2 needs the info tweak: CIRCL_HIP_EPARAM.
- * evaluate and finalize take no mode: they are base mode; the verifiable forms (with their proofs) are not served yet.
+ * evaluate and finalize take no mode: they are base mode; the verifiable modes are served by the DLEQ block below.
  * ok[i] = 0 means every output row of item i is all zero.  ok may be NULL.  Any other mode, stride or flag is CIRCL_HIP_EPARAM,
  * reported before a device is looked for.  Keys, blinds, seeds, inputs and outputs are wiped from the host forms' staging; the _dev
  * forms want 4-byte aligned rows and 8-byte aligned offsets (CIRCL_HIP_EWORKSPACE otherwise).  n == 0 is CIRCL_HIP_OK. */
@@ -957,6 +957,65 @@ int circl_hip_oprf_finalize_dev(const uint8_t *input_blob, const uint64_t *input
                             size_t n, void *stream);
 int circl_hip_oprf_full_evaluate_dev(int mode, const uint8_t *sk, size_t sk_stride, const uint8_t *input_blob, const uint64_t *input_off, uint8_t *out, uint8_t *ok,
                                  size_t n, void *stream);
+
+/* ---- batch DLEQ proofs (zk/dleq, the ...RFC9497 forms: fixed generator, the base not bound; RFC 9497 section 2.2) on ristretto255,
+ * and the mode-2 (POPRF) items of oprf/client.go and oprf/server.go -------------------------------------------------------------
+ * THE BATCH SHAPE.  A call carries n_req REQUESTS over flat arrays of elements (rows of 32 bytes) and req_off: n_req + 1 uint64_t
+ * offsets counted in ELEMENTS; request g owns elements [req_off[g], req_off[g+1]).  Per-request arguments are rows indexed by g:
+ * keys k, public keys kA, proof randomness r (32 bytes each), proofs (64 bytes: c || s) and ok.  k and kA may be shared by the call
+ * (stride 0) or per request (stride 32); any other stride is CIRCL_HIP_EPARAM.  One proof per request:
+ *   seed = SHA-512(I2(32) || kA || I2(len) || "Seed-" || dst),  d_j = HashToScalar(I2(64) || seed || I2(j) || I2(32) || B_j || I2(32) ||
+ *   kB_j || "Composite"),  M = sum d_j B_j,  Z = k M (prover) or sum d_j kB_j (verifier),  c = HashToScalar(I2(32) || kA || .. M .. Z ..
+ *   t2 .. t3 || "Challenge"),  both hashes under the tag "HashToScalar-" || dst;  prover: t2 = r G, t3 = r M, s = r - c k;  verifier:
+ *   t2 = s G + c kA, t3 = s M + c Z, accept iff the recomputed c equals c.
+ *   prove:   ProveBatchWithRandomnessRFC9497(k, kA, B, kB, r) per request.  kA is the caller's: a wrong kA yields a proof that does not
+ *            verify, nothing worse.  The library has no RNG: the caller draws r, as it draws blinds.
+ *   verify:  VerifyBatchRFC9497(kA, B, kB, proof) per request; ok[g] is the verdict (ok is required).
+ * FAILURE IS A MASK: a failed request gets ok[g] = 0 and (prove) an all-zero proof row, and never disturbs another request.  A request
+ * fails with 0 elements (ErrInvalidBatch) or more than 65535 (the index j travels as two bytes; the reference's uint16(j) would wrap
+ * silently); with k or r zero or >= L (THE ONE DELIBERATE DIFFERENCE from the reference, which does not test r: r = 0 hands out
+ * s = -c k); with kA or any element that does not decode (strict RFC 9496, as above); verification also with c or s >= L.
+ * flags bit 0, CIRCL_HIP_DLEQ_NO_IDENTITY: an element that is the identity (32 zero bytes) fails the request (DeserializeElement; the
+ * OPRF layer sets it); without it the identity is accepted, as zk/dleq accepts it.  Other flag bits are CIRCL_HIP_EPARAM.
+ * dst is the caller's tag (the reference's Params.DST), HOST bytes in both forms, 0 <= dst_len <= 242 (so that the hash tag fits 255
+ * bytes), else CIRCL_HIP_EPARAM.  The host forms check that req_off starts at 0 and never decreases (CIRCL_HIP_EPARAM).  The argument
+ * contract is reported before a device is looked for.  n_req == 0 is CIRCL_HIP_OK.  The _dev forms take device pointers (4-byte aligned
+ * rows, 8-byte aligned offsets and workspace), n_elems = req_off[n_req] - req_off[0] given explicitly, and a workspace of at least
+ * dleq_workspace_size(n_req, n_elems) bytes (monotone in both; about 5 bytes per element plus 320 per request; nothing secret is
+ * ever written to it), else CIRCL_HIP_EWORKSPACE.  k and r are wiped from the host forms' staging.
+ * OUT OF SCOPE: the bound-base Prove / VerifyBatch forms with a caller's base A; every group other than ristretto255; the Go bridge.
+ *   poprf_tweak:          secretFromInfo / pointFromInfo, m_i = HashToScalar("Info" || I2(len) || info_i).  With sk (pkS NULL), the
+ *                         server's side: t = sk + m, t_inv = t^-1, tweaked = t G; ok = 0 for t = 0 (ErrInverseZero) or sk zero or >= L.
+ *                         With pkS (sk NULL; t and t_inv not written), the client's: tweaked = m G + pkS; ok = 0 if that is the identity
+ *                         or pkS does not decode.  Both or neither: CIRCL_HIP_EPARAM.  An info over 65535 bytes is ok = 0.  Strides: 0
+ *                         (one key for the call) or 32.  t and t_inv are secret outputs.
+ *   poprf_finalize:       PartialObliviousClient.Finalize without the proof: SHA-512(I2(len) || input_i || I2(len) || info_i || I2(32) ||
+ *                         blind_i^-1 evaluated_i || "Finalize"); ok as for the base-mode finalize.
+ *   poprf_full_evaluate:  PartialObliviousServer.FullEvaluate in one kernel: evaluates with (sk + m_i)^-1. */
+#define CIRCL_HIP_DLEQ_NO_IDENTITY 1u
+size_t circl_hip_dleq_workspace_size(size_t n_req, size_t n_elems);
+int circl_hip_dleq_prove(const uint8_t *k, size_t k_stride, const uint8_t *kA, size_t kA_stride, const uint8_t *B, const uint8_t *kB, const uint64_t *req_off,
+                         const uint8_t *r, const uint8_t *dst, size_t dst_len, uint32_t flags, uint8_t *proofs, uint8_t *ok, size_t n_req, int device);
+int circl_hip_dleq_verify(const uint8_t *kA, size_t kA_stride, const uint8_t *B, const uint8_t *kB, const uint64_t *req_off, const uint8_t *proofs,
+                          const uint8_t *dst, size_t dst_len, uint32_t flags, uint8_t *ok, size_t n_req, int device);
+int circl_hip_dleq_prove_dev(const uint8_t *k, size_t k_stride, const uint8_t *kA, size_t kA_stride, const uint8_t *B, const uint8_t *kB, const uint64_t *req_off,
+                             const uint8_t *r, const uint8_t *dst, size_t dst_len, uint32_t flags, uint8_t *proofs, uint8_t *ok, size_t n_req, size_t n_elems,
+                             void *d_workspace, size_t workspace_bytes, void *stream);
+int circl_hip_dleq_verify_dev(const uint8_t *kA, size_t kA_stride, const uint8_t *B, const uint8_t *kB, const uint64_t *req_off, const uint8_t *proofs,
+                              const uint8_t *dst, size_t dst_len, uint32_t flags, uint8_t *ok, size_t n_req, size_t n_elems, void *d_workspace,
+                              size_t workspace_bytes, void *stream);
+int circl_hip_oprf_poprf_tweak(const uint8_t *sk, size_t sk_stride, const uint8_t *pkS, size_t pk_stride, const uint8_t *info_blob, const uint64_t *info_off,
+                               uint8_t *t, uint8_t *t_inv, uint8_t *tweaked, uint8_t *ok, size_t n, int device);
+int circl_hip_oprf_poprf_finalize(const uint8_t *input_blob, const uint64_t *input_off, const uint8_t *info_blob, const uint64_t *info_off, const uint8_t *blinds,
+                                  const uint8_t *evaluated, uint8_t *out, uint8_t *ok, size_t n, int device);
+int circl_hip_oprf_poprf_full_evaluate(const uint8_t *sk, size_t sk_stride, const uint8_t *input_blob, const uint64_t *input_off, const uint8_t *info_blob,
+                                       const uint64_t *info_off, uint8_t *out, uint8_t *ok, size_t n, int device);
+int circl_hip_oprf_poprf_tweak_dev(const uint8_t *sk, size_t sk_stride, const uint8_t *pkS, size_t pk_stride, const uint8_t *info_blob, const uint64_t *info_off,
+                                   uint8_t *t, uint8_t *t_inv, uint8_t *tweaked, uint8_t *ok, size_t n, void *stream);
+int circl_hip_oprf_poprf_finalize_dev(const uint8_t *input_blob, const uint64_t *input_off, const uint8_t *info_blob, const uint64_t *info_off,
+                                      const uint8_t *blinds, const uint8_t *evaluated, uint8_t *out, uint8_t *ok, size_t n, void *stream);
+int circl_hip_oprf_poprf_full_evaluate_dev(const uint8_t *sk, size_t sk_stride, const uint8_t *input_blob, const uint64_t *input_off, const uint8_t *info_blob,
+                                           const uint64_t *info_off, uint8_t *out, uint8_t *ok, size_t n, void *stream);
 
 /* ---- kernel-level profiling (used by bench.py for the roofline figures) --------------------
  * While enabled, every *_dev call brackets each kernel it enqueues with HIP events recorded on
@@ -999,7 +1058,12 @@ int circl_hip_oprf_full_evaluate_dev(int mode, const uint8_t *sk, size_t sk_stri
 #define CIRCL_HIP_KERNEL_OPRF_EVALUATE 34        /* OPRF Evaluate (base mode)       */
 #define CIRCL_HIP_KERNEL_OPRF_FINALIZE 35        /* OPRF Finalize (base mode)       */
 #define CIRCL_HIP_KERNEL_OPRF_FULL_EVALUATE 36   /* OPRF FullEvaluate               */
-#define CIRCL_HIP_KERNEL_COUNT 37
+#define CIRCL_HIP_KERNEL_DLEQ_COMPOSITE 37        /* DLEQ: d_j B_j per element, segmented sums */
+#define CIRCL_HIP_KERNEL_DLEQ_FINISH 38           /* DLEQ: the prover's / verifier's tail per request */
+#define CIRCL_HIP_KERNEL_OPRF_POPRF_TWEAK 39      /* POPRF secretFromInfo / pointFromInfo */
+#define CIRCL_HIP_KERNEL_OPRF_POPRF_FINALIZE 40   /* POPRF Finalize                  */
+#define CIRCL_HIP_KERNEL_OPRF_POPRF_FULL_EVALUATE 41 /* POPRF FullEvaluate           */
+#define CIRCL_HIP_KERNEL_COUNT 42
 int circl_hip_profile_enable(int on);
 int circl_hip_profile_read(int kernel, double *total_ms, uint64_t *launches);
 /* The VALU issue rates this chip sustains, measured live (bench.py prices the kernels' VALU time against them instead of against
