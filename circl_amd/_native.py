@@ -63,7 +63,8 @@ SYMBOLS = [
                                "circl_hip_oprf_derive_keypair", "circl_hip_oprf_blind", "circl_hip_oprf_evaluate", "circl_hip_oprf_finalize",
                                "circl_hip_oprf_full_evaluate", "circl_hip_dleq_prove", "circl_hip_dleq_verify", "circl_hip_oprf_poprf_tweak",
                                "circl_hip_oprf_poprf_finalize", "circl_hip_oprf_poprf_full_evaluate")
-                  for d in ("", "_dev")] + ["circl_hip_dleq_workspace_size"]
+                  for d in ("", "_dev")] + ["circl_hip_dleq_workspace_size", "circl_hip_ascon_key_size"] + [
+    f + d for f in ("circl_hip_ascon_seal", "circl_hip_ascon_open") for d in ("", "_dev")]
 
 OK, EPARAM, ENODEV, EHIP, ENOMEM, EWORKSPACE, EBUSY, EAGAIN = 0, -1, -2, -3, -4, -5, -6, -7
 ALL_DEVICES = -1
@@ -280,6 +281,10 @@ def lib():
         L.circl_hip_dleq_verify_dev.argtypes = dleq + [vp] + tail + [vp, sz, sz, vp, sz, vp]
         for name, args in (("oprf_poprf_tweak", [vp, sz, vp, sz, vp, vp, vp, vp, vp, vp]), ("oprf_poprf_finalize", [vp] * 8),
                            ("oprf_poprf_full_evaluate", [vp, sz] + [vp] * 6)):
+            getattr(L, "circl_hip_" + name).argtypes = args + [sz, i]
+            getattr(L, "circl_hip_" + name + "_dev").argtypes = args + [sz, vp]
+        L.circl_hip_ascon_key_size.restype, L.circl_hip_ascon_key_size.argtypes = sz, [i]
+        for name, args in (("ascon_seal", [i, vp, sz, vp] + [vp] * 5), ("ascon_open", [i, vp, sz, vp] + [vp] * 6)):
             getattr(L, "circl_hip_" + name).argtypes = args + [sz, i]
             getattr(L, "circl_hip_" + name + "_dev").argtypes = args + [sz, vp]
         for f in ("seed", "eseed", "pk", "sk", "ct", "ss"):

@@ -664,3 +664,36 @@ class OprfDevice:
         failed.index_add_(0, torch.repeat_interleave(torch.arange(n, device=self.device), counts), (item_ok == 0).to(torch.int64))
         ok = ok & (failed == 0).to(torch.uint8)
         return out * torch.repeat_interleave(ok, counts)[:, None], ok
+
+
+class AsconCipherDevice:
+    """One Ascon mode on resident tensors (circl_hip_ascon_*_dev), on torch's current stream.  keys: a (key size,) tensor (one key for
+    every item) or (n, key size); nonces (n, 16); ragged inputs are Ragged objects (aad None: every item empty).  Ciphertexts / plaintexts
+    are flat uint8 tensors laid out by the plaintext offsets: item i's ciphertext is at pt_off[i] + 16 i."""
+
+    def __init__(self, mode, keys, device="cuda"):
+        self.mode, self.device, self.L = mode, device, nat.lib()
+        self.KS = self.L.circl_hip_ascon_key_size(mode)
+        if not self.KS:
+            raise ValueError("ascon: mode %r is not served" % (mode,))
+        self.keys, self.stride = keys, 0 if keys.dim() == 1 else self.KS
+        _chk(keys, self.KS)
+
+    def _out(self, *shape):
+        return torch.empty(shape, dtype=torch.uint8, device=self.device)
+
+    def seal(self, nonces, pt, aad=None):
+        """pt: Ragged -> flat ciphertext tensor"""
+        n = nonces.shape[0]
+        ct = self._out(int(pt.off_host[n]) + 16 * n)
+        nat.check(self.L.circl_hip_ascon_seal_dev(self.mode, _chk(self.keys), self.stride, _chk(nonces, 16), *pt.args(), *_rag_args(aad), _chk(ct), n, _stream()),
+                  "ascon_seal_dev")
+        return ct
+
+    def open(self, nonces, ct, pt_off, aad=None):
+        """ct: flat tensor; pt_off: Ragged giving the plaintext layout (its blob is not read) -> (flat plaintext tensor, ok)"""
+        n = nonces.shape[0]
+        pt, ok = self._out(int(pt_off.off_host[n]) + 1), self._out(n)
+        nat.check(self.L.circl_hip_ascon_open_dev(self.mode, _chk(self.keys), self.stride, _chk(nonces, 16), _chk(ct), pt_off.off.data_ptr(), *_rag_args(aad),
+                                                  _chk(pt), _chk(ok), n, _stream()), "ascon_open_dev")
+        return pt, ok

@@ -1359,3 +1359,56 @@ def oprf_finalize_verifiable(mode, pkS, inputs, blinds, blinded, evaluated, req_
     out = np.array(out, copy=True)
     out[_per_element(off, ok) == 0] = 0
     return out, ok
+
+
+# ---- Ascon AEAD: Ascon128, Ascon128a, Ascon80pq (cipher/ascon/ascon.go) ----
+ASCON128, ASCON128A, ASCON80PQ = 1, 2, -1
+
+
+def ascon_key_size(mode):
+    return nat.lib().circl_hip_ascon_key_size(mode)
+
+
+class AsconCipher:
+    """One Ascon mode on host buffers, the reference's Cipher over batches.  key_or_keys: one key (a byte string of the mode's key size:
+    the reference's New(key), then many Seal / Open calls) or an (n, key size) array of one key per item.  Nonces are (n, 16); plaintexts,
+    ciphertexts and aads are lists of n byte strings (aads None: every item empty)."""
+    nonce_size = overhead = 16
+
+    def __init__(self, mode, key_or_keys, device=0):
+        self.mode, self.device, self.L = mode, device, nat.lib()
+        self.key_size = ascon_key_size(mode)
+        if not self.key_size:
+            raise ValueError("ascon: mode %r is not served" % (mode,))
+        self.shared = isinstance(key_or_keys, (bytes, bytearray))
+        if (len(key_or_keys) if self.shared else np.shape(key_or_keys)[-1]) != self.key_size:
+            raise ValueError("ascon: a key of this mode has %d bytes" % self.key_size)
+        self.keys = _u8(key_or_keys, self.key_size)
+
+    def _rows(self, nonces):
+        nonces = _u8(nonces, 16)
+        n = nonces.shape[0]
+        if not self.shared and self.keys.shape[0] != n:
+            raise ValueError("ascon: %d keys, %d nonces" % (self.keys.shape[0], n))
+        return nonces, n, 0 if self.shared else self.key_size
+
+    def seal(self, nonces, pts, aads=None):
+        """-> the n ciphertexts (ct || tag) as byte strings"""
+        nonces, n, stride = self._rows(nonces)
+        (pb, po), (ab, ao) = _rag(pts, n), _rag(aads, n)
+        ct = np.empty(int(po[n]) + 16 * n, np.uint8)
+        nat.check(self.L.circl_hip_ascon_seal(self.mode, _p(self.keys), stride, _p(nonces), _p(pb), _p(po), _po(ab), _po(ao), _p(ct), n, self.device), "ascon_seal")
+        return _unrag(ct, po, 16)
+
+    def open(self, nonces, cts, aads=None):
+        """-> (the n plaintexts as byte strings, ok (n,)); a ciphertext shorter than a tag is refused here"""
+        nonces, n, stride = self._rows(nonces)
+        if len(cts) != n or any(len(c) < 16 for c in cts):
+            raise ValueError("ascon_open: need %d ciphertexts of at least 16 bytes" % n)
+        cb, _ = _blob(cts)
+        _, po = _blob([bytes(len(c) - 16) for c in cts])
+        ab, ao = _rag(aads, n)
+        pt, ok = np.empty(int(po[n]) + 1, np.uint8), np.empty(n, np.uint8)
+        nat.check(self.L.circl_hip_ascon_open(self.mode, _p(self.keys), stride, _p(nonces), _p(cb), _p(po), _po(ab), _po(ao), _p(pt), _p(ok), n, self.device),
+                  "ascon_open")
+        return _unrag(pt, po), ok

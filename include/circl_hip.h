@@ -1017,6 +1017,37 @@ int circl_hip_oprf_poprf_finalize_dev(const uint8_t *input_blob, const uint64_t 
 int circl_hip_oprf_poprf_full_evaluate_dev(const uint8_t *sk, size_t sk_stride, const uint8_t *input_blob, const uint64_t *input_off, const uint8_t *info_blob,
                                            const uint64_t *info_off, uint8_t *out, uint8_t *ok, size_t n, void *stream);
 
+/* ---- Ascon AEAD: Ascon128, Ascon128a, Ascon80pq (cipher/ascon/ascon.go; Ascon v1.2) ------------------------------------------
+ * mode = the reference's Mode values.  One item per lane, one launch per call, no workspace.  Every other mode is
+ * CIRCL_HIP_EPARAM, reported before a device is looked for, as is every breach of the rules below.
+ * Keys are rows of circl_hip_ascon_key_size(mode) = 16 / 16 / 20 bytes (0 for an unknown mode), key_stride bytes apart (an array of
+ * n key_stride bytes): key_stride == 0 means ONE key for the whole batch (the reference's New(key) and many Seal calls), otherwise
+ * key_stride >= the key size and a multiple of 4.  Nonces are n rows of 16 bytes.  Keys are secret.
+ * Ragged arguments (aad, plaintexts) are a blob and n + 1 uint64_t offsets; a NULL blob means that every item's input is empty
+ * (its offsets are then not read).  Item i's plaintext is pt_off[i + 1] - pt_off[i] bytes at pt_blob[pt_off[i]]; its ciphertext
+ * (ct || tag) is 16 bytes longer at ct_blob[pt_off[i] + 16 i]: the one offset array describes both sides.  The ciphertext blob of
+ * Open is required (with pt_off == NULL it is n rows of 16: the tags of empty plaintexts).  Input and output blobs must not
+ * overlap: the reference's in-place reuse of a buffer is not offered.
+ *   seal: Cipher.Seal: initialize, assocData (an empty aad skips the absorb), procText, finalize -> ct || tag.
+ *   open: Cipher.Open: decrypts and authenticates in one pass; the plaintext is written as it is computed and cleared when the tag
+ *         does not verify.
+ * ok[i] = 0 and the plaintext row of item i all zero where, for Open, the tag does not verify.  ok may be NULL.  The host forms zero
+ * their staging; the _dev forms want 4-byte aligned key and nonce rows and 8-byte aligned offset arrays (CIRCL_HIP_EWORKSPACE
+ * otherwise).  n == 0 is CIRCL_HIP_OK. */
+#define CIRCL_HIP_ASCON128 1
+#define CIRCL_HIP_ASCON128A 2
+#define CIRCL_HIP_ASCON80PQ (-1)
+size_t circl_hip_ascon_key_size(int mode);
+int circl_hip_ascon_seal(int mode, const uint8_t *key, size_t key_stride, const uint8_t *nonce16, const uint8_t *pt_blob, const uint64_t *pt_off,
+                         const uint8_t *aad_blob, const uint64_t *aad_off, uint8_t *ct_blob, size_t n, int device);
+int circl_hip_ascon_open(int mode, const uint8_t *key, size_t key_stride, const uint8_t *nonce16, const uint8_t *ct_blob, const uint64_t *pt_off,
+                         const uint8_t *aad_blob, const uint64_t *aad_off, uint8_t *pt_blob, uint8_t *ok, size_t n, int device);
+/* the device-resident forms: the same arguments as device pointers, on the caller's stream */
+int circl_hip_ascon_seal_dev(int mode, const uint8_t *key, size_t key_stride, const uint8_t *nonce16, const uint8_t *pt_blob, const uint64_t *pt_off,
+                             const uint8_t *aad_blob, const uint64_t *aad_off, uint8_t *ct_blob, size_t n, void *stream);
+int circl_hip_ascon_open_dev(int mode, const uint8_t *key, size_t key_stride, const uint8_t *nonce16, const uint8_t *ct_blob, const uint64_t *pt_off,
+                             const uint8_t *aad_blob, const uint64_t *aad_off, uint8_t *pt_blob, uint8_t *ok, size_t n, void *stream);
+
 /* ---- kernel-level profiling (used by bench.py for the roofline figures) --------------------
  * While enabled, every *_dev call brackets each kernel it enqueues with HIP events recorded on
  * the caller's stream.  circl_hip_profile_read synchronises the pending events, returns the
@@ -1063,7 +1094,9 @@ int circl_hip_oprf_poprf_full_evaluate_dev(const uint8_t *sk, size_t sk_stride, 
 #define CIRCL_HIP_KERNEL_OPRF_POPRF_TWEAK 39      /* POPRF secretFromInfo / pointFromInfo */
 #define CIRCL_HIP_KERNEL_OPRF_POPRF_FINALIZE 40   /* POPRF Finalize                  */
 #define CIRCL_HIP_KERNEL_OPRF_POPRF_FULL_EVALUATE 41 /* POPRF FullEvaluate           */
-#define CIRCL_HIP_KERNEL_COUNT 42
+#define CIRCL_HIP_KERNEL_ASCON_SEAL 42             /* Ascon Seal                      */
+#define CIRCL_HIP_KERNEL_ASCON_OPEN 43             /* Ascon Open                      */
+#define CIRCL_HIP_KERNEL_COUNT 44
 int circl_hip_profile_enable(int on);
 int circl_hip_profile_read(int kernel, double *total_ms, uint64_t *launches);
 /* The VALU issue rates this chip sustains, measured live (bench.py prices the kernels' VALU time against them instead of against
