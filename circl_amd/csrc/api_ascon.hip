@@ -7,6 +7,7 @@
 // the ciphertext side the same with a pad of 16 bytes per item (host_common.h HBlob / HOut).  Keys and plaintexts are wiped from the
 // page-locked staging, and the device staging of every chunk is zeroed whole.  A key shared by the batch (stride 0) is a per-call input:
 // one row is staged with every chunk.  These calls do not join coalesced batches.
+// The arrays a host form stages are declared once each, by the Call field they come from and go back to (host_compose.h Bind).
 #include "ascon_kernels.h"
 #include "host_compose.h"
 
@@ -65,64 +66,23 @@ int launch(const Call &c, hipStream_t st) {
 int host_pipeline(const Call &c, int device) {
     const PipeOpts opts = secret_opts(size_t(1) << 16);
     const bool shared = c.key_stride == 0;
-    const size_t key_row = shared ? (size_t)as::key_bytes(c.mode) : c.key_stride;
     // the offsets that size both blobs, as launch() reads them; without them every plaintext is empty and a ciphertext is a row of 16
     const uint64_t *pt_off = c.in ? c.pt_off : nullptr;
     return shard(c.n, device, [&](int dev, size_t lo, size_t cnt) {
-        std::vector<HIn> ins;
-        std::vector<HBlob> blobs;
-        std::vector<HOut> outs;
-        HIn key = {c.key + (shared ? 0 : lo * key_row), key_row, true};
-        key.per_call = shared;
-        ins.push_back(key);                                            // 0
-        ins.push_back({c.nonce + lo * 16, 16, false});                 // 1
-        if (!c.seal && !pt_off) ins.push_back({c.in + lo * 16, 16, false});  // 2: an Open of empty plaintexts reads rows of tags
-        int b_aad = -1, b_in = -1;
-        if (c.aad) {
-            blobs.push_back({c.aad, c.aad_off + lo, false});
-            b_aad = (int)blobs.size() - 1;
-        }
-        if (pt_off) {  // plaintext in (Seal): the secret side
-            blobs.push_back({c.in + (c.seal ? 0 : 16 * lo), pt_off + lo, c.seal, c.seal ? size_t(0) : size_t(16)});
-            b_in = (int)blobs.size() - 1;
-        }
-        if (pt_off) outs.push_back({c.out + (c.seal ? 16 * lo : 0), 0, !c.seal, pt_off + lo, c.seal ? size_t(16) : size_t(0)});
-        else outs.push_back({c.seal ? c.out + 16 * lo : c.out, c.seal ? size_t(16) : size_t(0), false});
-        if (!c.seal) outs.push_back({c.ok ? c.ok + lo : nullptr, 1, false});
-        return run_pipeline(dev, cnt, ins, blobs, outs, kNoWs, opts, [&](Chunk &k) {
-            Call d = c;
-            d.key = k.in[0]; d.nonce = k.in[1];
-            d.aad = b_aad < 0 ? nullptr : k.blob[b_aad]; d.aad_off = b_aad < 0 ? nullptr : k.off[b_aad];
-            d.in = b_in < 0 ? (c.seal ? nullptr : k.in[2]) : k.blob[b_in]; d.pt_off = b_in < 0 ? nullptr : k.off[b_in];
-            d.out = k.out[0];
-            d.ok = c.seal ? nullptr : k.out[1];
-            d.n = k.cnt;
-            return launch(d, k.st);
-        });
+        Bind<Call> b(c, lo);
+        b.rows(&Call::key, shared ? (size_t)as::key_bytes(c.mode) : c.key_stride, true, shared);
+        b.rows(&Call::nonce, 16, false);
+        b.blob(&Call::aad, &Call::aad_off, false);
+        b.blob(&Call::in, &Call::pt_off, c.seal, c.seal ? 0 : 16, pt_off != nullptr);   // plaintext in (Seal): the secret side
+        if (!pt_off) b.rows(&Call::in, 16, false, false, !c.seal);                      // an Open of empty plaintexts reads rows of tags
+        if (pt_off) b.ragged(&Call::out, &Call::pt_off, !c.seal, c.seal ? 16 : 0);
+        else b.out(&Call::out, c.seal ? 16 : 0, false);
+        b.out(&Call::ok, 1, false, !c.seal);
+        return run_pipeline(dev, cnt, b.ins, b.blobs, b.outs, kNoWs, opts, [&](Chunk &k) { return launch(b.on(k), k.st); });
     }, kHeavyOneDeviceMax);
 }
 
-int run(const Call &c, bool dev, int device, void *stream) {
-    if (int rc = check(c)) return rc;
-    if (c.n == 0) return CIRCL_HIP_OK;
-    return dev ? launch(c, static_cast<hipStream_t>(stream)) : host_pipeline(c, device);
-}
-
 }  // namespace
-
-// both forms of one entry point: NAME(params..., n, int device) and NAME_dev(params..., n, void *stream)
-#define BOTH_FORMS(NAME, PARAMS, BODY)                                        \
-    int NAME(PARAMS, size_t n, int device) {                                  \
-        const bool dev_ = false;                                              \
-        void *stream = nullptr;                                               \
-        BODY                                                                  \
-    }                                                                         \
-    int NAME##_dev(PARAMS, size_t n, void *stream) {                          \
-        const bool dev_ = true;                                               \
-        const int device = 0;                                                 \
-        BODY                                                                  \
-    }
-#define P(...) __VA_ARGS__
 
 extern "C" {
 
@@ -135,7 +95,7 @@ BOTH_FORMS(circl_hip_ascon_seal,
                Call c;
                c.seal = true; c.mode = mode; c.key = key; c.key_stride = key_stride; c.nonce = nonce16;
                c.in = pt_blob; c.pt_off = pt_off; c.aad = aad_blob; c.aad_off = aad_off; c.out = ct_blob; c.n = n;
-               return run(c, dev_, device, stream);
+               return run_call(c, dev_, device, stream);
            })
 
 BOTH_FORMS(circl_hip_ascon_open,
@@ -145,7 +105,7 @@ BOTH_FORMS(circl_hip_ascon_open,
                Call c;
                c.seal = false; c.mode = mode; c.key = key; c.key_stride = key_stride; c.nonce = nonce16;
                c.in = ct_blob; c.pt_off = pt_off; c.aad = aad_blob; c.aad_off = aad_off; c.out = pt_blob; c.ok = ok; c.n = n;
-               return run(c, dev_, device, stream);
+               return run_call(c, dev_, device, stream);
            })
 
 }  // extern "C"

@@ -6,6 +6,7 @@
 // arrays travel as blobs over ONE scaled copy of req_off (x 32 bytes) that is built once per call, and a launch gets the chunk's
 // offsets in bytes (dleq::Args::off_shift).  k and r are secret: their staging is wiped and the device staging of every chunk is zeroed,
 // except the workspace, which holds sums of public points only.
+// The arrays a host form stages are declared once each, by the Call field they come from and go back to (host_compose.h Bind).
 #include "dleq_kernels.h"
 #include "host_compose.h"
 
@@ -88,52 +89,33 @@ int launch(const Call &c, hipStream_t st) {
 
 // ---- host form: shard / run_pipeline over requests --------------------------------------------------------------------------------
 int host_pipeline(const Call &c, int device) {
-    // the one scaled copy of the offsets: the element arrays are blobs of 32-byte rows
+    // the one scaled copy of the offsets: the element arrays are blobs of 32-byte rows, staged from the call that holds it
     std::vector<uint64_t> scaled(c.n_req + 1);
     for (size_t g = 0; g <= c.n_req; g++) scaled[g] = c.off[g] * 32;
+    Call sc = c;
+    sc.off = scaled.data();
     PipeOpts opts;
     opts.chunk_items = host_chunk_items(size_t(1) << 14);
     opts.wipe_device = !c.verify;
     opts.ws_secret_bytes = [](size_t) { return size_t(0); };   // partial sums of d_j B_j: public
     return shard(c.n_req, device, [&](int dev, size_t lo, size_t cnt) {
-        std::vector<HIn> ins;
-        HIn ka = {c.kA + (c.kA_stride ? lo * 32 : 0), 32, false};
-        ka.per_call = c.kA_stride == 0;
-        ins.push_back(ka);
-        if (c.verify) {
-            ins.push_back({c.proofs + lo * 64, 64, false});
-        } else {
-            HIn k = {c.k + (c.k_stride ? lo * 32 : 0), 32, true};
-            k.per_call = c.k_stride == 0;
-            ins.push_back(k);
-            ins.push_back({c.r + lo * 32, 32, true});
-        }
-        const std::vector<HBlob> blobs = {{c.B, scaled.data() + lo, false}, {c.kB, scaled.data() + lo, false}};
-        std::vector<HOut> outs;
-        if (!c.verify) outs.push_back({c.proofs + lo * 64, 64, false});
-        outs.push_back({c.ok ? c.ok + lo : nullptr, 1, false});
+        Bind<Call> b(sc, lo, &Call::n_req);
+        b.rows(&Call::kA, 32, false, c.kA_stride == 0);
+        b.rows(&Call::k, 32, true, c.k_stride == 0, !c.verify);
+        b.rows(&Call::r, 32, true, false, !c.verify);
+        if (c.verify) b.rows(&Call::proofs, 64, false);
+        else b.out(&Call::proofs, 64, false);
+        b.blob(&Call::B, &Call::off, false);
+        b.blob(&Call::kB, &Call::off, false);    // (each blob stages the offsets; a launch reads one copy)
+        b.out(&Call::ok, 1, false);
         // a chunk's workspace: sized for the chunk of this shard that has the most elements
         const size_t chunk = std::max<size_t>(1, std::min(cnt, opts.chunk_items));
         size_t most = 0;
         for (size_t s = lo; s < lo + cnt; s += chunk) most = std::max<size_t>(most, c.off[std::min(s + chunk, lo + cnt)] - c.off[s]);
         size_t at = lo;   // the chunks of a shard are launched in order, on this thread
-        return run_pipeline(dev, cnt, ins, blobs, outs, [&](size_t n) { return ws_size(n, most); }, opts, [&](Chunk &k) {
-            Call d = c;
-            d.kA = k.in[0];
-            if (c.verify) {
-                d.proofs = k.in[1];
-                d.ok = k.out[0];
-            } else {
-                d.k = k.in[1];
-                d.r = k.in[2];
-                d.proofs = k.out[0];
-                d.ok = k.out[1];
-            }
-            d.B = k.blob[0];
-            d.kB = k.blob[1];
-            d.off = k.off[0];
+        return run_pipeline(dev, cnt, b.ins, b.blobs, b.outs, [&](size_t n) { return ws_size(n, most); }, opts, [&](Chunk &k) {
+            Call d = b.on(k);
             d.off_shift = 5;
-            d.n_req = k.cnt;
             d.n_elems = c.off[at + k.cnt] - c.off[at];
             at += k.cnt;
             d.ws = k.ws;
@@ -218,60 +200,17 @@ int launch(const ItemCall &c, hipStream_t st) {
 int host_pipeline(const ItemCall &c, int device) {
     const PipeOpts opts = secret_opts(size_t(1) << 16);
     return shard(c.n, device, [&](int dev, size_t lo, size_t cnt) {
-        std::vector<HIn> ins;
-        std::vector<HBlob> blobs;
-        std::vector<HOut> outs;
-        int i_sc = -1, i_el = -1, b_in = -1, b_info = -1;
-        if (c.takes_scalars()) {
-            HIn in = {c.scalars + (c.scalar_stride ? lo * 32 : 0), 32, true};
-            in.per_call = c.scalar_stride == 0;
-            ins.push_back(in);
-            i_sc = (int)ins.size() - 1;
-        }
-        if (c.takes_elems()) {
-            const bool shared = c.op == dq::kTweakClient && c.elem_stride == 0;
-            HIn in = {c.elems + (shared ? 0 : lo * 32), 32, false};
-            in.per_call = shared;
-            ins.push_back(in);
-            i_el = (int)ins.size() - 1;
-        }
-        if (c.takes_input() && c.input) {
-            blobs.push_back({c.input, c.input_off + lo, true});   // the client's private input
-            b_in = (int)blobs.size() - 1;
-        }
-        if (c.info) {
-            blobs.push_back({c.info, c.info_off + lo, false});
-            b_info = (int)blobs.size() - 1;
-        }
-        const bool secret_out = c.op != dq::kTweakClient;
-        outs.push_back({c.out + lo * c.out_row(), c.out_row(), secret_out});
-        if (c.op == dq::kTweakServer) {
-            outs.push_back({c.out2 + lo * 32, 32, true});
-            outs.push_back({c.out3 + lo * 32, 32, false});
-        }
-        outs.push_back({c.ok ? c.ok + lo : nullptr, 1, false});
-        return run_pipeline(dev, cnt, ins, blobs, outs, kNoWs, opts, [&](Chunk &k) {
-            ItemCall d = c;
-            d.scalars = i_sc < 0 ? nullptr : k.in[i_sc];
-            d.elems = i_el < 0 ? nullptr : k.in[i_el];
-            d.input = b_in < 0 ? nullptr : k.blob[b_in];
-            d.input_off = b_in < 0 ? nullptr : k.off[b_in];
-            d.info = b_info < 0 ? nullptr : k.blob[b_info];
-            d.info_off = b_info < 0 ? nullptr : k.off[b_info];
-            d.out = k.out[0];
-            d.out2 = c.op == dq::kTweakServer ? k.out[1] : nullptr;
-            d.out3 = c.op == dq::kTweakServer ? k.out[2] : nullptr;
-            d.ok = k.out.back();
-            d.n = k.cnt;
-            return launch(d, k.st);
-        });
+        Bind<ItemCall> b(c, lo);
+        b.rows(&ItemCall::scalars, 32, true, c.scalar_stride == 0, c.takes_scalars());
+        b.rows(&ItemCall::elems, 32, false, c.op == dq::kTweakClient && c.elem_stride == 0, c.takes_elems());
+        b.blob(&ItemCall::input, &ItemCall::input_off, true, 0, c.takes_input());   // the client's private input
+        b.blob(&ItemCall::info, &ItemCall::info_off, false);
+        b.out(&ItemCall::out, c.out_row(), c.op != dq::kTweakClient);
+        b.out(&ItemCall::out2, 32, true, c.op == dq::kTweakServer);
+        b.out(&ItemCall::out3, 32, false, c.op == dq::kTweakServer);
+        b.out(&ItemCall::ok, 1, false);
+        return run_pipeline(dev, cnt, b.ins, b.blobs, b.outs, kNoWs, opts, [&](Chunk &k) { return launch(b.on(k), k.st); });
     }, kHeavyOneDeviceMax);
-}
-
-int run(const ItemCall &c, bool dev, int device, void *stream) {
-    if (int rc = check(c)) return rc;
-    if (c.n == 0) return CIRCL_HIP_OK;
-    return dev ? launch(c, static_cast<hipStream_t>(stream)) : host_pipeline(c, device);
 }
 
 // sk given: the server's side (t, t^-1, t G); pkS given: the client's (the tweaked key only); both or neither: no call
@@ -286,7 +225,7 @@ int run_tweak(ItemCall &c, const uint8_t *sk, size_t sk_stride, const uint8_t *p
         c.out = c.out3;
         c.out2 = c.out3 = nullptr;
     }
-    return run(c, dev, device, stream);
+    return run_call(c, dev, device, stream);
 }
 
 }  // namespace
@@ -328,48 +267,33 @@ int circl_hip_dleq_verify_dev(DLEQ_PARAMS_, const uint8_t *proofs, DLEQ_TAIL_, u
     return run(c, true, 0, stream);
 }
 
-#define POPRF_TWEAK_BODY(DEV, DEVICE, STREAM)                                                                                              \
-    ItemCall c;                                                                                                                            \
-    c.info = info_blob; c.info_off = info_off; c.out = t; c.out2 = t_inv; c.out3 = tweaked; c.ok = ok; c.n = n;                             \
-    return run_tweak(c, sk, sk_stride, pkS, pk_stride, DEV, DEVICE, STREAM);
+BOTH_FORMS(circl_hip_oprf_poprf_tweak,
+           P(const uint8_t *sk, size_t sk_stride, const uint8_t *pkS, size_t pk_stride, const uint8_t *info_blob, const uint64_t *info_off, uint8_t *t,
+             uint8_t *t_inv, uint8_t *tweaked, uint8_t *ok),
+           {
+               ItemCall c;
+               c.info = info_blob; c.info_off = info_off; c.out = t; c.out2 = t_inv; c.out3 = tweaked; c.ok = ok; c.n = n;
+               return run_tweak(c, sk, sk_stride, pkS, pk_stride, dev_, device, stream);
+           })
 
-int circl_hip_oprf_poprf_tweak(const uint8_t *sk, size_t sk_stride, const uint8_t *pkS, size_t pk_stride, const uint8_t *info_blob, const uint64_t *info_off,
-                               uint8_t *t, uint8_t *t_inv, uint8_t *tweaked, uint8_t *ok, size_t n, int device) {
-    POPRF_TWEAK_BODY(false, device, nullptr)
-}
-int circl_hip_oprf_poprf_tweak_dev(const uint8_t *sk, size_t sk_stride, const uint8_t *pkS, size_t pk_stride, const uint8_t *info_blob, const uint64_t *info_off,
-                                   uint8_t *t, uint8_t *t_inv, uint8_t *tweaked, uint8_t *ok, size_t n, void *stream) {
-    POPRF_TWEAK_BODY(true, 0, stream)
-}
+BOTH_FORMS(circl_hip_oprf_poprf_finalize,
+           P(const uint8_t *input_blob, const uint64_t *input_off, const uint8_t *info_blob, const uint64_t *info_off, const uint8_t *blinds,
+             const uint8_t *evaluated, uint8_t *out, uint8_t *ok),
+           {
+               ItemCall c;
+               c.op = dq::kPoprfFinalize; c.input = input_blob; c.input_off = input_off; c.info = info_blob; c.info_off = info_off; c.scalars = blinds;
+               c.elems = evaluated; c.out = out; c.ok = ok; c.n = n;
+               return run_call(c, dev_, device, stream);
+           })
 
-#define POPRF_FINALIZE_BODY(DEV, DEVICE, STREAM)                                                                                           \
-    ItemCall c;                                                                                                                            \
-    c.op = dq::kPoprfFinalize; c.input = input_blob; c.input_off = input_off; c.info = info_blob; c.info_off = info_off; c.scalars = blinds; \
-    c.elems = evaluated; c.out = out; c.ok = ok; c.n = n;                                                                                  \
-    return run(c, DEV, DEVICE, STREAM);
-
-int circl_hip_oprf_poprf_finalize(const uint8_t *input_blob, const uint64_t *input_off, const uint8_t *info_blob, const uint64_t *info_off, const uint8_t *blinds,
-                                  const uint8_t *evaluated, uint8_t *out, uint8_t *ok, size_t n, int device) {
-    POPRF_FINALIZE_BODY(false, device, nullptr)
-}
-int circl_hip_oprf_poprf_finalize_dev(const uint8_t *input_blob, const uint64_t *input_off, const uint8_t *info_blob, const uint64_t *info_off,
-                                      const uint8_t *blinds, const uint8_t *evaluated, uint8_t *out, uint8_t *ok, size_t n, void *stream) {
-    POPRF_FINALIZE_BODY(true, 0, stream)
-}
-
-#define POPRF_FULL_BODY(DEV, DEVICE, STREAM)                                                                                               \
-    ItemCall c;                                                                                                                            \
-    c.op = dq::kPoprfFullEvaluate; c.scalars = sk; c.scalar_stride = sk_stride; c.input = input_blob; c.input_off = input_off;              \
-    c.info = info_blob; c.info_off = info_off; c.out = out; c.ok = ok; c.n = n;                                                            \
-    return run(c, DEV, DEVICE, STREAM);
-
-int circl_hip_oprf_poprf_full_evaluate(const uint8_t *sk, size_t sk_stride, const uint8_t *input_blob, const uint64_t *input_off, const uint8_t *info_blob,
-                                       const uint64_t *info_off, uint8_t *out, uint8_t *ok, size_t n, int device) {
-    POPRF_FULL_BODY(false, device, nullptr)
-}
-int circl_hip_oprf_poprf_full_evaluate_dev(const uint8_t *sk, size_t sk_stride, const uint8_t *input_blob, const uint64_t *input_off, const uint8_t *info_blob,
-                                           const uint64_t *info_off, uint8_t *out, uint8_t *ok, size_t n, void *stream) {
-    POPRF_FULL_BODY(true, 0, stream)
-}
+BOTH_FORMS(circl_hip_oprf_poprf_full_evaluate,
+           P(const uint8_t *sk, size_t sk_stride, const uint8_t *input_blob, const uint64_t *input_off, const uint8_t *info_blob, const uint64_t *info_off,
+             uint8_t *out, uint8_t *ok),
+           {
+               ItemCall c;
+               c.op = dq::kPoprfFullEvaluate; c.scalars = sk; c.scalar_stride = sk_stride; c.input = input_blob; c.input_off = input_off;
+               c.info = info_blob; c.info_off = info_off; c.out = out; c.ok = ok; c.n = n;
+               return run_call(c, dev_, device, stream);
+           })
 
 }  // extern "C"

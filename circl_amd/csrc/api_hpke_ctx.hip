@@ -8,6 +8,7 @@
 // that share ONE offset array: the plaintext side is a blob / a ragged output over pt_off, the ciphertext side the same with a pad
 // of 16 bytes per item (host_common.h HBlob / HOut).  Plaintexts and the secret rows are wiped from the page-locked staging, and
 // the device staging of every chunk is zeroed whole.
+// The arrays a host form stages are declared once each, by the Call field they come from and go back to (host_compose.h Bind).
 #include "host_compose.h"
 #include "hpke_kernels.h"
 
@@ -145,12 +146,6 @@ int launch(const Call &c, hipStream_t st) {
     return CIRCL_HIP_OK;
 }
 
-int dev_form(const Call &c, void *stream) {
-    if (int rc = check(c)) return rc;
-    if (c.n == 0) return CIRCL_HIP_OK;
-    return launch(c, static_cast<hipStream_t>(stream));
-}
-
 // ---- host forms: shard / run_pipeline -------------------------------------------------------------------------------------------
 int host_pipeline(const Call &c, int device) {
     const size_t N = key_bytes(c.kem), CS = c.setup() ? ctx_bytes(c.kdf) : c.ctx_stride;
@@ -159,59 +154,30 @@ int host_pipeline(const Call &c, int device) {
     const uint64_t *pt_off = c.does_aead() && c.in ? c.pt_off : nullptr;
     const bool sealing = c.does_aead() && c.sender(), opening = c.does_aead() && !c.sender();  // plaintext in / plaintext out: the secret side
     return shard(c.n, device, [&](int dev, size_t lo, size_t cnt) {
-        std::vector<HIn> ins;
-        std::vector<HBlob> blobs;
-        std::vector<HOut> outs;
-        auto in = [&](const void *p, size_t row, bool secret) {
-            if (!p) return -1;
-            ins.push_back({static_cast<const uint8_t *>(p) + lo * row, row, secret});
-            return (int)ins.size() - 1;
-        };
-        auto blob = [&](const uint8_t *b, const uint64_t *off, bool secret, size_t pad = 0) {
-            if (!b) return -1;
-            blobs.push_back({b + pad * lo, off + lo, secret, pad});
-            return (int)blobs.size() - 1;
-        };
-        auto out = [&](uint8_t *p, size_t row, bool secret, bool want) {
-            if (!want) return -1;
-            outs.push_back({p ? p + lo * row : nullptr, row, secret});
-            return (int)outs.size() - 1;
-        };
-        auto ragged = [&](uint8_t *p, bool secret, size_t pad) {
-            outs.push_back({p + pad * lo, 0, secret, pt_off + lo, pad});
-            return (int)outs.size() - 1;
-        };
-        const int i_pkR = in(c.pkR, N, false), i_ikmE = in(c.ikmE, N, true), i_skR = in(c.skR, N, true), i_skS = in(c.skS, N, true), i_pkS = in(c.pkS, N, false),
-                  i_enc = in(c.enc_in, N, false), i_ctx = in(c.ctx_in, CS, true), i_seq = in(c.seq, 8, false),
-                  i_tags = in(opening && !pt_off ? c.in : nullptr, 16, false);
-        const int b_info = blob(c.info, c.info_off, false), b_psk = blob(c.psk, c.psk_off, true), b_id = blob(c.psk_id, c.psk_id_off, false),
-                  b_exp = blob(c.exp, c.exp_off, false), b_aad = blob(c.aad, c.aad_off, false),
-                  b_in = blob(pt_off ? c.in : nullptr, pt_off, sealing, sealing ? 0 : 16);
-        const int o_enc = out(c.enc_out, N, false, c.op == kSetupSender), o_ctx = out(c.ctx_out, CS, true, c.setup() && c.what == hp::kStoreContext),
-                  o_exp = out(c.exp_out, c.L, true, c.does_export()), o_ok = out(c.ok, 1, false, c.setup() || c.op == kOpen),
-                  o_aead = !c.does_aead() ? -1 : pt_off ? ragged(c.out, opening, sealing ? 16 : 0) : out(c.out, sealing ? 16 : 0, false, true);
-        return run_pipeline(dev, cnt, ins, blobs, outs, kNoWs, opts, [&](Chunk &k) {
-            auto I = [&](int j) -> const uint8_t * { return j < 0 ? nullptr : k.in[j]; };
-            auto B = [&](int j) -> const uint8_t * { return j < 0 ? nullptr : k.blob[j]; };
-            auto F = [&](int j) -> const uint64_t * { return j < 0 ? nullptr : k.off[j]; };
-            auto O = [&](int j) -> uint8_t * { return j < 0 ? nullptr : k.out[j]; };
-            Call d = c;
-            d.pkR = I(i_pkR); d.ikmE = I(i_ikmE); d.skR = I(i_skR); d.skS = I(i_skS); d.pkS = I(i_pkS); d.enc_in = I(i_enc); d.ctx_in = I(i_ctx);
-            d.seq = reinterpret_cast<const uint64_t *>(I(i_seq));
-            d.info = B(b_info); d.info_off = F(b_info); d.psk = B(b_psk); d.psk_off = F(b_psk); d.psk_id = B(b_id); d.psk_id_off = F(b_id);
-            d.exp = B(b_exp); d.exp_off = F(b_exp); d.aad = B(b_aad); d.aad_off = F(b_aad);
-            d.in = pt_off ? B(b_in) : I(i_tags); d.pt_off = F(b_in);
-            d.enc_out = O(o_enc); d.ctx_out = O(o_ctx); d.exp_out = O(o_exp); d.ok = O(o_ok); d.out = O(o_aead);
-            d.n = k.cnt;
-            return launch(d, k.st);
-        });
+        Bind<Call> b(c, lo);
+        b.rows(&Call::pkR, N, false);
+        b.rows(&Call::ikmE, N, true);
+        b.rows(&Call::skR, N, true);
+        b.rows(&Call::skS, N, true);
+        b.rows(&Call::pkS, N, false);
+        b.rows(&Call::enc_in, N, false);
+        b.rows(&Call::ctx_in, CS, true);
+        b.rows(&Call::seq, 8, false);
+        b.blob(&Call::info, &Call::info_off, false);
+        b.blob(&Call::psk, &Call::psk_off, true);
+        b.blob(&Call::psk_id, &Call::psk_id_off, false);
+        b.blob(&Call::exp, &Call::exp_off, false);
+        b.blob(&Call::aad, &Call::aad_off, false);
+        b.blob(&Call::in, &Call::pt_off, sealing, sealing ? 0 : 16, pt_off != nullptr);
+        if (!pt_off) b.rows(&Call::in, 16, false, false, opening);   // an Open of empty plaintexts reads rows of tags
+        b.out(&Call::enc_out, N, false, c.op == kSetupSender);
+        b.out(&Call::ctx_out, CS, true, c.setup() && c.what == hp::kStoreContext);
+        b.out(&Call::exp_out, c.L, true, c.does_export());
+        b.out(&Call::ok, 1, false, c.setup() || c.op == kOpen);
+        if (pt_off) b.ragged(&Call::out, &Call::pt_off, opening, sealing ? 16 : 0);
+        else b.out(&Call::out, sealing ? 16 : 0, false, c.does_aead());
+        return run_pipeline(dev, cnt, b.ins, b.blobs, b.outs, kNoWs, opts, [&](Chunk &k) { return launch(b.on(k), k.st); });
     }, kHeavyOneDeviceMax);
-}
-
-int host_form(const Call &c, int device) {
-    if (int rc = check(c)) return rc;
-    if (c.n == 0) return CIRCL_HIP_OK;
-    return host_pipeline(c, device);
 }
 
 Call sender_call(int kem, int kdf, int aead, int mode, const uint8_t *pkR, const uint8_t *ikmE, const uint8_t *skS, const uint8_t *pkS, const uint8_t *info_blob,
@@ -248,8 +214,6 @@ Call rows_call(Op op, int aead, const uint8_t *ctx, size_t ctx_stride, size_t n)
     return c;
 }
 
-int run(const Call &c, bool dev, int device, void *stream) { return dev ? dev_form(c, stream) : host_form(c, device); }
-
 }  // namespace
 
 // the setup arguments of a sender / a receiver as every entry point spells them
@@ -262,20 +226,6 @@ int run(const Call &c, bool dev, int device, void *stream) { return dev ? dev_fo
         const uint64_t *info_off, const uint8_t *psk_blob, const uint64_t *psk_off, const uint8_t *psk_id_blob, const uint64_t *psk_id_off
 #define RECEIVER_ARGS kem, kdf, aead, mode, skR, pkR, enc, pkS, info_blob, info_off, psk_blob, psk_off, psk_id_blob, psk_id_off
 
-// both forms of one entry point: NAME(params..., n, int device) and NAME_dev(params..., n, void *stream)
-#define BOTH_FORMS(NAME, PARAMS, BODY)                                        \
-    int NAME(PARAMS, size_t n, int device) {                                  \
-        const bool dev_ = false;                                              \
-        void *stream = nullptr;                                               \
-        BODY                                                                  \
-    }                                                                         \
-    int NAME##_dev(PARAMS, size_t n, void *stream) {                          \
-        const bool dev_ = true;                                               \
-        const int device = 0;                                                 \
-        BODY                                                                  \
-    }
-#define P(...) __VA_ARGS__
-
 extern "C" {
 
 size_t circl_hip_hpke_context_size(int kdf) { return ctx_bytes(kdf); }
@@ -283,13 +233,13 @@ size_t circl_hip_hpke_context_size(int kdf) { return ctx_bytes(kdf); }
 BOTH_FORMS(circl_hip_hpke_setup_sender, P(SENDER_PARAMS, uint8_t *enc, uint8_t *ctx, uint8_t *ok), {
     Call c = sender_call(SENDER_ARGS, enc, ok, n);
     c.ctx_out = ctx;
-    return run(c, dev_, device, stream);
+    return run_call(c, dev_, device, stream);
 })
 
 BOTH_FORMS(circl_hip_hpke_setup_receiver, P(RECEIVER_PARAMS, uint8_t *ctx, uint8_t *ok), {
     Call c = receiver_call(RECEIVER_ARGS, ok, n);
     c.ctx_out = ctx;
-    return run(c, dev_, device, stream);
+    return run_call(c, dev_, device, stream);
 })
 
 BOTH_FORMS(circl_hip_hpke_seal,
@@ -299,7 +249,7 @@ BOTH_FORMS(circl_hip_hpke_seal,
                Call c = rows_call(kSeal, aead, ctx, ctx_stride, n);
                c.seq = seq;
                with_aead(c, pt_blob, pt_off, aad_blob, aad_off, ct_blob);
-               return run(c, dev_, device, stream);
+               return run_call(c, dev_, device, stream);
            })
 
 BOTH_FORMS(circl_hip_hpke_open,
@@ -310,7 +260,7 @@ BOTH_FORMS(circl_hip_hpke_open,
                c.seq = seq;
                c.ok = ok;
                with_aead(c, ct_blob, pt_off, aad_blob, aad_off, pt_blob);
-               return run(c, dev_, device, stream);
+               return run_call(c, dev_, device, stream);
            })
 
 BOTH_FORMS(circl_hip_hpke_export,
@@ -319,7 +269,7 @@ BOTH_FORMS(circl_hip_hpke_export,
                c.kem = kem;
                c.kdf = kdf;
                with_export(c, exp_blob, exp_off, L, out);
-               return run(c, dev_, device, stream);
+               return run_call(c, dev_, device, stream);
            })
 
 BOTH_FORMS(circl_hip_hpke_seal_single,
@@ -328,26 +278,26 @@ BOTH_FORMS(circl_hip_hpke_seal_single,
            {
                Call c = sender_call(SENDER_ARGS, enc, ok, n);
                with_aead(c, pt_blob, pt_off, aad_blob, aad_off, ct_blob);
-               return run(c, dev_, device, stream);
+               return run_call(c, dev_, device, stream);
            })
 
 BOTH_FORMS(circl_hip_hpke_open_single,
            P(RECEIVER_PARAMS, const uint8_t *ct_blob, const uint64_t *pt_off, const uint8_t *aad_blob, const uint64_t *aad_off, uint8_t *pt_blob, uint8_t *ok), {
                Call c = receiver_call(RECEIVER_ARGS, ok, n);
                with_aead(c, ct_blob, pt_off, aad_blob, aad_off, pt_blob);
-               return run(c, dev_, device, stream);
+               return run_call(c, dev_, device, stream);
            })
 
 BOTH_FORMS(circl_hip_hpke_export_single, P(SENDER_PARAMS, const uint8_t *exp_blob, const uint64_t *exp_off, size_t L, uint8_t *enc, uint8_t *out, uint8_t *ok), {
     Call c = sender_call(SENDER_ARGS, enc, ok, n);
     with_export(c, exp_blob, exp_off, L, out);
-    return run(c, dev_, device, stream);
+    return run_call(c, dev_, device, stream);
 })
 
 BOTH_FORMS(circl_hip_hpke_export_single_receiver, P(RECEIVER_PARAMS, const uint8_t *exp_blob, const uint64_t *exp_off, size_t L, uint8_t *out, uint8_t *ok), {
     Call c = receiver_call(RECEIVER_ARGS, ok, n);
     with_export(c, exp_blob, exp_off, L, out);
-    return run(c, dev_, device, stream);
+    return run_call(c, dev_, device, stream);
 })
 
 }  // extern "C"

@@ -6,6 +6,7 @@
 // Every host form goes through shard / run_pipeline.  Keys, blinds, seeds, the client's inputs and the outputs derived from them are
 // flagged secret: their page-locked staging is wiped and the device staging of every chunk is zeroed.  A scalar row that is shared
 // by the batch (stride 0: the server's one key) is a per-call input of the pipeline: one row is staged with every chunk, never n copies.
+// The arrays a host form stages are declared once each, by the Call field they come from and go back to (host_compose.h Bind).
 #include "host_compose.h"
 #include "oprf_kernels.h"
 
@@ -117,119 +118,67 @@ int host_pipeline(const Call &c, int device) {
     const bool secret_elems = c.op == op::kDeriveKeyPair;                                               // seeds
     const bool secret_out = c.op == op::kDeriveKeyPair || c.op == op::kFinalize || c.op == op::kFullEvaluate || c.op == op::kScalarMult;
     return shard(c.n, device, [&](int dev, size_t lo, size_t cnt) {
-        std::vector<HIn> ins;
-        std::vector<HBlob> blobs;
-        std::vector<HOut> outs;
-        int i_sc = -1, i_el = -1, b_in = -1, o_out = -1, o_out2 = -1, o_ok = -1;
-        if (c.takes_scalars()) {
-            HIn in = {c.scalars + (shared ? 0 : lo * 32), 32, true};
-            in.per_call = shared;
-            ins.push_back(in);
-            i_sc = (int)ins.size() - 1;
-        }
-        if (c.elems && (c.needs_elems() || c.op == op::kScalarMult)) {
-            ins.push_back({c.elems + lo * 32, 32, secret_elems});
-            i_el = (int)ins.size() - 1;
-        }
-        if (c.takes_blob() && c.blob) {
-            blobs.push_back({c.blob, c.off + lo, secret_blob});
-            b_in = 0;
-        }
-        outs.push_back({c.out + lo * c.out_row(), c.out_row(), secret_out});
-        o_out = 0;
-        if (c.op == op::kDeriveKeyPair) {
-            outs.push_back({c.out2 + lo * 32, 32, false});
-            o_out2 = (int)outs.size() - 1;
-        }
-        if (!c.hashes_to_group()) {
-            outs.push_back({c.ok ? c.ok + lo : nullptr, 1, false});
-            o_ok = (int)outs.size() - 1;
-        }
-        return run_pipeline(dev, cnt, ins, blobs, outs, kNoWs, opts, [&](Chunk &k) {
-            Call d = c;
-            d.scalars = i_sc < 0 ? nullptr : k.in[i_sc];
-            d.elems = i_el < 0 ? nullptr : k.in[i_el];
-            d.blob = b_in < 0 ? nullptr : k.blob[b_in];
-            d.off = b_in < 0 ? nullptr : k.off[b_in];
-            d.out = k.out[o_out];
-            d.out2 = o_out2 < 0 ? nullptr : k.out[o_out2];
-            d.ok = o_ok < 0 ? nullptr : k.out[o_ok];
-            d.n = k.cnt;
-            return launch(d, k.st);
-        });
+        Bind<Call> b(c, lo);
+        b.rows(&Call::scalars, 32, true, shared, c.takes_scalars());
+        b.rows(&Call::elems, 32, secret_elems, false, c.needs_elems() || c.op == op::kScalarMult);
+        b.blob(&Call::blob, &Call::off, secret_blob, 0, c.takes_blob());
+        b.out(&Call::out, c.out_row(), secret_out);
+        b.out(&Call::out2, 32, false, c.op == op::kDeriveKeyPair);
+        b.out(&Call::ok, 1, false, !c.hashes_to_group());
+        return run_pipeline(dev, cnt, b.ins, b.blobs, b.outs, kNoWs, opts, [&](Chunk &k) { return launch(b.on(k), k.st); });
     }, kHeavyOneDeviceMax);
 }
 
-int run(const Call &c, bool dev, int device, void *stream) {
-    if (int rc = check(c)) return rc;
-    if (c.n == 0) return CIRCL_HIP_OK;
-    return dev ? launch(c, static_cast<hipStream_t>(stream)) : host_pipeline(c, device);
-}
-
 }  // namespace
-
-// both forms of one entry point: NAME(params..., n, int device) and NAME_dev(params..., n, void *stream)
-#define BOTH_FORMS(NAME, PARAMS, BODY)                                        \
-    int NAME(PARAMS, size_t n, int device) {                                  \
-        const bool dev_ = false;                                              \
-        void *stream = nullptr;                                               \
-        BODY                                                                  \
-    }                                                                         \
-    int NAME##_dev(PARAMS, size_t n, void *stream) {                          \
-        const bool dev_ = true;                                               \
-        const int device = 0;                                                 \
-        BODY                                                                  \
-    }
-#define P(...) __VA_ARGS__
 
 extern "C" {
 
 BOTH_FORMS(circl_hip_ristretto255_hash_to_group, P(const uint8_t *msg_blob, const uint64_t *msg_off, const uint8_t *dst, size_t dst_len, uint8_t *out), {
     Call c;
     c.op = op::kHashToGroup; c.blob = msg_blob; c.off = msg_off; c.dst = dst; c.dst_len = dst_len; c.out = out; c.n = n;
-    return run(c, dev_, device, stream);
+    return run_call(c, dev_, device, stream);
 })
 
 BOTH_FORMS(circl_hip_ristretto255_hash_to_scalar, P(const uint8_t *msg_blob, const uint64_t *msg_off, const uint8_t *dst, size_t dst_len, uint8_t *out), {
     Call c;
     c.op = op::kHashToScalar; c.blob = msg_blob; c.off = msg_off; c.dst = dst; c.dst_len = dst_len; c.out = out; c.n = n;
-    return run(c, dev_, device, stream);
+    return run_call(c, dev_, device, stream);
 })
 
 BOTH_FORMS(circl_hip_ristretto255_scalar_mult, P(const uint8_t *scalars, size_t scalar_stride, const uint8_t *elems, uint32_t flags, uint8_t *out, uint8_t *ok), {
     Call c;
     c.op = op::kScalarMult; c.scalars = scalars; c.scalar_stride = scalar_stride; c.elems = elems; c.flags = flags; c.out = out; c.ok = ok; c.n = n;
-    return run(c, dev_, device, stream);
+    return run_call(c, dev_, device, stream);
 })
 
 BOTH_FORMS(circl_hip_oprf_derive_keypair, P(int mode, const uint8_t *seeds, const uint8_t *info_blob, const uint64_t *info_off, uint8_t *sk, uint8_t *pk, uint8_t *ok), {
     Call c;
     c.op = op::kDeriveKeyPair; c.mode = mode; c.elems = seeds; c.blob = info_blob; c.off = info_off; c.out = sk; c.out2 = pk; c.ok = ok; c.n = n;
-    return run(c, dev_, device, stream);
+    return run_call(c, dev_, device, stream);
 })
 
 BOTH_FORMS(circl_hip_oprf_blind, P(int mode, const uint8_t *input_blob, const uint64_t *input_off, const uint8_t *blinds, uint8_t *blinded, uint8_t *ok), {
     Call c;
     c.op = op::kBlind; c.mode = mode; c.blob = input_blob; c.off = input_off; c.scalars = blinds; c.out = blinded; c.ok = ok; c.n = n;
-    return run(c, dev_, device, stream);
+    return run_call(c, dev_, device, stream);
 })
 
 BOTH_FORMS(circl_hip_oprf_evaluate, P(const uint8_t *sk, size_t sk_stride, const uint8_t *blinded, uint8_t *evaluated, uint8_t *ok), {
     Call c;
     c.op = op::kEvaluate; c.scalars = sk; c.scalar_stride = sk_stride; c.elems = blinded; c.out = evaluated; c.ok = ok; c.n = n;
-    return run(c, dev_, device, stream);
+    return run_call(c, dev_, device, stream);
 })
 
 BOTH_FORMS(circl_hip_oprf_finalize, P(const uint8_t *input_blob, const uint64_t *input_off, const uint8_t *blinds, const uint8_t *evaluated, uint8_t *out, uint8_t *ok), {
     Call c;
     c.op = op::kFinalize; c.blob = input_blob; c.off = input_off; c.scalars = blinds; c.elems = evaluated; c.out = out; c.ok = ok; c.n = n;
-    return run(c, dev_, device, stream);
+    return run_call(c, dev_, device, stream);
 })
 
 BOTH_FORMS(circl_hip_oprf_full_evaluate, P(int mode, const uint8_t *sk, size_t sk_stride, const uint8_t *input_blob, const uint64_t *input_off, uint8_t *out, uint8_t *ok), {
     Call c;
     c.op = op::kFullEvaluate; c.mode = mode; c.scalars = sk; c.scalar_stride = sk_stride; c.blob = input_blob; c.off = input_off; c.out = out; c.ok = ok; c.n = n;
-    return run(c, dev_, device, stream);
+    return run_call(c, dev_, device, stream);
 })
 
 }  // extern "C"

@@ -51,7 +51,8 @@ def unguard(a, nbytes, what):
 
 
 def run(api, device, n_req):
-    """prove and verify through the host forms, outputs between guard margins; the inputs are made on device 0 by single-chunk calls"""
+    """prove and verify through the host forms, outputs between guard margins; the inputs are made on device 0 by single-chunk calls.
+    Then the POPRF item calls (run_items)."""
     from circl_amd import _native as nat
     lib = nat.lib()
     p = lambda a: a.ctypes.data_as(C.c_void_p)
@@ -68,6 +69,29 @@ def run(api, device, n_req):
     bad[1::2, 40] ^= 4          # every second proof's s
     nat.check(lib.circl_hip_dleq_verify(p(kA), 32, p(B), p(kB), p(off), p(bad), p(ctx), len(CTX), 1, pv, n_req, device), "dleq_verify")
     o["verdict_bad"] = unguard(verdict, n_req, "verdict")
+    o.update(run_items(api, device, n_req, k, kA, r))
+    return o
+
+
+def item_inputs(n):
+    """(infos, inputs) of n POPRF items: infos of i % 7 bytes, inputs of i % 41 bytes (empty ones at both sides of the chunk boundary 255 | 256)"""
+    rng = np.random.default_rng(9497)
+    return [rng.bytes(i % 7) for i in range(n)], [rng.bytes(0 if i in (255, 256) else i % 41) for i in range(n)]
+
+
+def run_items(api, device, n, k, kA, r):
+    """the POPRF item calls through the host forms: the tweak with a key per item, with one key and on the client's side (one public key);
+    Finalize and FullEvaluate with and without an info blob.  k are the keys (k[0] the shared one, kA[0] its public key), r the blinds, and
+    kA stands in for the evaluated elements (Finalize takes any valid element)."""
+    infos, ins = item_inputs(n)
+    o = {}
+    o["t"], o["tinv"], o["tw"], o["ok_tw"] = api.oprf_poprf_tweak(infos, sk=k, device=device)
+    o["t1"], o["tinv1"], o["tw1"], o["ok_tw1"] = api.oprf_poprf_tweak(infos, sk=k[0].tobytes(), device=device)
+    o["twc"], o["ok_twc"] = api.oprf_poprf_tweak(infos, pkS=kA[0].tobytes(), device=device)
+    o["pfin"], o["ok_pfin"] = api.oprf_poprf_finalize(ins, infos, r, kA, device=device)
+    o["pfin0"], o["ok_pfin0"] = api.oprf_poprf_finalize(ins, None, r, kA, device=device)
+    o["pfull"], o["ok_pfull"] = api.oprf_poprf_full_evaluate(k, ins, infos, device=device)
+    o["pfull0"], o["ok_pfull0"] = api.oprf_poprf_full_evaluate(k[0].tobytes(), ins, None, device=device)
     return o
 
 

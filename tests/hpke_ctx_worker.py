@@ -14,6 +14,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 SUITE = (0x20, 1, 3)
 FORGED = (255, 256, 299)
+FORGED_TAG = 100   # in the Open over rows of tags: the first item of the second shard
+EXPORT_L = 33
 GUARD, FILL = 64, 0xA5
 
 
@@ -37,7 +39,8 @@ def _flat(items):
 def run(api, pkR, skR, ikmE, device):
     """every host form that reads or writes a ragged blob, through HpkeSuite; then the same four entry points once more through ctypes
     into blobs with a guard margin on both sides (`guards` = every margin still holds its fill value, `guarded_same` = the blobs
-    between the margins equal HpkeSuite's), and Seal without a plaintext blob"""
+    between the margins equal HpkeSuite's), Seal without a plaintext blob and Open over those rows of tags; then Export and its single-shot
+    forms, and every setup and single-shot form once more in mode 3 (run_auth_psk)"""
     from circl_amd import _native as nat
     h = api.HpkeSuite(*SUITE, device=device)
     n = len(pkR)
@@ -76,7 +79,46 @@ def run(api, pkR, skR, ikmE, device):
     nat.check(L.circl_hip_hpke_seal(3, p(ctx), h.CS, p(sq), None, None, p(ab), p(ao), p(g_tags), n, device), "seal without plaintexts")
     o["tags"] = g_tags.copy()
     o["guarded_same"] = np.array([(g_ct == o["ct"]).all(), (g_pt == o["pt"]).all(), (g_ct1 == o["ct1"]).all(), (g_pt1 == o["pt1"]).all()])
+    # Open without offsets: the ciphertexts are rows of tags, FORGED_TAG's is forged; no plaintext byte is written
+    bad_tags, g_none, o["tok"] = g_tags.copy(), guarded(0), np.empty(n, np.uint8)
+    bad_tags[16 * FORGED_TAG + 15] ^= 1
+    nat.check(L.circl_hip_hpke_open(3, p(ctx_r), h.CS, p(sq), p(bad_tags), None, p(ab), p(ao), p(g_none), p(o["tok"]), n, device), "open of rows of tags")
     o["guards"] = np.array([(b[:GUARD] == FILL).all() and (b[GUARD + nb:] == FILL).all() for b, nb in held])
+    # Export on context rows and its two single-shot forms
+    exps = exporter_contexts(n)
+    o["exp"] = h.export(ctx, exps, EXPORT_L)
+    o["enc_x"], o["exp1"], o["ok_x"] = h.export_single(0, pkR, ikmE, exps, EXPORT_L)
+    o["exp1r"], o["ok_xr"] = h.export_single_receiver(0, skR, o["enc_x"], exps, EXPORT_L)
+    o.update(run_auth_psk(api, h, pkR, skR, ikmE, device))
+    return o
+
+
+def exporter_contexts(n):
+    rng = np.random.default_rng(33)
+    return [rng.bytes(i % 13) for i in range(n)]
+
+
+def auth_psk_inputs(n):
+    """(the sender's ikm rows, infos of i % 8 bytes, psks of 32 + i % 5 bytes, psk ids of 1 + i % 6 bytes)"""
+    rng = np.random.default_rng(3)
+    return (rng.integers(0, 256, (n, 32), dtype=np.uint8), [rng.bytes(i % 8) for i in range(n)], [rng.bytes(32 + i % 5) for i in range(n)],
+            [rng.bytes(1 + i % 6) for i in range(n)])
+
+
+def run_auth_psk(api, h, pkR, skR, ikmE, device):
+    """the second pass, in mode 3 (auth + PSK): the sender's key rows, the psk and psk id blobs and the info blob are staged too"""
+    n = len(pkR)
+    pts, aads, _ = inputs(n)
+    ikmS, infos, psks, ids = auth_psk_inputs(n)
+    skS, pkS = api.hpke_dhkem_derive_keypair(SUITE[0], ikmS, device=device)
+    exps, o = exporter_contexts(n), {"skS": skS, "pkS": pkS}
+    o["enc3"], o["ctx3"], o["ok3_s"] = h.setup_sender(3, pkR, ikmE, infos, psks, ids, skS=skS, pkS=pkS)
+    o["ctx3_r"], o["ok3_r"] = h.setup_receiver(3, skR, o["enc3"], infos, psks, ids, pkS=pkS, pkR=pkR)
+    o["enc3_1"], ct, o["ok3_1"] = h.seal_single(3, pkR, ikmE, pts, aads, infos, psks, ids, skS=skS, pkS=pkS)
+    pt, o["ok3_1r"] = h.open_single(3, skR, o["enc3_1"], ct, aads, infos, psks, ids, pkS=pkS, pkR=pkR)
+    o["ct3_1"], o["pt3_1"] = _flat(ct), _flat(pt)
+    o["enc3_x"], o["exp3"], o["ok3_x"] = h.export_single(3, pkR, ikmE, exps, EXPORT_L, infos, psks, ids, skS=skS, pkS=pkS)
+    o["exp3_r"], o["ok3_xr"] = h.export_single_receiver(3, skR, o["enc3_x"], exps, EXPORT_L, infos, psks, ids, pkS=pkS, pkR=pkR)
     return o
 
 

@@ -1,6 +1,6 @@
 """Batch Ascon128 / Ascon128a / Ascon80pq on the GPU, host and _dev forms, against the reference's vectors (tests/golden/ascon.json.gz) and
 the checker tests/ascon.py: every vector in one call, a ragged batch with distinct keys and nonces at odd offsets, failure masks, the
-bytes around the output blobs, and all-empty plaintexts."""
+bytes around the output blobs, all-empty plaintexts, and the host pipeline's chunks, shards and copy routes (tests/ascon_worker.py)."""
 import ctypes as C
 
 import numpy as np
@@ -218,3 +218,63 @@ def test_empty_plaintexts_without_a_blob(L, form, name):
     assert call(L, form, mode, False, keys, nonces, tags, ads, no_blob=True) == ([b""] * N, [1] * N)
     tags[64] = flip(tags[64], 127)
     assert call(L, form, mode, False, keys, nonces, tags, ads, no_blob=True) == ([b""] * N, [0 if j == 64 else 1 for j in range(N)])
+
+
+# ---- the host pipeline's routes -------------------------------------------------------------------------------------------------
+N_PIPE = 300   # two chunks of 256 + 44 items at CIRCL_HIP_HOST_CHUNK = 8; three shards of 100 on three logical devices
+SPOTS = (0, 99, 100, 199, 200, 255, 256, 299)   # both ends, both sides of the shard boundaries and of the chunk boundary
+
+
+@pytest.fixture(scope="module")
+def pipe(L):
+    """this process's own run with the default settings -- one chunk at lo = 0 -- computed once and shared"""
+    import ascon_worker as aw
+    return aw.run(L, 0, N_PIPE)
+
+
+def _items(flat, lens, extra=0):
+    off = np.concatenate([[0], np.cumsum(lens)])
+    return [flat[int(off[j]) + extra * j:int(off[j + 1]) + extra * (j + 1)].tobytes() for j in range(len(lens))]
+
+
+def _check_pipeline_run(o, base):
+    """what every configuration asserts about one run of ascon_worker.run"""
+    import ascon_worker as aw
+    keys, nonces, pts, aads = aw.inputs(N_PIPE)
+    lens = [len(x) for x in pts]
+    assert lens[0] == lens[255] == lens[256] == 0 and lens[299] == 3 and lens[100] == 26
+    for k in base:
+        assert o[k].shape == base[k].shape and (np.asarray(o[k]) == base[k]).all(), k
+    for name, mode, ks in aw.KEYINGS:
+        g = lambda what: o[name + "_" + what]
+        key = lambda j: keys[name][j, :ks].tobytes() if name == "a128" else keys[name].tobytes()
+        assert g("ok").all() and g("pt").tobytes() == b"".join(pts), name
+        assert g("ct").size == sum(lens) + 16 * N_PIPE and g("tags").size == 16 * N_PIPE
+        ct, ct_noaad, tags = _items(g("ct"), lens, 16), _items(g("ct_noaad"), lens, 16), _items(g("tags"), [0] * N_PIPE, 16)
+        for j in SPOTS:
+            nonce = nonces[j].tobytes()
+            assert ct[j] == ascon.seal(mode, key(j), nonce, pts[j], aads[j]) and ct_noaad[j] == ascon.seal(mode, key(j), nonce, pts[j]), (name, j)
+            assert tags[j] == ascon.seal(mode, key(j), nonce, b"", aads[j]), (name, j)
+        # forged tags: ok = 0 and zeros of the right length there, every other item intact
+        assert g("fok").tolist() == [0 if j in aw.FORGED else 1 for j in range(N_PIPE)], name
+        assert _items(g("fpt"), lens) == [bytes(lens[j]) if j in aw.FORGED else pts[j] for j in range(N_PIPE)], name
+        assert g("tok").tolist() == [0 if j == aw.FORGED_TAG else 1 for j in range(N_PIPE)], name
+    assert o["guards"].all()      # nothing was written before or behind an output
+
+
+def test_pipeline_default_run_takes_the_checks(pipe):
+    _check_pipeline_run(pipe, pipe)
+
+
+@pytest.mark.parametrize("env,device", [({"CIRCL_HIP_HOST_CHUNK": "8"}, 0), ({"CIRCL_HIP_HOST_CHUNK": "8", "CIRCL_HIP_LOGICAL_DEVICES": "3"}, -1),
+                                        ({"CIRCL_HIP_ZEROCOPY_KB": "0"}, 0)], ids=["chunks", "chunks-in-shards", "merged-copy"])
+def test_pipeline_routes_agree(pipe, tmp_path, env, device):
+    import os
+    import subprocess
+    import sys
+    dst = str(tmp_path / "out.npz")
+    e = {k: v for k, v in os.environ.items() if k not in ("CIRCL_HIP_HOST_CHUNK", "CIRCL_HIP_ZEROCOPY_KB", "CIRCL_HIP_LOGICAL_DEVICES")}
+    e.update(env)
+    subprocess.run([sys.executable, os.path.join(os.path.dirname(os.path.abspath(__file__)), "ascon_worker.py"), str(device), str(N_PIPE), dst], check=True,
+                   env=e, timeout=300)
+    _check_pipeline_run(np.load(dst), pipe)

@@ -359,6 +359,20 @@ def _check_pipeline_run(o, base):
     Bs, kBs = split(B, off), split(kB, off)
     for g in (0, 255, 256, 299):
         assert o["proofs"][g].tobytes() == dleq.prove(k[g].tobytes(), kA[g].tobytes(), Bs[g], kBs[g], r[g].tobytes(), dw.CTX, 1)[0], g
+    # the POPRF items
+    for key in ("ok_tw", "ok_tw1", "ok_twc", "ok_pfin", "ok_pfin0", "ok_pfull", "ok_pfull0"):
+        assert o[key].all(), key
+    assert (o["twc"] == o["tw1"]).all()         # pk + m G = (sk + m) G
+    infos, ins = dw.item_inputs(N_PIPE)
+    b = lambda a: a.tobytes()
+    for g in (0, 99, 100, 199, 200, 255, 256, 299):   # both ends, both sides of the shard boundaries and of the chunk boundary
+        assert (b(o["t"][g]), b(o["tinv"][g]), b(o["tw"][g]), 1) == dleq.poprf_tweak_server(b(k[g]), infos[g]), g
+        assert (b(o["t1"][g]), b(o["tinv1"][g]), b(o["tw1"][g]), 1) == dleq.poprf_tweak_server(b(k[0]), infos[g]), g
+        assert (b(o["twc"][g]), 1) == dleq.poprf_tweak_client(b(kA[0]), infos[g]), g
+        assert b(o["pfin"][g]) == dleq.poprf_finalize(ins[g], infos[g], b(r[g]), b(kA[g]))[0], g
+        assert b(o["pfin0"][g]) == dleq.poprf_finalize(ins[g], b"", b(r[g]), b(kA[g]))[0], g
+        assert b(o["pfull"][g]) == dleq.poprf_full_evaluate(b(k[g]), ins[g], infos[g])[0], g
+        assert b(o["pfull0"][g]) == dleq.poprf_full_evaluate(b(k[0]), ins[g], b"")[0], g
 
 
 def test_pipeline_default_run_takes_the_checks(pipe):

@@ -329,6 +329,24 @@ def _check_pipeline_run(o, keys, base):
     assert _split(o["fpt"], lens) == [bytes(lens[i]) if i in hw.FORGED else pts[i] for i in range(N_PIPE)]
     # nothing was written before or behind an output blob
     assert o["guards"].all() and o["guarded_same"].all()
+    # an Open over rows of tags, Export, and the pass in mode 3: byte for byte the default run's, and the checker at both ends and on both
+    # sides of the shard boundaries and of the chunk boundary
+    more = ("tok", "exp", "enc_x", "exp1", "exp1r", "ok_x", "ok_xr", "skS", "pkS", "enc3", "ctx3", "ctx3_r", "ok3_s", "ok3_r", "enc3_1", "ct3_1", "pt3_1",
+            "ok3_1", "ok3_1r", "enc3_x", "exp3", "exp3_r", "ok3_x", "ok3_xr")
+    for name in more:
+        assert o[name].shape == base[name].shape and (o[name] == base[name]).all(), name
+    assert all(o[name].all() for name in more if name.startswith("ok"))
+    assert o["tok"].tolist() == [0 if i == hw.FORGED_TAG else 1 for i in range(N_PIPE)]
+    assert (o["exp1r"] == o["exp1"]).all() and (o["enc_x"] == o["enc"]).all() and o["exp"].shape == (N_PIPE, hw.EXPORT_L)
+    assert (o["ctx3_r"] == o["ctx3"]).all() and (o["exp3_r"] == o["exp3"]).all() and o["pt3_1"].tobytes() == b"".join(pts)
+    assert (o["enc3_1"] == o["enc3"]).all() and (o["enc3_x"] == o["enc3"]).all()
+    exps, (_, infos, psks, ids), ct3 = hw.exporter_contexts(N_PIPE), hw.auth_psk_inputs(N_PIPE), _split(o["ct3_1"], lens, 16)
+    for i in (0, 99, 100, 199, 200, 255, 256, 299):
+        _, ks = s.setup_sender(0, bytes(keys["pkR"][i]), bytes(keys["ikmE"][i]), b"")
+        assert bytes(o["exp"][i]) == bytes(o["exp1"][i]) == s.export(ks, exps[i], hw.EXPORT_L), i
+        enc, ks = s.setup_sender(3, bytes(keys["pkR"][i]), bytes(keys["ikmE"][i]), infos[i], psks[i], ids[i], skS=bytes(o["skS"][i]))
+        assert bytes(o["enc3"][i]) == enc and bytes(o["ctx3"][i]) == s.context_row(ks), i
+        assert ct3[i] == s.seal(ks, 0, pts[i], aads[i]) and bytes(o["exp3"][i]) == s.export(ks, exps[i], hw.EXPORT_L), i
 
 
 def test_pipeline_default_run_takes_the_checks(pipe):
