@@ -64,7 +64,7 @@ SYMBOLS = [
                                "circl_hip_oprf_full_evaluate", "circl_hip_dleq_prove", "circl_hip_dleq_verify", "circl_hip_oprf_poprf_tweak",
                                "circl_hip_oprf_poprf_finalize", "circl_hip_oprf_poprf_full_evaluate")
                   for d in ("", "_dev")] + ["circl_hip_dleq_workspace_size", "circl_hip_ascon_key_size"] + [
-    f + d for f in ("circl_hip_ascon_seal", "circl_hip_ascon_open") for d in ("", "_dev")]
+    f + d for f in ("circl_hip_ascon_seal", "circl_hip_ascon_open", "circl_hip_aesgcm_seal", "circl_hip_aesgcm_open") for d in ("", "_dev")]
 
 OK, EPARAM, ENODEV, EHIP, ENOMEM, EWORKSPACE, EBUSY, EAGAIN = 0, -1, -2, -3, -4, -5, -6, -7
 ALL_DEVICES = -1
@@ -284,7 +284,8 @@ def lib():
             getattr(L, "circl_hip_" + name).argtypes = args + [sz, i]
             getattr(L, "circl_hip_" + name + "_dev").argtypes = args + [sz, vp]
         L.circl_hip_ascon_key_size.restype, L.circl_hip_ascon_key_size.argtypes = sz, [i]
-        for name, args in (("ascon_seal", [i, vp, sz, vp] + [vp] * 5), ("ascon_open", [i, vp, sz, vp] + [vp] * 6)):
+        for name, args in (("ascon_seal", [i, vp, sz, vp] + [vp] * 5), ("ascon_open", [i, vp, sz, vp] + [vp] * 6),
+                           ("aesgcm_seal", [i, vp, sz, vp, sz] + [vp] * 6), ("aesgcm_open", [i, vp, sz, vp, sz] + [vp] * 7)):
             getattr(L, "circl_hip_" + name).argtypes = args + [sz, i]
             getattr(L, "circl_hip_" + name + "_dev").argtypes = args + [sz, vp]
         for f in ("seed", "eseed", "pk", "sk", "ct", "ss"):

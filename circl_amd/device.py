@@ -697,3 +697,43 @@ class AsconCipherDevice:
         nat.check(self.L.circl_hip_ascon_open_dev(self.mode, _chk(self.keys), self.stride, _chk(nonces, 16), _chk(ct), pt_off.off.data_ptr(), *_rag_args(aad),
                                                   _chk(pt), _chk(ok), n, _stream()), "ascon_open_dev")
         return pt, ok
+
+
+class AesGcmDevice:
+    """AES-128-GCM / AES-256-GCM on resident tensors (circl_hip_aesgcm_*_dev), on torch's current stream.  keys: a (16,) / (32,) tensor
+    (one key for every item) or (n, key size); nonces (n, 12), or with seq (an (n,) int64 / uint64 tensor of sequence numbers) base nonces,
+    (n, 12) or one (12,) for the batch; ragged inputs are Ragged objects (aad None: every item empty).  Ciphertexts / plaintexts are flat
+    uint8 tensors laid out by the plaintext offsets: item i's ciphertext is at pt_off[i] + 16 i.  Distinct (key, nonce) pairs are the
+    caller's duty."""
+
+    def __init__(self, keys, device="cuda"):
+        self.device, self.L = device, nat.lib()
+        self.KS = int(keys.shape[-1])
+        if self.KS not in (16, 32):
+            raise ValueError("aesgcm: a key has 16 or 32 bytes")
+        self.keys, self.stride = keys, 0 if keys.dim() == 1 else self.KS
+        _chk(keys, self.KS)
+
+    def _out(self, *shape):
+        return torch.empty(shape, dtype=torch.uint8, device=self.device)
+
+    def _nonce(self, nonces, seq):
+        if nonces.dim() == 1 and seq is None:
+            raise ValueError("aesgcm: one base nonce for the batch needs seq")
+        return _chk(nonces, 12), 0 if nonces.dim() == 1 else 12, None if seq is None else seq.data_ptr()
+
+    def seal(self, nonces, pt, aad=None, seq=None):
+        """pt: Ragged -> flat ciphertext tensor"""
+        n = pt.off_host.shape[0] - 1
+        ct = self._out(int(pt.off_host[n]) + 16 * n)
+        nat.check(self.L.circl_hip_aesgcm_seal_dev(self.KS, _chk(self.keys), self.stride, *self._nonce(nonces, seq), *pt.args(), *_rag_args(aad), _chk(ct), n,
+                                                   _stream()), "aesgcm_seal_dev")
+        return ct
+
+    def open(self, nonces, ct, pt_off, aad=None, seq=None):
+        """ct: flat tensor; pt_off: Ragged giving the plaintext layout (its blob is not read) -> (flat plaintext tensor, ok)"""
+        n = pt_off.off_host.shape[0] - 1
+        pt, ok = self._out(int(pt_off.off_host[n]) + 1), self._out(n)
+        nat.check(self.L.circl_hip_aesgcm_open_dev(self.KS, _chk(self.keys), self.stride, *self._nonce(nonces, seq), _chk(ct), pt_off.off.data_ptr(),
+                                                   *_rag_args(aad), _chk(pt), _chk(ok), n, _stream()), "aesgcm_open_dev")
+        return pt, ok

@@ -1412,3 +1412,56 @@ class AsconCipher:
         nat.check(self.L.circl_hip_ascon_open(self.mode, _p(self.keys), stride, _p(nonces), _p(cb), _p(po), _po(ab), _po(ao), _p(pt), _p(ok), n, self.device),
                   "ascon_open")
         return _unrag(pt, po), ok
+
+
+# ---- AES-GCM AEAD: AES-128-GCM, AES-256-GCM (hpke/aead.go's AEAD ids 1 and 2; NIST SP 800-38D) ----
+AES128GCM, AES256GCM = 16, 32
+
+
+class AesGcm:
+    """AES-GCM on host buffers, Go's cipher.AEAD over batches.  key_or_keys: one key (a byte string of 16 or 32 bytes: one
+    cipher.NewGCM, then many Seal / Open calls) or an (n, key size) array of one key per item.  Nonces are (n, 12); with seq (n sequence
+    numbers, or one for all) a row is a base nonce and the nonce is row XOR BE96(seq), and one (12,) base nonce may serve the whole batch.
+    Plaintexts, ciphertexts and aads are lists of n byte strings (aads None: every item empty).  Distinct (key, nonce) pairs are the
+    caller's duty."""
+    nonce_size, overhead = 12, 16
+
+    def __init__(self, key_or_keys, device=0):
+        self.device, self.L = device, nat.lib()
+        self.shared = isinstance(key_or_keys, (bytes, bytearray))
+        self.key_size = len(key_or_keys) if self.shared else int(np.shape(key_or_keys)[-1])
+        if self.key_size not in (AES128GCM, AES256GCM):
+            raise ValueError("aesgcm: a key has 16 or 32 bytes")
+        self.keys = _u8(key_or_keys, self.key_size)
+
+    def _rows(self, nonces, seq, n):
+        one = seq is not None and (isinstance(nonces, (bytes, bytearray)) or (np.ndim(nonces) == 1 and not isinstance(nonces, (list, tuple))))
+        nonces = _u8(nonces, 12)
+        if not one and nonces.shape[0] != n or not self.shared and self.keys.shape[0] != n:
+            raise ValueError("aesgcm: %d items, %d keys, %d nonces" % (n, self.keys.shape[0], nonces.shape[0]))
+        seq = None if seq is None else np.ascontiguousarray(np.broadcast_to(np.asarray(seq, np.uint64), (n,)))
+        return nonces, 0 if one else 12, seq, 0 if self.shared else self.key_size
+
+    def seal(self, nonces, pts, aads=None, seq=None):
+        """-> the n ciphertexts (ct || tag) as byte strings"""
+        n = len(pts)
+        nonces, nstride, seq, stride = self._rows(nonces, seq, n)
+        (pb, po), (ab, ao) = _rag(pts, n), _rag(aads, n)
+        ct = np.empty(int(po[n]) + 16 * n, np.uint8)
+        nat.check(self.L.circl_hip_aesgcm_seal(self.key_size, _p(self.keys), stride, _p(nonces), nstride, _po(seq), _p(pb), _p(po), _po(ab), _po(ao), _p(ct), n,
+                                               self.device), "aesgcm_seal")
+        return _unrag(ct, po, 16)
+
+    def open(self, nonces, cts, aads=None, seq=None):
+        """-> (the n plaintexts as byte strings, ok (n,)); a ciphertext shorter than a tag is refused here"""
+        n = len(cts)
+        if any(len(c) < 16 for c in cts):
+            raise ValueError("aesgcm_open: need ciphertexts of at least 16 bytes")
+        nonces, nstride, seq, stride = self._rows(nonces, seq, n)
+        cb, _ = _blob(cts)
+        _, po = _blob([bytes(len(c) - 16) for c in cts])
+        ab, ao = _rag(aads, n)
+        pt, ok = np.empty(int(po[n]) + 1, np.uint8), np.empty(n, np.uint8)
+        nat.check(self.L.circl_hip_aesgcm_open(self.key_size, _p(self.keys), stride, _p(nonces), nstride, _po(seq), _p(cb), _p(po), _po(ab), _po(ao), _p(pt),
+                                               _p(ok), n, self.device), "aesgcm_open")
+        return _unrag(pt, po), ok

@@ -1048,6 +1048,47 @@ int circl_hip_ascon_seal_dev(int mode, const uint8_t *key, size_t key_stride, co
 int circl_hip_ascon_open_dev(int mode, const uint8_t *key, size_t key_stride, const uint8_t *nonce16, const uint8_t *ct_blob, const uint64_t *pt_off,
                              const uint8_t *aad_blob, const uint64_t *aad_off, uint8_t *pt_blob, uint8_t *ok, size_t n, void *stream);
 
+/* ---- AES-GCM AEAD: AES-128-GCM, AES-256-GCM (hpke/aead.go's AEAD ids 1 and 2; NIST SP 800-38D over FIPS 197) -------------------
+ * key_bytes = the key size, 16 or 32.  12-byte nonces, 16-byte tags.  One item per lane, one launch per call, no workspace.  Every
+ * other key size (24 included: AES-192 is not served) is CIRCL_HIP_EPARAM, reported before a device is looked for, as is every
+ * breach of the rules below.  AES and GHASH are constant-time software (the chip has neither an AES round nor a carry-less
+ * multiply): no table is indexed by, and no branch depends on, a key, a plaintext, the hash key or a tag.
+ * Keys are rows of key_bytes, key_stride bytes apart (an array of n key_stride bytes): key_stride == 0 means ONE key for the whole
+ * batch, otherwise key_stride >= key_bytes and a multiple of 4.  Keys are secret.
+ * Nonces are rows of 12 bytes, nonce_stride bytes apart (only the 12 bytes of a row are read): nonce_stride >= 12 and a multiple of
+ * 4, or nonce_stride == 0 -- ONE base nonce for the whole batch -- which needs seq.  seq == NULL: the row is the nonce.  seq != NULL
+ * (n sequence numbers): the nonce is the row XOR BE96(seq[i]), as hpke/aead.go computes it; one HPKE context sealing a run of
+ * records is key_stride = nonce_stride = 0 and seq = first, first + 1, ...  With both strides free an array of HPKE-style context
+ * rows (key || base_nonce || ...) is passed as it stands: key at +0, nonce12 at +32, both strides the row size (80 or 112).
+ * Distinct (key, nonce) pairs are the CALLER's duty, as with Go's cipher.AEAD: nothing here detects a pair used twice, in a batch
+ * or across calls, and a repeated pair gives away the xor of the plaintexts and the hash key.
+ * Ragged arguments (aad, plaintexts) are a blob and n + 1 uint64_t offsets; a NULL blob means that every item's input is empty
+ * (its offsets are then not read).  Item i's plaintext is pt_off[i + 1] - pt_off[i] bytes at pt_blob[pt_off[i]]; its ciphertext
+ * (ct || tag) is 16 bytes longer at ct_blob[pt_off[i] + 16 i]: the one offset array describes both sides.  The ciphertext blob of
+ * Open is required (with pt_off == NULL it is n rows of 16: the tags of empty plaintexts).  Input and output blobs must not
+ * overlap: in-place operation is not offered.  A plaintext is at most 2^36 - 32 bytes (SP 800-38D 5.2.1.1): the host forms, which
+ * read the offsets, refuse a longer one (and decreasing offsets); for the _dev forms that limit is the caller's to keep.
+ *   seal: ct = pt XOR the keystream E_K(nonce || 2), E_K(nonce || 3), ... (inc32); tag = GHASH_H(aad, ct, lengths) XOR E_K(nonce || 1).
+ *   open: authenticates the whole ciphertext first and decrypts under the verdict: no unauthenticated plaintext byte is written.
+ * ok[i] = 0 and the plaintext row of item i all zero where, for Open, the tag does not verify.  ok may be NULL.  The host forms zero
+ * their staging; the _dev forms want 4-byte aligned key and nonce rows and 8-byte aligned seq and offset arrays
+ * (CIRCL_HIP_EWORKSPACE otherwise).  n == 0 is CIRCL_HIP_OK. */
+#define CIRCL_HIP_AES128GCM 16 /* = the key size in bytes */
+#define CIRCL_HIP_AES256GCM 32
+int circl_hip_aesgcm_seal(int key_bytes, const uint8_t *key, size_t key_stride, const uint8_t *nonce12, size_t nonce_stride, const uint64_t *seq,
+                          const uint8_t *pt_blob, const uint64_t *pt_off, const uint8_t *aad_blob, const uint64_t *aad_off, uint8_t *ct_blob, size_t n,
+                          int device);
+int circl_hip_aesgcm_open(int key_bytes, const uint8_t *key, size_t key_stride, const uint8_t *nonce12, size_t nonce_stride, const uint64_t *seq,
+                          const uint8_t *ct_blob, const uint64_t *pt_off, const uint8_t *aad_blob, const uint64_t *aad_off, uint8_t *pt_blob, uint8_t *ok,
+                          size_t n, int device);
+/* the device-resident forms: the same arguments as device pointers, on the caller's stream */
+int circl_hip_aesgcm_seal_dev(int key_bytes, const uint8_t *key, size_t key_stride, const uint8_t *nonce12, size_t nonce_stride, const uint64_t *seq,
+                              const uint8_t *pt_blob, const uint64_t *pt_off, const uint8_t *aad_blob, const uint64_t *aad_off, uint8_t *ct_blob, size_t n,
+                              void *stream);
+int circl_hip_aesgcm_open_dev(int key_bytes, const uint8_t *key, size_t key_stride, const uint8_t *nonce12, size_t nonce_stride, const uint64_t *seq,
+                              const uint8_t *ct_blob, const uint64_t *pt_off, const uint8_t *aad_blob, const uint64_t *aad_off, uint8_t *pt_blob, uint8_t *ok,
+                              size_t n, void *stream);
+
 /* ---- kernel-level profiling (used by bench.py for the roofline figures) --------------------
  * While enabled, every *_dev call brackets each kernel it enqueues with HIP events recorded on
  * the caller's stream.  circl_hip_profile_read synchronises the pending events, returns the
@@ -1096,7 +1137,9 @@ int circl_hip_ascon_open_dev(int mode, const uint8_t *key, size_t key_stride, co
 #define CIRCL_HIP_KERNEL_OPRF_POPRF_FULL_EVALUATE 41 /* POPRF FullEvaluate           */
 #define CIRCL_HIP_KERNEL_ASCON_SEAL 42             /* Ascon Seal                      */
 #define CIRCL_HIP_KERNEL_ASCON_OPEN 43             /* Ascon Open                      */
-#define CIRCL_HIP_KERNEL_COUNT 44
+#define CIRCL_HIP_KERNEL_AESGCM_SEAL 44            /* AES-GCM Seal                    */
+#define CIRCL_HIP_KERNEL_AESGCM_OPEN 45            /* AES-GCM Open                    */
+#define CIRCL_HIP_KERNEL_COUNT 46
 int circl_hip_profile_enable(int on);
 int circl_hip_profile_read(int kernel, double *total_ms, uint64_t *launches);
 /* The VALU issue rates this chip sustains, measured live (bench.py prices the kernels' VALU time against them instead of against
