@@ -41,6 +41,19 @@
 #define CIRCL_KEM_WAVES_PER_EU 4
 #endif
 // (CIRCL_KEM_RING_XCH, the exchange form of the big-batch kernels' transforms, is set in kyber_dev.h.)
+// Entries (int16) a matrix stream moves from its LDS FIFO to its scratch row at a time: 8 (one 16-byte store per check, a check every 8
+// candidates, 32 slots), 16 (two stores, a check every 16, 32 slots) or 32 (four stores = 64 contiguous bytes, checks after candidates
+// 32 / 64 / 96 / 112, 64 slots: Geom<K>::LDS_FIFO grows from 5 120 to 9 216 bytes).  The rows are the same bytes in every form
+// (parse_shake128_block_fifo); profiles/kem_flush_ab.txt has the three measured side by side.
+#ifndef CIRCL_KEM_FIFO_FLUSH
+#define CIRCL_KEM_FIFO_FLUSH 32
+#endif
+// Measurement only (tools/clocks_kem.hip, profiles/kem_flush_ab.txt section 1): 1 compiles the FIFO reads and the row stores of every flush
+// out -- the counters advance as ever, the rows hold whatever the scratch held: what the flush work and its traffic cost together.
+#ifndef CIRCL_KEM_FIFO_ABLATE
+#define CIRCL_KEM_FIFO_ABLATE 0
+#endif
+static_assert(CIRCL_KEM_FIFO_FLUSH == 8 || CIRCL_KEM_FIFO_FLUSH == 16 || CIRCL_KEM_FIFO_FLUSH == 32, "flush granularity");
 
 namespace circl {
 namespace mlkem {
@@ -74,8 +87,10 @@ template <int K> struct Geom {
     static constexpr int LDS_XCH = 1024;                 // 256 x 32-bit: the widest exchange of the inverse transform
     static constexpr int LDS_TOTAL = LDS_A + LDS_NOISE + LDS_XCH;
     // "scratch" variant: the sampled matrix goes through a per-workgroup global scratch (L2 / Infinity
-    // Cache resident) instead of LDS, which cuts LDS per wave from ~40 KB to ~7 KB (4 waves per SIMD).
-    static constexpr int FIFO_STRIDE = 80;               // 32 int16 slots + 16 B pad per lane
+    // Cache resident) instead of LDS, which cuts LDS per wave from ~40 KB to 9 KB (4 waves per SIMD: 16 x 9 216 B of a CU's 160 KiB).
+    static constexpr int FIFO_FLUSH = CIRCL_KEM_FIFO_FLUSH;         // entries a lane moves from its FIFO to its row at a time
+    static constexpr int FIFO_SLOTS = FIFO_FLUSH > 16 ? 2 * FIFO_FLUSH : 32;
+    static constexpr int FIFO_STRIDE = 2 * FIFO_SLOTS + 16;         // int16 slots + 16 B pad per lane
     static constexpr int LDS_FIFO = 64 * FIFO_STRIDE;
     static constexpr int LDS_SCRATCH_TOTAL = (LDS_FIFO > LDS_NOISE + LDS_XCH) ? LDS_FIFO : LDS_NOISE + LDS_XCH;
     static constexpr int SCRATCH_BYTES = 64 * 512;       // per resident workgroup
@@ -435,13 +450,17 @@ __device__ __forceinline__ void count_accept(int &cnt, uint32_t v) {
 #endif
 }
 
-// Scratch variant of phase A.  Each lane appends accepted coefficients to a 32-slot LDS FIFO and
-// flushes 8 of them (16 bytes) at a time to its 512-byte row of the workgroup's global scratch, so
-// every global store is a full 16-byte segment.  Same branch-free acceptance as above.
-// TAIL = true is used from the 4th block on, where only the few unfinished streams still matter: the
-// wave leaves the block as soon as every stream is complete (checked at the 8-candidate flush points).
-template <bool TAIL, int SLOTS = 32>
+// Scratch variant of phase A.  Each lane appends accepted coefficients to a SLOTS-entry LDS FIFO and flushes FLUSH of them at a time
+// to its 512-byte row of the workgroup's global scratch: FLUSH / 8 reads of 16 bytes issued together, one wait, FLUSH / 8 stores of
+// 16 bytes to 2 FLUSH contiguous bytes (64 bytes, half a cache line, in the product's form).  Same branch-free acceptance as above.
+// A block is checked for a flush after every FLUSH candidates and after its last one (candidates 32, 64, 96, 112 at FLUSH = 32).
+// TAIL = true is used from the 4th block on, where only the few unfinished streams still matter: the wave leaves the block as soon
+// as every stream is complete, so that form checks (and tests the wave-uniform exit) every 8 candidates whatever FLUSH is.
+// `flushed` is a multiple of FLUSH throughout, and 256 is one: a stream is complete exactly when flushed == 256.
+template <bool TAIL, int SLOTS = Geom<3>::FIFO_SLOTS, int FLUSH = Geom<3>::FIFO_FLUSH>
 __device__ __forceinline__ void parse_shake128_block_fifo(const KeccakState &s, int16_t *fifo, int16_t *row, int &cnt, int &flushed) {
+    static_assert(FLUSH % 8 == 0 && 256 % FLUSH == 0 && SLOTS % FLUSH == 0 && SLOTS >= 2 * FLUSH && (SLOTS & (SLOTS - 1)) == 0, "FIFO geometry");
+    constexpr int CHECK = TAIL ? 8 : FLUSH;  // candidates between two checks
     bool live = true;
     detail::static_for<0, 112>([&](auto ic) {
         constexpr int c = decltype(ic)::v;
@@ -453,15 +472,30 @@ __device__ __forceinline__ void parse_shake128_block_fifo(const KeccakState &s, 
             else v = alignbit(word(w + 1), word(w), sh) & 0xfffu;
             fifo[cnt & (SLOTS - 1)] = (int16_t)v;
             count_accept(cnt, v);
-            if constexpr (c % 8 == 7) {
-                // The count is capped at the row length here, once per 8 candidates, not per candidate: between two checks a
-                // finished stream runs at most 8 entries past 256, into FIFO slots that hold nothing pending (fewer than 8
-                // pending entries + 8 new ones <= 16 <= SLOTS), and nothing beyond entry 255 is ever flushed.
+            if constexpr (c % CHECK == CHECK - 1 || c == 111) {
+                // The count is capped at the row length here, once per check, not per candidate.  Every check leaves fewer than
+                // FLUSH entries pending, and at most CHECK <= FLUSH candidates follow before the next one: at most 2 FLUSH - 1 <= SLOTS - 1
+                // entries (63 of 64 slots at FLUSH = 32) are ever in the FIFO, so a new entry never lands on a pending one -- nor
+                // do the at most CHECK entries a finished stream runs past 256 between two checks.  Nothing beyond entry 255 is
+                // ever flushed: flushed stops at 256, a multiple of FLUSH.
                 cnt = min(cnt, 256);
-                if (cnt - flushed >= 8) {  // at most 15 pending here, so one flush per check suffices
-                    const uint4 d = *reinterpret_cast<const uint4 *>(fifo + (flushed & (SLOTS - 1)));
-                    *reinterpret_cast<uint4 *>(row + flushed) = d;
-                    flushed += 8;
+                if (cnt - flushed >= FLUSH) {  // at most 2 FLUSH - 1 pending here, so one flush per check suffices
+#if !CIRCL_KEM_FIFO_ABLATE
+                    if constexpr (TAIL) {  // the rare path, 14 sites a block: a chunk at a time, four registers
+#pragma unroll 1
+                        for (int k = 0; k < FLUSH; k += 8) {
+                            const uint4 d = *reinterpret_cast<const uint4 *>(fifo + (flushed & (SLOTS - 1)) + k);
+                            *reinterpret_cast<uint4 *>(row + flushed + k) = d;
+                        }
+                    } else {
+                        uint4 d[FLUSH / 8];
+#pragma unroll
+                        for (int k = 0; k < FLUSH / 8; k++) d[k] = *reinterpret_cast<const uint4 *>(fifo + (flushed & (SLOTS - 1)) + 8 * k);
+#pragma unroll
+                        for (int k = 0; k < FLUSH / 8; k++) *reinterpret_cast<uint4 *>(row + flushed + 8 * k) = d[k];
+                    }
+#endif
+                    flushed += FLUSH;
                 }
                 if constexpr (TAIL) live = __any(flushed < 256);  // wave-uniform
             }
@@ -529,8 +563,11 @@ __device__ __forceinline__ void sample_matrix_and_prf(uint8_t *lds_fifo, uint8_t
     constexpr int LAST_BASE = ((STREAMS - 1) / 64) * 64, USED_LAST = STREAMS - LAST_BASE, FREE = 64 - USED_LAST;
     constexpr int MAX_HITCH = FREE < 15 ? FREE : 15;  // mini FIFO #15 is the dummy of the other lanes
     constexpr bool CAN_HITCH = Params<K>::ETA1 == 2 && MAX_HITCH > 0;
-    constexpr int STASH = 240;                          // bytes per parked stream
+    constexpr int FLUSH = Gm::FIFO_FLUSH, SLOTS = Gm::FIFO_SLOTS, CHUNKS = FLUSH / 8;
+    // bytes per parked stream: the sponge state, three counters, and the pending FIFO entries (fewer than FLUSH: 64 bytes at FLUSH = 32)
+    constexpr int STASH = (200 + 12 + 2 * FLUSH + 15) / 16 * 16;
     static_assert(15 * STASH <= Gm::LDS_FIFO, "stash fits in the FIFO area");
+    static_assert(15 * STASH <= Gm::LDS_NOISE, "stash ends below the mini FIFOs of the exchange area");
 
     // ---- phase A: three blocks for every stream ----
     KeccakState s;
@@ -567,15 +604,23 @@ __device__ __forceinline__ void sample_matrix_and_prf(uint8_t *lds_fifo, uint8_t
     const int nstr = __popcll(smask);
     if (nstr > 0) {
         const bool mine = (smask >> lane) & 1;
-        uint4 pend = make_uint4(0, 0, 0, 0);
-        if (mine) pend = *reinterpret_cast<const uint4 *>(fifo + (flushed & 31));  // < 8 pending entries, one aligned chunk
+        uint4 pend[CHUNKS];
+#pragma unroll
+        for (int k = 0; k < CHUNKS; k++) pend[k] = make_uint4(0, 0, 0, 0);
+        if (mine) {  // < FLUSH pending entries, and flushed is a multiple of FLUSH: one aligned run of CHUNKS 16-byte chunks
+#pragma unroll
+            for (int k = 0; k < CHUNKS; k++) pend[k] = *reinterpret_cast<const uint4 *>(fifo + (flushed & (SLOTS - 1)) + 8 * k);
+        }
         __syncthreads();  // every pending chunk is in registers before the stash overwrites FIFO rows
         if (mine) {
-            uint32_t *st = reinterpret_cast<uint32_t *>(lds_fifo + __popcll(smask & ((1ull << lane) - 1)) * STASH);
+            // rank among the parked streams = set bits of smask below this lane (V_MBCNT: no per-lane 64-bit mask to keep around)
+            const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(smask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)smask, 0u));
+            uint32_t *st = reinterpret_cast<uint32_t *>(lds_fifo + rank * STASH);
 #pragma unroll
             for (int w = 0; w < 25; w++) { st[2 * w] = s.lo[w]; st[2 * w + 1] = s.hi[w]; }
             st[50] = (uint32_t)cnt; st[51] = (uint32_t)flushed; st[52] = (uint32_t)lane;
-            st[53] = pend.x; st[54] = pend.y; st[55] = pend.z; st[56] = pend.w;
+#pragma unroll
+            for (int k = 0; k < CHUNKS; k++) { st[53 + 4 * k] = pend[k].x; st[54 + 4 * k] = pend[k].y; st[55 + 4 * k] = pend[k].z; st[56 + 4 * k] = pend[k].w; }
         }
     }
     __syncthreads();
@@ -596,13 +641,25 @@ __device__ __forceinline__ void sample_matrix_and_prf(uint8_t *lds_fifo, uint8_t
         const int tk = lane - USED_LAST;
         const bool target = adopt_pass && tk >= 0 && tk < nstr;
         int tcnt = 256, tflushed = 256, tsrc = 0;
-        uint4 pend = make_uint4(0, 0, 0, 0);
+        int16_t *tf = reinterpret_cast<int16_t *>(lds_mini + (target ? tk : 15) * 32);
         if (target) {
             const uint32_t *st = reinterpret_cast<const uint32_t *>(lds_fifo + tk * STASH);
 #pragma unroll
             for (int w = 0; w < 25; w++) { s.lo[w] = st[2 * w]; s.hi[w] = st[2 * w + 1]; }
             tcnt = (int)st[50]; tflushed = (int)st[51]; tsrc = (int)st[52];
-            pend = make_uint4(st[53], st[54], st[55], st[56]);
+            // the pending entries (fewer than FLUSH): the whole 8-entry chunks go straight to the row, the rest (fewer than 8)
+            // opens the 16-slot mini FIFO, which flushes 8 at a time
+            const int npend = tcnt - tflushed;
+            int16_t *trow = rows + tsrc * 256;
+            uint4 rest = make_uint4(0, 0, 0, 0);
+#pragma unroll
+            for (int k = 0; k < CHUNKS; k++) {
+                const uint4 p = make_uint4(st[53 + 4 * k], st[54 + 4 * k], st[55 + 4 * k], st[56 + 4 * k]);
+                if (npend >= 8 * (k + 1)) *reinterpret_cast<uint4 *>(trow + tflushed + 8 * k) = p;
+                if ((npend >> 3) == k) rest = p;
+            }
+            tflushed += npend & ~7;
+            *reinterpret_cast<uint4 *>(tf + (tflushed & 15)) = rest;
         }
         keccak_f1600(s);
         uint32_t *out = reinterpret_cast<uint32_t *>(lds_noise + (on ? sidx : 0) * Gm::NOISE_STRIDE);
@@ -627,14 +684,12 @@ __device__ __forceinline__ void sample_matrix_and_prf(uint8_t *lds_fifo, uint8_t
             }
         }
         if (adopt_pass) {  // wave-uniform
-            int16_t *tf = reinterpret_cast<int16_t *>(lds_mini + (target ? tk : 15) * 32);
             int16_t *trow = rows + tsrc * 256;
-            if (target) *reinterpret_cast<uint4 *>(tf + (tflushed & 15)) = pend;
-            parse_shake128_block_fifo<true, 16>(s, tf, trow, tcnt, tflushed);
+            parse_shake128_block_fifo<true, 16, 8>(s, tf, trow, tcnt, tflushed);
 #pragma unroll 1
             while (__any(tflushed < 256)) {
                 keccak_f1600(s);
-                parse_shake128_block_fifo<true, 16>(s, tf, trow, tcnt, tflushed);
+                parse_shake128_block_fifo<true, 16, 8>(s, tf, trow, tcnt, tflushed);
             }
         }
     }

@@ -21,4 +21,10 @@ if [ "${VARIANTS:-0}" = 1 ]; then
   done
   wait
   echo built tools/bin/ablate_dsa_{w5,prio0,prio3}
+  # the headline kernel's sampler at the other flush granularities, and with the flush bodies and row stores compiled out (profiles/kem_flush_ab.txt)
+  for v in "f8:-DCIRCL_KEM_FIFO_FLUSH=8" "f16:-DCIRCL_KEM_FIFO_FLUSH=16" "f8_noflush:-DCIRCL_KEM_FIFO_FLUSH=8 -DCIRCL_KEM_FIFO_ABLATE=1"; do
+    /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -Icircl_amd/csrc -Iinclude ${v#*:} tools/clocks_kem.hip -o tools/bin/clocks_kem_${v%%:*} &
+  done
+  wait
+  echo built tools/bin/clocks_kem_{f8,f16,f8_noflush}
 fi

@@ -5,6 +5,8 @@
 // (NTTs through LDS exchanges, the products against the scratch rows, compression) -- while three other wavefronts of the same SIMD are in
 // whatever phase they are in.  Real keys (GPU key generation), real r (the hash kernel): the kernel does exactly the headline's work.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -Icircl_amd/csrc -Iinclude [-DCIRCL_KEM_RING_PRIO=0] [-DCIRCL_KEM_RING_XCH=0|2|3] tools/clocks_kem.hip -o tools/bin/clocks_kem
+//   [-DCIRCL_KEM_FIFO_FLUSH=8|16|32]: the sampler's flush granularity; with -DCIRCL_KEM_FIFO_ABLATE=1 the flush bodies and row stores are compiled
+//   out (wrong outputs, time and clock only: the upper bound of profiles/kem_flush_ab.txt section 1)
 //   tools/bin/clocks_kem [log2 n = 20]
 #include <hip/hip_runtime.h>
 
