@@ -64,7 +64,10 @@ SYMBOLS = [
                                "circl_hip_oprf_full_evaluate", "circl_hip_dleq_prove", "circl_hip_dleq_verify", "circl_hip_oprf_poprf_tweak",
                                "circl_hip_oprf_poprf_finalize", "circl_hip_oprf_poprf_full_evaluate")
                   for d in ("", "_dev")] + ["circl_hip_dleq_workspace_size", "circl_hip_ascon_key_size"] + [
-    f + d for f in ("circl_hip_ascon_seal", "circl_hip_ascon_open", "circl_hip_aesgcm_seal", "circl_hip_aesgcm_open") for d in ("", "_dev")]
+    f + d for f in ("circl_hip_ascon_seal", "circl_hip_ascon_open", "circl_hip_aesgcm_seal", "circl_hip_aesgcm_open") for d in ("", "_dev")] + [
+    f + d for f in ("circl_hip_nistp_hash_to_group", "circl_hip_nistp_hash_to_scalar", "circl_hip_nistp_scalar_mult", "circl_hip_oprf_nistp_derive_keypair",
+                    "circl_hip_oprf_nistp_blind", "circl_hip_oprf_nistp_evaluate", "circl_hip_oprf_nistp_finalize", "circl_hip_oprf_nistp_full_evaluate")
+    for d in ("", "_dev")]
 
 OK, EPARAM, ENODEV, EHIP, ENOMEM, EWORKSPACE, EBUSY, EAGAIN = 0, -1, -2, -3, -4, -5, -6, -7
 ALL_DEVICES = -1
@@ -270,6 +273,13 @@ def lib():
                            ("ristretto255_scalar_mult", [vp, sz, vp, u32, vp, vp]), ("oprf_derive_keypair", [i, vp, vp, vp, vp, vp, vp]),
                            ("oprf_blind", [i, vp, vp, vp, vp, vp]), ("oprf_evaluate", [vp, sz, vp, vp, vp]),
                            ("oprf_finalize", [vp, vp, vp, vp, vp, vp]), ("oprf_full_evaluate", [i, vp, sz, vp, vp, vp, vp])):
+            getattr(L, "circl_hip_" + name).argtypes = args + [sz, i]
+            getattr(L, "circl_hip_" + name + "_dev").argtypes = args + [sz, vp]
+        # the same operations on P-256 / P-384: the curve first, hash_to_group with flags
+        for name, args in (("nistp_hash_to_group", [i, vp, vp, vp, sz, u32, vp]), ("nistp_hash_to_scalar", [i, vp, vp, vp, sz, vp]),
+                           ("nistp_scalar_mult", [i, vp, sz, vp, u32, vp, vp]), ("oprf_nistp_derive_keypair", [i, i, vp, vp, vp, vp, vp, vp]),
+                           ("oprf_nistp_blind", [i, i, vp, vp, vp, vp, vp]), ("oprf_nistp_evaluate", [i, vp, sz, vp, vp, vp]),
+                           ("oprf_nistp_finalize", [i, vp, vp, vp, vp, vp, vp]), ("oprf_nistp_full_evaluate", [i, i, vp, sz, vp, vp, vp, vp])):
             getattr(L, "circl_hip_" + name).argtypes = args + [sz, i]
             getattr(L, "circl_hip_" + name + "_dev").argtypes = args + [sz, vp]
         dleq = [vp, sz, vp, vp, vp]      # kA and its stride, B, kB, req_off

@@ -1,7 +1,8 @@
 // hkdf_dev.h -- HMAC, HKDF-Extract and one-block HKDF-Expand (RFC 5869) over a hash policy, and on top of them HPKE's
 // LabeledExtract / LabeledExpand for a KEM (hpke/kembase.go:52-82), one computation per lane.
 //
-// Two policies: Sha256 (block 64, output 32; sha256_dev.h) and Sha512 (block 128, output 64; sha512_dev.h).  Every message here
+// Three policies: Sha256 (block 64, output 32; sha256_dev.h), Sha512 (block 128, output 64; sha512_dev.h) and Sha384 (SHA-512's
+// compression from its own initial value, output 48; it serves the run-time-length streams of hkdf_stream_dev.h).  Every message here
 // has a length known at compile time, so a message is an array of little-endian 32-bit words (the bytes as they sit in memory)
 // that full unrolling keeps in registers: labels are constants the compiler folds, register-held words go in with constant
 // shifts (put_word), and the padding and the bit length are constants too.  No byte array, no address and no branch depends on
@@ -54,6 +55,31 @@ struct Sha512 {
     static CIRCL_HD void digest(uint32_t *out, const State &s) {
 #pragma unroll
         for (int i = 0; i < 8; i++) {
+            out[2 * i] = bswap32(s.h[i].hi);
+            out[2 * i + 1] = bswap32(s.h[i].lo);
+        }
+    }
+};
+
+// FIPS 180-4 5.3.4 / 6.5: SHA-512's compression from another initial value, the first 48 bytes of the state as the digest
+struct Sha384 {
+    static constexpr int BLOCK = 128, OUT = 48, LEN_BYTES = 16;
+    using State = sha512::State;
+    static CIRCL_HD void init(State &s) {
+        constexpr uint64_t IV[8] = {0xcbbb9d5dc1059ed8ull, 0x629a292a367cd507ull, 0x9159015a3070dd17ull, 0x152fecd8f70e5939ull,
+                                    0x67332667ffc00b31ull, 0x8eb44a8768581511ull, 0xdb0c2e0d64f98fa7ull, 0x47b5481dbefa4fa4ull};
+#pragma unroll
+        for (int i = 0; i < 8; i++) s.h[i] = {(uint32_t)IV[i], (uint32_t)(IV[i] >> 32)};
+    }
+    CIRCL_HKDF_BLOCK void block(State &s, const uint32_t *m) {
+        sha512::W64 w[16];
+#pragma unroll
+        for (int i = 0; i < 16; i++) w[i] = {bswap32(m[2 * i + 1]), bswap32(m[2 * i])};
+        sha512::compress(s, w);
+    }
+    static CIRCL_HD void digest(uint32_t *out, const State &s) {
+#pragma unroll
+        for (int i = 0; i < 6; i++) {
             out[2 * i] = bswap32(s.h[i].hi);
             out[2 * i + 1] = bswap32(s.h[i].lo);
         }

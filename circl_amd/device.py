@@ -737,3 +737,84 @@ class AesGcmDevice:
         nat.check(self.L.circl_hip_aesgcm_open_dev(self.KS, _chk(self.keys), self.stride, *self._nonce(nonces, seq), _chk(ct), pt_off.off.data_ptr(),
                                                    *_rag_args(aad), _chk(pt), _chk(ok), n, _stream()), "aesgcm_open_dev")
         return pt, ok
+
+
+class NistpOprfDevice:
+    """P-256 / P-384 and base-mode OPRF on them (suites P256-SHA256, P384-SHA384) on resident tensors (circl_hip_nistp_*_dev,
+    circl_hip_oprf_nistp_*_dev), on torch's current stream; shaped like OprfDevice.  curve = 256 or 384.  Scalars, keys and blinds are (n, Ns)
+    big-endian rows (Ns = 32 / 48), elements (n, Ne) SEC 1 compressed rows (Ne = 33 / 49; the identity: the zero row), seeds (n, 32), OPRF
+    outputs (n, Nh = Ns); ragged inputs are Ragged objects (or None: every item empty).  A key or scalar of shape (Ns,) or (1, Ns) is shared
+    by the batch.  Failed items have ok = 0 and zero rows."""
+
+    def __init__(self, curve, device="cuda"):
+        if curve not in (256, 384):
+            raise ValueError("curve is 256 or 384")
+        self.curve, self.device, self.L = curve, device, nat.lib()
+        self.Ns = curve // 8
+        self.Ne, self.Nh = self.Ns + 1, self.Ns
+
+    def _out(self, *shape):
+        return torch.empty(shape, dtype=torch.uint8, device=self.device)
+
+    def _scalars(self, t, n):
+        shared = t.numel() == self.Ns and n != 1
+        assert shared or t.shape == (n, self.Ns), (t.shape, n)
+        return _chk(t, self.Ns), 0 if shared else self.Ns
+
+    @staticmethod
+    def _dst(dst):
+        import numpy as np
+        return np.frombuffer(bytes(dst) + b"\0", np.uint8)      # the tag is host bytes in both forms
+
+    def hash_to_group(self, msgs, n, dst, nonuniform=False):
+        d, out = self._dst(dst), self._out(n, self.Ne)
+        nat.check(self.L.circl_hip_nistp_hash_to_group_dev(self.curve, *_rag_args(msgs), d.ctypes.data_as(C.c_void_p), len(dst), 1 if nonuniform else 0,
+                                                           _chk(out), n, _stream()), "nistp_hash_to_group_dev")
+        return out
+
+    def hash_to_scalar(self, msgs, n, dst):
+        d, out = self._dst(dst), self._out(n, self.Ns)
+        nat.check(self.L.circl_hip_nistp_hash_to_scalar_dev(self.curve, *_rag_args(msgs), d.ctypes.data_as(C.c_void_p), len(dst), _chk(out), n, _stream()),
+                  "nistp_hash_to_scalar_dev")
+        return out
+
+    def scalar_mult(self, scalars, elems=None, invert=False, n=None):
+        n = elems.shape[0] if elems is not None else (scalars.shape[0] if n is None else n)
+        out, ok = self._out(n, self.Ne), self._out(n)
+        nat.check(self.L.circl_hip_nistp_scalar_mult_dev(self.curve, *self._scalars(scalars, n), None if elems is None else _chk(elems, self.Ne),
+                                                         1 if invert else 0, _chk(out), _chk(ok), n, _stream()), "nistp_scalar_mult_dev")
+        return out, ok
+
+    def derive_keypair(self, mode, seeds, infos=None):
+        n = seeds.shape[0]
+        sk, pk, ok = self._out(n, self.Ns), self._out(n, self.Ne), self._out(n)
+        nat.check(self.L.circl_hip_oprf_nistp_derive_keypair_dev(self.curve, mode, _chk(seeds, 32), *_rag_args(infos), _chk(sk), _chk(pk), _chk(ok), n,
+                                                                 _stream()), "oprf_nistp_derive_keypair_dev")
+        return sk, pk, ok
+
+    def blind(self, mode, inputs, blinds):
+        n = blinds.shape[0]
+        out, ok = self._out(n, self.Ne), self._out(n)
+        nat.check(self.L.circl_hip_oprf_nistp_blind_dev(self.curve, mode, *_rag_args(inputs), _chk(blinds, self.Ns), _chk(out), _chk(ok), n, _stream()),
+                  "oprf_nistp_blind_dev")
+        return out, ok
+
+    def evaluate(self, sk, blinded):
+        n = blinded.shape[0]
+        out, ok = self._out(n, self.Ne), self._out(n)
+        nat.check(self.L.circl_hip_oprf_nistp_evaluate_dev(self.curve, *self._scalars(sk, n), _chk(blinded, self.Ne), _chk(out), _chk(ok), n, _stream()),
+                  "oprf_nistp_evaluate_dev")
+        return out, ok
+
+    def finalize(self, inputs, blinds, evaluated):
+        n = blinds.shape[0]
+        out, ok = self._out(n, self.Nh), self._out(n)
+        nat.check(self.L.circl_hip_oprf_nistp_finalize_dev(self.curve, *_rag_args(inputs), _chk(blinds, self.Ns), _chk(evaluated, self.Ne), _chk(out),
+                                                           _chk(ok), n, _stream()), "oprf_nistp_finalize_dev")
+        return out, ok
+
+    def full_evaluate(self, mode, sk, inputs, n):
+        out, ok = self._out(n, self.Nh), self._out(n)
+        nat.check(self.L.circl_hip_oprf_nistp_full_evaluate_dev(self.curve, mode, *self._scalars(sk, n), *_rag_args(inputs), _chk(out), _chk(ok), n,
+                                                                _stream()), "oprf_nistp_full_evaluate_dev")
+        return out, ok

@@ -1465,3 +1465,99 @@ class AesGcm:
         nat.check(self.L.circl_hip_aesgcm_open(self.key_size, _p(self.keys), stride, _p(nonces), nstride, _po(seq), _p(cb), _p(po), _po(ab), _po(ao), _p(pt),
                                                _p(ok), n, self.device), "aesgcm_open")
         return _unrag(pt, po), ok
+
+
+# ---- NIST P-256 / P-384 (group/short.go) and base-mode OPRF on them (RFC 9497, suites P256-SHA256 and P384-SHA384) ---------------------
+class NistpOprf:
+    """The group operations and the proof-free part of OPRF on one NIST curve (circl_hip_nistp_*, circl_hip_oprf_nistp_*), shaped like the
+    ristretto255 functions above.  curve = 256 or 384.  Scalars, keys and blinds are big-endian rows of Ns = 32 / 48 bytes, elements SEC 1
+    compressed rows of Ne = 33 / 49 (the identity: the zero row), seeds rows of 32, OPRF outputs rows of Nh = 32 / 48.  A single scalar row
+    is shared by the batch.  Failed items have ok = 0 and zero rows."""
+
+    def __init__(self, curve, device=0):
+        if curve not in (256, 384):
+            raise ValueError("curve is 256 or 384")
+        self.curve, self.device, self.L = curve, device, nat.lib()
+        self.Ns = curve // 8
+        self.Ne, self.Nh = self.Ns + 1, self.Ns
+
+    def context_string(self, mode):
+        return b"OPRFV1-" + bytes([mode]) + (b"-P256-SHA256" if self.curve == 256 else b"-P384-SHA384")
+
+    def _scalar_rows(self, x, n=None):
+        a = _u8(x, self.Ns)
+        if n is not None and len(a) == 1 and n != 1:
+            return a, 0
+        if n is not None and len(a) != n:
+            raise ValueError("need 1 or %d scalar rows, got %d" % (n, len(a)))
+        return a, self.Ns
+
+    def hash_to_group(self, msgs, dst, nonuniform=False):
+        """HashToElement(msg_i, dst) (nonuniform: HashToElementNonUniform) -> (n, Ne); one dst of 1..255 bytes for the batch"""
+        n = len(msgs)
+        (mb, mo), d, out = _blob(msgs), np.frombuffer(bytes(dst) + b"\0", np.uint8), np.empty((n, self.Ne), np.uint8)
+        nat.check(self.L.circl_hip_nistp_hash_to_group(self.curve, _p(mb), _p(mo), _p(d), len(dst), 1 if nonuniform else 0, _p(out), n, self.device),
+                  "nistp_hash_to_group")
+        return out
+
+    def hash_to_scalar(self, msgs, dst):
+        """HashToScalar(msg_i, dst) -> (n, Ns)"""
+        n = len(msgs)
+        (mb, mo), d, out = _blob(msgs), np.frombuffer(bytes(dst) + b"\0", np.uint8), np.empty((n, self.Ns), np.uint8)
+        nat.check(self.L.circl_hip_nistp_hash_to_scalar(self.curve, _p(mb), _p(mo), _p(d), len(dst), _p(out), n, self.device), "nistp_hash_to_scalar")
+        return out
+
+    def scalar_mult(self, scalars, elems=None, invert=False, n=None):
+        """scalar_i elem_i (elems None: the generator; invert: by scalar_i^-1) -> (out (n, Ne), ok (n,))"""
+        elems = None if elems is None else _u8(elems, self.Ne)
+        n = len(elems) if elems is not None else n
+        sc, stride = self._scalar_rows(scalars, n)
+        n = len(sc) if n is None else n
+        out, ok = np.empty((n, self.Ne), np.uint8), np.empty(n, np.uint8)
+        nat.check(self.L.circl_hip_nistp_scalar_mult(self.curve, _p(sc), stride, _po(elems), 1 if invert else 0, _p(out), _p(ok), n, self.device),
+                  "nistp_scalar_mult")
+        return out, ok
+
+    def derive_keypair(self, mode, seeds, infos=None):
+        """oprf.DeriveKey(suite, mode, seed_i, info_i) -> (sk (n, Ns), pk (n, Ne), ok (n,))"""
+        seeds = _u8(seeds, 32)
+        n = len(seeds)
+        (ib, io), sk, pk, ok = _rag(infos, n), np.empty((n, self.Ns), np.uint8), np.empty((n, self.Ne), np.uint8), np.empty(n, np.uint8)
+        nat.check(self.L.circl_hip_oprf_nistp_derive_keypair(self.curve, mode, _p(seeds), _po(ib), _po(io), _p(sk), _p(pk), _p(ok), n, self.device),
+                  "oprf_nistp_derive_keypair")
+        return sk, pk, ok
+
+    def blind(self, mode, inputs, blinds):
+        """Client.DeterministicBlind -> (blinded (n, Ne), ok (n,)); the caller draws the blinds"""
+        blinds = _u8(blinds, self.Ns)
+        n = len(blinds)
+        (ib, io), out, ok = _rag(inputs, n), np.empty((n, self.Ne), np.uint8), np.empty(n, np.uint8)
+        nat.check(self.L.circl_hip_oprf_nistp_blind(self.curve, mode, _po(ib), _po(io), _p(blinds), _p(out), _p(ok), n, self.device), "oprf_nistp_blind")
+        return out, ok
+
+    def evaluate(self, sk, blinded):
+        """base-mode Server.Evaluate -> (evaluated (n, Ne), ok (n,)); sk = one key for the batch or (n, Ns) rows"""
+        blinded = _u8(blinded, self.Ne)
+        n = len(blinded)
+        (key, stride), out, ok = self._scalar_rows(sk, n), np.empty((n, self.Ne), np.uint8), np.empty(n, np.uint8)
+        nat.check(self.L.circl_hip_oprf_nistp_evaluate(self.curve, _p(key), stride, _p(blinded), _p(out), _p(ok), n, self.device), "oprf_nistp_evaluate")
+        return out, ok
+
+    def finalize(self, inputs, blinds, evaluated):
+        """base-mode Client.Finalize -> (outputs (n, Nh), ok (n,))"""
+        blinds, evaluated = _u8(blinds, self.Ns), _u8(evaluated, self.Ne)
+        n = len(blinds)
+        if len(evaluated) != n:
+            raise ValueError("finalize: %d blinds, %d evaluated elements" % (n, len(evaluated)))
+        (ib, io), out, ok = _rag(inputs, n), np.empty((n, self.Nh), np.uint8), np.empty(n, np.uint8)
+        nat.check(self.L.circl_hip_oprf_nistp_finalize(self.curve, _po(ib), _po(io), _p(blinds), _p(evaluated), _p(out), _p(ok), n, self.device),
+                  "oprf_nistp_finalize")
+        return out, ok
+
+    def full_evaluate(self, mode, sk, inputs):
+        """Server.FullEvaluate (mode 0) / VerifiableServer.FullEvaluate (mode 1) -> (outputs (n, Nh), ok (n,)); sk as in evaluate"""
+        n = len(inputs)
+        (key, stride), (ib, io), out, ok = self._scalar_rows(sk, n), _blob(inputs), np.empty((n, self.Nh), np.uint8), np.empty(n, np.uint8)
+        nat.check(self.L.circl_hip_oprf_nistp_full_evaluate(self.curve, mode, _p(key), stride, _p(ib), _p(io), _p(out), _p(ok), n, self.device),
+                  "oprf_nistp_full_evaluate")
+        return out, ok

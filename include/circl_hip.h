@@ -958,6 +958,67 @@ int circl_hip_oprf_finalize_dev(const uint8_t *input_blob, const uint64_t *input
 int circl_hip_oprf_full_evaluate_dev(int mode, const uint8_t *sk, size_t sk_stride, const uint8_t *input_blob, const uint64_t *input_off, uint8_t *out, uint8_t *ok,
                                  size_t n, void *stream);
 
+/* ---- NIST P-256 / P-384 (group/short.go; SEC 1, RFC 9380) and base-mode OPRF on them (RFC 9497, suites P256-SHA256 and
+ * P384-SHA384) --------------------------------------------------------------------------------------------------------------------
+ * The operations of the ristretto255 block above, on a curve chosen per call: curve = CIRCL_HIP_P256 or CIRCL_HIP_P384, anything else
+ * is CIRCL_HIP_EPARAM.  One item per lane, one launch per call, no workspace.  Row shapes, for P-256 / P-384:
+ *   scalars, keys, blinds   BIG-ENDIAN rows of Ns = 32 / 48 bytes; a stride is Ns, or 0 for one row for the batch
+ *   elements                packed rows of Ne = 33 / 49 bytes, the SEC 1 COMPRESSED form 02|03 || x; no alignment is asked for
+ *   seeds                   rows of 32
+ *   OPRF outputs            rows of Nh = 32 / 48 (SHA-256 / SHA-384)
+ * THE ONE DIFFERENCE FROM THE REFERENCE: only the compressed form is accepted (the reference also reads the uncompressed 04 || x || y),
+ * and the identity, which SEC 1 writes as the single byte 00, is the all-zero row.  Decoding is strict: a prefix other than 02 / 03,
+ * x >= p, or an x^3 - 3x + b that is not a square is refused, and so is a scalar >= n.
+ * The rules of the ristretto255 block carry over: ragged blobs with n + 1 offsets, a NULL blob meaning every item's is empty, a blob
+ * without offsets CIRCL_HIP_EPARAM; ONE host-side dst for the batch, 1..255 bytes; inputs and infos of at most 65535 bytes, else
+ * ok = 0; ok[i] = 0 means every output row of item i is all zero; ok may be NULL; n == 0 is CIRCL_HIP_OK; secrets are wiped from the
+ * host forms' staging; the contract is checked before a device is looked for.
+ *   hash_to_group:   HashToElement(msg_i, dst) (two maps, added); flags & 1: HashToElementNonUniform (one map).  expand_message_xmd
+ *                    over SHA-256 / SHA-384, L = 48 / 72, simplified SWU with Z = -10 / -12.
+ *   hash_to_scalar:  HashToScalar(msg_i, dst): one L-byte value mod n.
+ *   scalar_mult:     out_i = scalar_i elem_i; elems == NULL: the generator; flags & 1: by the scalar's inverse.  The identity is
+ *                    accepted, in and out, with ok = 1.  ok = 0 where the element does not decode, the scalar is >= n or an inverse
+ *                    of zero is asked.
+ *   derive_keypair, blind, evaluate, finalize, full_evaluate: as in the ristretto255 block, with the context string
+ *                    "OPRFV1-" || mode || "-P256-SHA256" / "-P384-SHA384", I2OSP(Ne, 2) in the Finalize hash, modes 0, 1, 2 (full_evaluate:
+ *                    0, 1; 2 is CIRCL_HIP_EPARAM).  full_evaluate keeps the hashed point and the evaluated element out of memory.
+ * The _dev forms want 4-byte aligned scalar, seed, sk and output rows and 8-byte aligned offsets (CIRCL_HIP_EWORKSPACE otherwise);
+ * element rows may lie anywhere.  OUT OF SCOPE: P-521, the DLEQ proofs (VOPRF / POPRF proofs) on these curves, the Go bridge. */
+#define CIRCL_HIP_P256 256
+#define CIRCL_HIP_P384 384
+#define CIRCL_HIP_NISTP_NONUNIFORM 1u /* hash_to_group flags */
+#define CIRCL_HIP_NISTP_INVERT 1u     /* scalar_mult flags */
+int circl_hip_nistp_hash_to_group(int curve, const uint8_t *msg_blob, const uint64_t *msg_off, const uint8_t *dst, size_t dst_len, uint32_t flags, uint8_t *out,
+                                  size_t n, int device);
+int circl_hip_nistp_hash_to_scalar(int curve, const uint8_t *msg_blob, const uint64_t *msg_off, const uint8_t *dst, size_t dst_len, uint8_t *out, size_t n, int device);
+int circl_hip_nistp_scalar_mult(int curve, const uint8_t *scalars, size_t scalar_stride, const uint8_t *elems, uint32_t flags, uint8_t *out, uint8_t *ok, size_t n,
+                                int device);
+int circl_hip_oprf_nistp_derive_keypair(int curve, int mode, const uint8_t *seeds, const uint8_t *info_blob, const uint64_t *info_off, uint8_t *sk, uint8_t *pk,
+                                        uint8_t *ok, size_t n, int device);
+int circl_hip_oprf_nistp_blind(int curve, int mode, const uint8_t *input_blob, const uint64_t *input_off, const uint8_t *blinds, uint8_t *blinded, uint8_t *ok,
+                               size_t n, int device);
+int circl_hip_oprf_nistp_evaluate(int curve, const uint8_t *sk, size_t sk_stride, const uint8_t *blinded, uint8_t *evaluated, uint8_t *ok, size_t n, int device);
+int circl_hip_oprf_nistp_finalize(int curve, const uint8_t *input_blob, const uint64_t *input_off, const uint8_t *blinds, const uint8_t *evaluated, uint8_t *out,
+                                  uint8_t *ok, size_t n, int device);
+int circl_hip_oprf_nistp_full_evaluate(int curve, int mode, const uint8_t *sk, size_t sk_stride, const uint8_t *input_blob, const uint64_t *input_off, uint8_t *out,
+                                       uint8_t *ok, size_t n, int device);
+/* the device-resident forms: the same arguments as device pointers (dst stays host bytes), on the caller's stream */
+int circl_hip_nistp_hash_to_group_dev(int curve, const uint8_t *msg_blob, const uint64_t *msg_off, const uint8_t *dst, size_t dst_len, uint32_t flags, uint8_t *out,
+                                      size_t n, void *stream);
+int circl_hip_nistp_hash_to_scalar_dev(int curve, const uint8_t *msg_blob, const uint64_t *msg_off, const uint8_t *dst, size_t dst_len, uint8_t *out, size_t n,
+                                       void *stream);
+int circl_hip_nistp_scalar_mult_dev(int curve, const uint8_t *scalars, size_t scalar_stride, const uint8_t *elems, uint32_t flags, uint8_t *out, uint8_t *ok, size_t n,
+                                    void *stream);
+int circl_hip_oprf_nistp_derive_keypair_dev(int curve, int mode, const uint8_t *seeds, const uint8_t *info_blob, const uint64_t *info_off, uint8_t *sk, uint8_t *pk,
+                                            uint8_t *ok, size_t n, void *stream);
+int circl_hip_oprf_nistp_blind_dev(int curve, int mode, const uint8_t *input_blob, const uint64_t *input_off, const uint8_t *blinds, uint8_t *blinded, uint8_t *ok,
+                                   size_t n, void *stream);
+int circl_hip_oprf_nistp_evaluate_dev(int curve, const uint8_t *sk, size_t sk_stride, const uint8_t *blinded, uint8_t *evaluated, uint8_t *ok, size_t n, void *stream);
+int circl_hip_oprf_nistp_finalize_dev(int curve, const uint8_t *input_blob, const uint64_t *input_off, const uint8_t *blinds, const uint8_t *evaluated, uint8_t *out,
+                                      uint8_t *ok, size_t n, void *stream);
+int circl_hip_oprf_nistp_full_evaluate_dev(int curve, int mode, const uint8_t *sk, size_t sk_stride, const uint8_t *input_blob, const uint64_t *input_off,
+                                           uint8_t *out, uint8_t *ok, size_t n, void *stream);
+
 /* ---- batch DLEQ proofs (zk/dleq, the ...RFC9497 forms: fixed generator, the base not bound; RFC 9497 section 2.2) on ristretto255,
  * and the mode-2 (POPRF) items of oprf/client.go and oprf/server.go -------------------------------------------------------------
  * THE BATCH SHAPE.  A call carries n_req REQUESTS over flat arrays of elements (rows of 32 bytes) and req_off: n_req + 1 uint64_t
@@ -1122,6 +1183,7 @@ int circl_hip_aesgcm_open_dev(int key_bytes, const uint8_t *key, size_t key_stri
 #define CIRCL_HIP_KERNEL_HPKE_SETUP 26     /* HPKE setup (DHKEM + key schedule) and the single-shot forms */
 #define CIRCL_HIP_KERNEL_HPKE_AEAD 27      /* HPKE Seal / Open on context rows (ChaCha20-Poly1305) */
 #define CIRCL_HIP_KERNEL_HPKE_EXPORT 28    /* HPKE Export on context rows              */
+/* ids 29..36: the ristretto255 launches, and the circl_hip_nistp_* / circl_hip_oprf_nistp_* launches of the same operation */
 #define CIRCL_HIP_KERNEL_OPRF_HASH_TO_GROUP 29   /* ristretto255 HashToElement      */
 #define CIRCL_HIP_KERNEL_OPRF_HASH_TO_SCALAR 30  /* ristretto255 HashToScalar       */
 #define CIRCL_HIP_KERNEL_OPRF_SCALAR_MULT 31     /* ristretto255 scalar multiplication */
