@@ -18,7 +18,7 @@ namespace {
 const uint32_t *w(const uint8_t *p) { return reinterpret_cast<const uint32_t *>(p); }
 uint32_t *w(uint8_t *p) { return reinterpret_cast<uint32_t *>(p); }
 
-constexpr size_t kMaxCtx = 255 - dq::kTagHead;   // "HashToScalar-" || dst must fit xmd64's tag
+constexpr size_t kMaxCtx = 255 - dq::kTagHead;   // "HashToScalar-" || dst must fit xmd's tag
 
 // ---- the proofs ----------------------------------------------------------------------------------------------------------------
 struct Call {

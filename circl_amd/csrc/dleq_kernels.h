@@ -12,20 +12,19 @@
 //                      element carries the neutral element, and a failed element raises the request's flag in the workspace.
 //   finish<VERIFY>     one lane per REQUEST: adds the request's slots (contiguous, at most 1025) and runs the prover's or verifier's tail.
 // d_j and the elements are public; the prover's k M, r M, r G and s = r - c k act on secrets and use the constant-time routines.  Nothing
-// secret reaches the workspace.  The hashes are functions of their own (noinline), as in oprf_kernels.h.
+// secret reaches the workspace.  The hashes are functions of their own (noinline), as in oprf_group_kernels.h.
 //
-// The POPRF items are of the shape of oprf_kernels.h (one item per lane) with an argument struct of their own: two ragged arguments.
+// The POPRF items are of the shape of oprf_group_kernels.h (one item per lane, ristretto255 only) with an argument struct of their own: two ragged arguments.
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "oprf_kernels.h"
+#include "oprf_group_kernels.h"
 
 namespace circl {
 namespace dleq {
 
 using ed25519::Ge;
 using oprf::load8;
-using oprf::secret_scalar_ok;
 using oprf::store_masked;
 using oprf::wipe;
 
@@ -121,7 +120,7 @@ CIRCL_HD void composite_scalar(uint32_t d[8], const uint32_t seed[16], uint32_t 
     put_row(m + 104, kb, 8);
     const char label[] = "Composite";
     for (int i = 0; i < 9; i++) m[136 + i] = (uint8_t)label[i];
-    r255::xmd64<WAVES>(u, m, 145, nullptr, 0, nullptr, 0, tag, tag_len);
+    hkdf::xmd<hkdf::Sha512, WAVES>(u, 64, m, 145, nullptr, 0, nullptr, 0, tag, tag_len);
     r255::sc_from_uniform(d, u);
 }
 
@@ -136,7 +135,7 @@ CIRCL_HD void challenge_scalar(uint32_t c[8], const uint32_t rows[40], const uin
     }
     const char label[] = "Challenge";
     for (int i = 0; i < 9; i++) m[170 + i] = (uint8_t)label[i];
-    r255::xmd64<WAVES>(u, m, 179, nullptr, 0, nullptr, 0, tag, tag_len);
+    hkdf::xmd<hkdf::Sha512, WAVES>(u, 64, m, 179, nullptr, 0, nullptr, 0, tag, tag_len);
     r255::sc_from_uniform(c, u);
     for (int i = 0; i < 179; i++) m[i] = 0;   // (the prover's Z and t3 are derived from secrets)
     wipe<16>(u);
@@ -187,7 +186,7 @@ CIRCL_HD void prove_tail(const Args &a, size_t g, const Ge &M, uint32_t good) {
     load8(k, a.k + g * a.k_stride);
     load8(r, a.r + 8 * g);
     load8(rows, a.kA + g * a.kA_stride);
-    good &= secret_scalar_ok(k) & secret_scalar_ok(r);
+    good &= oprf::secret_scalar_ok<oprf::R255>(k) & oprf::secret_scalar_ok<oprf::R255>(r);
     Ge p;
     mul_call<WAVES>(p, k, M);
     r255::r255_encode(rows + 8, M);
@@ -333,7 +332,7 @@ CIRCL_HD void info_scalar(uint32_t m[8], const uint8_t *info, uint64_t len) {
     uint8_t tag[48], pre[6] = {'I', 'n', 'f', 'o', (uint8_t)(len >> 8), (uint8_t)len};
     uint32_t u[16];
     const uint32_t tag_len = mode2_tag(tag, false);
-    r255::xmd64<WAVES>(u, pre, 6, info, len, nullptr, 0, tag, tag_len);
+    hkdf::xmd<hkdf::Sha512, WAVES>(u, 64, pre, 6, info, len, nullptr, 0, tag, tag_len);
     r255::sc_from_uniform(m, u);
 }
 
@@ -364,7 +363,7 @@ CIRCL_HD uint32_t tweaked_secret(uint32_t t[8], const ItemArgs &a, size_t i, con
     load8(sk, a.scalars + i * a.scalar_stride);
     info_scalar(m, info, fits ? info_len : 0);
     ed25519::sc_muladd(t, sk, one, m);
-    const uint32_t good = secret_scalar_ok(sk) & (fits ? 1u : 0u) & (r255::sc_is_zero(t) ? 0u : 1u);
+    const uint32_t good = oprf::secret_scalar_ok<oprf::R255>(sk) & (fits ? 1u : 0u) & (r255::sc_is_zero(t) ? 0u : 1u);
     wipe<8>(sk);
     return good;
 }
@@ -416,7 +415,7 @@ CIRCL_HD void item<kPoprfFinalize>(const ItemArgs &a, size_t i) {
     load8(k, a.scalars + i * a.scalar_stride);
     load8(e, a.elems + 8 * i);
     Ge p;
-    const uint32_t good = secret_scalar_ok(k) & r255::r255_decode(p, e) & (r255::r255_equal_identity(e) ? 0u : 1u) & (fits ? 1u : 0u);
+    const uint32_t good = oprf::secret_scalar_ok<oprf::R255>(k) & r255::r255_decode(p, e) & (r255::r255_equal_identity(e) ? 0u : 1u) & (fits ? 1u : 0u);
     r255::sc_inv(kinv, k);
     p = r255::r255_mul(kinv, p);
     r255::r255_encode(enc, p);
@@ -440,7 +439,7 @@ CIRCL_HD void item<kPoprfFullEvaluate>(const ItemArgs &a, size_t i) {
     uint32_t good = tweaked_secret(t, a, i, info, info_len) & (fits ? 1u : 0u);
     r255::sc_inv(tinv, t);
     const uint32_t tag_len = mode2_tag(tag, true);
-    r255::xmd64<WAVES>(u, nullptr, 0, m, fits ? len : 0, nullptr, 0, tag, tag_len);
+    hkdf::xmd<hkdf::Sha512, WAVES>(u, 64, nullptr, 0, m, fits ? len : 0, nullptr, 0, tag, tag_len);
     Ge p = r255::r255_from_uniform(u);
     p = r255::r255_mul(tinv, p);
     r255::r255_encode(enc, p);

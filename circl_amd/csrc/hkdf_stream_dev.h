@@ -95,6 +95,42 @@ CIRCL_HKDF_STREAM_CALL(WV) void hmac_stream(uint32_t *out, const uint32_t *key, 
     for (int i = 0; i < BW; i++) kb[i] = 0;
 }
 
+// uniform = expand_message_xmd(H, pre || body || suf, dst, out_len) (RFC 9380 5.3.1), as words the way memory holds them; out has room
+// for ell = ceil(out_len / H::OUT) <= 3 digests:
+//   b_0 = H(0^BLOCK || msg || I2OSP(out_len, 2) || 0 || DST'),  b_1 = H(b_0 || 1 || DST'),  b_i = H((b_0 xor b_(i-1)) || i || DST')
+// pre and suf are bytes the lane built, body is the caller's bytes in global memory.  1 <= len(DST) <= 255 (RFC 9380's rule for a longer
+// DST is not implemented: the entry points refuse it).  A function of its own per hash and occupancy class, as the streams are.
+template <class H, int WV>
+CIRCL_HKDF_STREAM_CALL(WV) void xmd(uint32_t *out, uint32_t out_len, const uint8_t *pre, uint32_t pre_len, const uint8_t *body, uint64_t body_len,
+                                    const uint8_t *suf, uint32_t suf_len, const uint8_t *dst, uint32_t dst_len) {
+    constexpr int OW = H::OUT / 4;
+    Stream<H, WV> st;
+    uint32_t zero[H::BLOCK / 4], b0[OW], x[OW];
+    for (int i = 0; i < H::BLOCK / 4; i++) zero[i] = 0;
+    st.init();
+    st.put_block(zero);
+    st.put(pre, pre_len);
+    st.put(body, body_len);
+    st.put(suf, suf_len);
+    st.put((uint8_t)(out_len >> 8));
+    st.put((uint8_t)out_len);
+    st.put((uint8_t)0);
+    st.put(dst, dst_len);
+    st.put((uint8_t)dst_len);
+    st.finish(b0);
+    const uint32_t ell = (out_len + H::OUT - 1) / H::OUT;
+    for (uint32_t i = 1; i <= ell; i++) {
+        for (int j = 0; j < OW; j++) x[j] = i == 1 ? b0[j] : b0[j] ^ out[(i - 2) * OW + j];
+        st.init();
+        st.put(reinterpret_cast<const uint8_t *>(x), H::OUT);
+        st.put((uint8_t)i);
+        st.put(dst, dst_len);
+        st.put((uint8_t)dst_len);
+        st.finish(out + (i - 1) * OW);
+    }
+    for (int j = 0; j < OW; j++) b0[j] = x[j] = 0;
+}
+
 // the HPKE suite of a context (util.go:85-91): the three code points that enter every label
 struct SuiteId {
     int kem, kdf, aead;

@@ -22,8 +22,7 @@
 //                     verdict 0.  The all-zero row is the identity (the reference's one-byte 00, padded).  Computes either way.
 //   sswu_map          group/short.go sswu3mod4Map step by step, e1 (xd = 0 -> Z A) and both selects included; sgn0 is the low bit of the
 //                     canonical value.  The result stays projective (xn : y xd : xd): the reference's inversion of xd is not needed.
-//   xmd               expand_message_xmd(H, pre || body || suf, DST, out_len) for out_len up to 3 digests (L and 2 L need 2 and 3).
-//                     1 <= len(DST) <= 255 (the entry points refuse anything else).
+//   (hashing)         expand_message_xmd is hkdf::xmd of hkdf_stream_dev.h: L and 2 L bytes need 2 and 3 digests.
 //
 // Constant time: no branch and no address depends on a scalar, a blind, a key, a hashed point or an evaluated element.  Only lengths and
 // public exponents steer loops.
@@ -626,41 +625,6 @@ CIRCL_HD Pt<C> sswu_map(const Fe<C::N> &u) {
     const bool e3 = fe_sgn0<C>(u) == fe_sgn0<C>(y);                          // 32
     y = fe_select(fe_neg<M>(y), y, e3);                                      // 33
     return {xn, mont_mul<M>(y, xd), xd};                                     // 34, projective
-}
-
-// uniform = expand_message_xmd(H, pre || body || suf, dst, out_len) (RFC 9380 5.3.1), as words the way memory holds them; out has room
-// for ell = ceil(out_len / H::OUT) <= 3 digests:
-//   b_0 = H(0^BLOCK || msg || I2OSP(out_len, 2) || 0 || DST'),  b_1 = H(b_0 || 1 || DST'),  b_i = H((b_0 xor b_(i-1)) || i || DST')
-// A function of its own per hash and occupancy class, as the streams of hkdf_stream_dev.h are.
-template <class H, int WV>
-CIRCL_HKDF_STREAM_CALL(WV) void xmd(uint32_t *out, uint32_t out_len, const uint8_t *pre, uint32_t pre_len, const uint8_t *body, uint64_t body_len,
-                                    const uint8_t *suf, uint32_t suf_len, const uint8_t *dst, uint32_t dst_len) {
-    constexpr int OW = H::OUT / 4;
-    hkdf::Stream<H, WV> st;
-    uint32_t zero[H::BLOCK / 4], b0[OW], x[OW];
-    for (int i = 0; i < H::BLOCK / 4; i++) zero[i] = 0;
-    st.init();
-    st.put_block(zero);
-    st.put(pre, pre_len);
-    st.put(body, body_len);
-    st.put(suf, suf_len);
-    st.put((uint8_t)(out_len >> 8));
-    st.put((uint8_t)out_len);
-    st.put((uint8_t)0);
-    st.put(dst, dst_len);
-    st.put((uint8_t)dst_len);
-    st.finish(b0);
-    const uint32_t ell = (out_len + H::OUT - 1) / H::OUT;
-    for (uint32_t i = 1; i <= ell; i++) {
-        for (int j = 0; j < OW; j++) x[j] = i == 1 ? b0[j] : b0[j] ^ out[(i - 2) * OW + j];
-        st.init();
-        st.put(reinterpret_cast<const uint8_t *>(x), H::OUT);
-        st.put((uint8_t)i);
-        st.put(dst, dst_len);
-        st.put((uint8_t)dst_len);
-        st.finish(out + (i - 1) * OW);
-    }
-    for (int j = 0; j < OW; j++) b0[j] = x[j] = 0;
 }
 
 // the words an xmd of COUNT field elements needs

@@ -16,9 +16,7 @@
 //                     branch or address depends on k or P (DESIGN.md 4.8f weighs it against a masked radix-16 table).
 //   sc_mul / sc_inv   products mod L through sc_muladd; x^(L - 2) by square-and-multiply over the PUBLIC exponent (its bits steer
 //                     wave-uniform branches), 252 squarings and 65 products for every x.  0 maps to 0: the caller masks it.
-//   xmd64             expand_message_xmd(SHA-512, pre || body || suf, DST, 64): pre and suf are bytes the lane built, body is the
-//                     caller's bytes in global memory; exactly one b_1.  1 <= len(DST) <= 255 (RFC 9380's rule for a longer DST is
-//                     not implemented: the entry points refuse it).
+//   (hashing)         expand_message_xmd is hkdf::xmd<hkdf::Sha512, WV>(out, 64, ...) of hkdf_stream_dev.h: exactly one b_1.
 #pragma once
 #include <stdint.h>
 
@@ -236,36 +234,6 @@ CIRCL_HD void sc_inv(uint32_t out[8], const uint32_t x[8]) {
 }
 
 // ---- hashing -----------------------------------------------------------------------------------------------------------------
-// uniform[0 .. 64) = expand_message_xmd(SHA-512, pre || body || suf, dst, 64) as sixteen little-endian words:
-//   b_0 = H(0^128 || msg || I2OSP(64, 2) || 0 || DST'),  b_1 = H(b_0 || 1 || DST'),  DST' = dst || I2OSP(dst_len, 1)
-// A function of its own per occupancy class, as the streams of hkdf_stream_dev.h are.
-template <int WV>
-CIRCL_HKDF_STREAM_CALL(WV) void xmd64(uint32_t *out, const uint8_t *pre, uint32_t pre_len, const uint8_t *body, uint64_t body_len, const uint8_t *suf,
-                                      uint32_t suf_len, const uint8_t *dst, uint32_t dst_len) {
-    using H = hkdf::Sha512;
-    hkdf::Stream<H, WV> st;
-    uint32_t zero[H::BLOCK / 4], b0[16];
-    for (int i = 0; i < H::BLOCK / 4; i++) zero[i] = 0;
-    st.init();
-    st.put_block(zero);
-    st.put(pre, pre_len);
-    st.put(body, body_len);
-    st.put(suf, suf_len);
-    st.put((uint8_t)0);
-    st.put((uint8_t)64);
-    st.put((uint8_t)0);
-    st.put(dst, dst_len);
-    st.put((uint8_t)dst_len);
-    st.finish(b0);
-    st.init();
-    st.put(reinterpret_cast<const uint8_t *>(b0), 64);
-    st.put((uint8_t)1);
-    st.put(dst, dst_len);
-    st.put((uint8_t)dst_len);
-    st.finish(out);
-    for (int i = 0; i < 16; i++) b0[i] = 0;
-}
-
 // group.Ristretto255.HashToElement on the 64 uniform bytes: each half masked to 255 bits and mapped, the two points added
 CIRCL_HD Ge r255_from_uniform(const uint32_t u[16]) { return r255_add(r255_map(u), r255_map(u + 8)); }
 

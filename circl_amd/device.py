@@ -496,77 +496,87 @@ class HpkeSuiteDevice:
         return out, ok
 
 
-class OprfDevice:
+class _OprfGroupDevice:
+    """The group operations and the proof-free part of OPRF for one suite on resident tensors, on torch's current stream, written once:
+    OprfDevice and NistpOprfDevice bind it.  _group / _oprf: the prefixes of the symbols (and of the names in error messages); _lead: the
+    arguments every call starts with (the curve id, or none); Ns / Ne / Nh: bytes of a scalar, an element, an output; _nonuniform:
+    hash_to_group takes a flags argument."""
+
+    def _out(self, *shape):
+        return torch.empty(shape, dtype=torch.uint8, device=self.device)
+
+    def _scalars(self, t, n):
+        """(pointer, stride) of n scalar rows, or of one row shared by the batch"""
+        shared = t.numel() == self.Ns and n != 1
+        assert shared or t.shape == (n, self.Ns), (t.shape, n)
+        return _chk(t, self.Ns), 0 if shared else self.Ns
+
+    def _call(self, name, *args):
+        nat.check(getattr(self.L, "circl_hip_" + name)(*self._lead, *args, _stream()), name)
+
+    def _hash(self, name, width, msgs, n, dst, flags=()):
+        import numpy as np
+        d = np.frombuffer(bytes(dst) + b"\0", np.uint8)      # the tag is host bytes in both forms
+        out = self._out(n, width)
+        self._call(self._group + name, *_rag_args(msgs), d.ctypes.data_as(C.c_void_p), len(dst), *flags, _chk(out), n)
+        return out
+
+    def hash_to_group(self, msgs, n, dst, nonuniform=False):
+        return self._hash("_hash_to_group_dev", self.Ne, msgs, n, dst, (1 if nonuniform else 0,) if self._nonuniform else ())
+
+    def hash_to_scalar(self, msgs, n, dst):
+        return self._hash("_hash_to_scalar_dev", self.Ns, msgs, n, dst)
+
+    def scalar_mult(self, scalars, elems=None, invert=False, n=None):
+        n = elems.shape[0] if elems is not None else (scalars.shape[0] if n is None else n)
+        out, ok = self._out(n, self.Ne), self._out(n)
+        self._call(self._group + "_scalar_mult_dev", *self._scalars(scalars, n), None if elems is None else _chk(elems, self.Ne), 1 if invert else 0,
+                   _chk(out), _chk(ok), n)
+        return out, ok
+
+    def derive_keypair(self, mode, seeds, infos=None):
+        n = seeds.shape[0]
+        sk, pk, ok = self._out(n, self.Ns), self._out(n, self.Ne), self._out(n)
+        self._call(self._oprf + "_derive_keypair_dev", mode, _chk(seeds, 32), *_rag_args(infos), _chk(sk), _chk(pk), _chk(ok), n)
+        return sk, pk, ok
+
+    def blind(self, mode, inputs, blinds):
+        n = blinds.shape[0]
+        out, ok = self._out(n, self.Ne), self._out(n)
+        self._call(self._oprf + "_blind_dev", mode, *_rag_args(inputs), _chk(blinds, self.Ns), _chk(out), _chk(ok), n)
+        return out, ok
+
+    def evaluate(self, sk, blinded):
+        n = blinded.shape[0]
+        out, ok = self._out(n, self.Ne), self._out(n)
+        self._call(self._oprf + "_evaluate_dev", *self._scalars(sk, n), _chk(blinded, self.Ne), _chk(out), _chk(ok), n)
+        return out, ok
+
+    def finalize(self, inputs, blinds, evaluated):
+        n = blinds.shape[0]
+        out, ok = self._out(n, self.Nh), self._out(n)
+        self._call(self._oprf + "_finalize_dev", *_rag_args(inputs), _chk(blinds, self.Ns), _chk(evaluated, self.Ne), _chk(out), _chk(ok), n)
+        return out, ok
+
+    def full_evaluate(self, mode, sk, inputs, n):
+        out, ok = self._out(n, self.Nh), self._out(n)
+        self._call(self._oprf + "_full_evaluate_dev", mode, *self._scalars(sk, n), *_rag_args(inputs), _chk(out), _chk(ok), n)
+        return out, ok
+
+
+class OprfDevice(_OprfGroupDevice):
     """ristretto255 and base-mode OPRF (suite ristretto255-SHA512) on resident tensors (circl_hip_ristretto255_*_dev, circl_hip_oprf_*_dev),
     on torch's current stream.  Elements, scalars, keys and blinds are (n, 32) uint8 tensors, OPRF outputs (n, 64); ragged inputs are Ragged
     objects (or None: every item empty).  A key or scalar of shape (32,) or (1, 32) is shared by the batch.  Failed items have ok = 0 and zero
     rows."""
+    _group, _oprf, _lead, _nonuniform, Ns, Ne, Nh = "ristretto255", "oprf", (), False, 32, 32, 64
 
     def __init__(self, device="cuda"):
         self.device = device
         self.L = nat.lib()
 
-    def _out(self, *shape):
-        return torch.empty(shape, dtype=torch.uint8, device=self.device)
-
-    @staticmethod
-    def _scalars(t, n):
-        """(pointer, stride) of n scalar rows, or of one row shared by the batch"""
-        shared = t.numel() == 32 and n != 1
-        assert shared or t.shape == (n, 32), (t.shape, n)
-        return _chk(t, 32), 0 if shared else 32
-
-    def _hash(self, fn, msgs, n, dst):
-        import numpy as np
-        d = np.frombuffer(bytes(dst) + b"\0", np.uint8)      # the tag is host bytes in both forms
-        out = self._out(n, 32)
-        nat.check(fn(*_rag_args(msgs), d.ctypes.data_as(C.c_void_p), len(dst), _chk(out), n, _stream()), "ristretto255_hash_dev")
-        return out
-
     def hash_to_group(self, msgs, n, dst):
-        return self._hash(self.L.circl_hip_ristretto255_hash_to_group_dev, msgs, n, dst)
-
-    def hash_to_scalar(self, msgs, n, dst):
-        return self._hash(self.L.circl_hip_ristretto255_hash_to_scalar_dev, msgs, n, dst)
-
-    def scalar_mult(self, scalars, elems=None, invert=False, n=None):
-        n = elems.shape[0] if elems is not None else (scalars.shape[0] if n is None else n)
-        out, ok = self._out(n, 32), self._out(n)
-        nat.check(self.L.circl_hip_ristretto255_scalar_mult_dev(*self._scalars(scalars, n), None if elems is None else _chk(elems, 32), 1 if invert else 0,
-                                                                _chk(out), _chk(ok), n, _stream()), "ristretto255_scalar_mult_dev")
-        return out, ok
-
-    def derive_keypair(self, mode, seeds, infos=None):
-        n = seeds.shape[0]
-        sk, pk, ok = self._out(n, 32), self._out(n, 32), self._out(n)
-        nat.check(self.L.circl_hip_oprf_derive_keypair_dev(mode, _chk(seeds, 32), *_rag_args(infos), _chk(sk), _chk(pk), _chk(ok), n, _stream()),
-                  "oprf_derive_keypair_dev")
-        return sk, pk, ok
-
-    def blind(self, mode, inputs, blinds):
-        n = blinds.shape[0]
-        out, ok = self._out(n, 32), self._out(n)
-        nat.check(self.L.circl_hip_oprf_blind_dev(mode, *_rag_args(inputs), _chk(blinds, 32), _chk(out), _chk(ok), n, _stream()), "oprf_blind_dev")
-        return out, ok
-
-    def evaluate(self, sk, blinded):
-        n = blinded.shape[0]
-        out, ok = self._out(n, 32), self._out(n)
-        nat.check(self.L.circl_hip_oprf_evaluate_dev(*self._scalars(sk, n), _chk(blinded, 32), _chk(out), _chk(ok), n, _stream()), "oprf_evaluate_dev")
-        return out, ok
-
-    def finalize(self, inputs, blinds, evaluated):
-        n = blinds.shape[0]
-        out, ok = self._out(n, 64), self._out(n)
-        nat.check(self.L.circl_hip_oprf_finalize_dev(*_rag_args(inputs), _chk(blinds, 32), _chk(evaluated, 32), _chk(out), _chk(ok), n, _stream()),
-                  "oprf_finalize_dev")
-        return out, ok
-
-    def full_evaluate(self, mode, sk, inputs, n):
-        out, ok = self._out(n, 64), self._out(n)
-        nat.check(self.L.circl_hip_oprf_full_evaluate_dev(mode, *self._scalars(sk, n), *_rag_args(inputs), _chk(out), _chk(ok), n, _stream()),
-                  "oprf_full_evaluate_dev")
-        return out, ok
+        return super().hash_to_group(msgs, n, dst)
 
     # ---- batch DLEQ proofs and the verifiable modes (circl_hip_dleq_*_dev, circl_hip_oprf_poprf_*_dev) ----
     @staticmethod
@@ -739,82 +749,17 @@ class AesGcmDevice:
         return pt, ok
 
 
-class NistpOprfDevice:
+class NistpOprfDevice(_OprfGroupDevice):
     """P-256 / P-384 and base-mode OPRF on them (suites P256-SHA256, P384-SHA384) on resident tensors (circl_hip_nistp_*_dev,
     circl_hip_oprf_nistp_*_dev), on torch's current stream; shaped like OprfDevice.  curve = 256 or 384.  Scalars, keys and blinds are (n, Ns)
     big-endian rows (Ns = 32 / 48), elements (n, Ne) SEC 1 compressed rows (Ne = 33 / 49; the identity: the zero row), seeds (n, 32), OPRF
     outputs (n, Nh = Ns); ragged inputs are Ragged objects (or None: every item empty).  A key or scalar of shape (Ns,) or (1, Ns) is shared
     by the batch.  Failed items have ok = 0 and zero rows."""
+    _group, _oprf, _nonuniform = "nistp", "oprf_nistp", True
 
     def __init__(self, curve, device="cuda"):
         if curve not in (256, 384):
             raise ValueError("curve is 256 or 384")
-        self.curve, self.device, self.L = curve, device, nat.lib()
+        self.curve, self.device, self.L, self._lead = curve, device, nat.lib(), (curve,)
         self.Ns = curve // 8
         self.Ne, self.Nh = self.Ns + 1, self.Ns
-
-    def _out(self, *shape):
-        return torch.empty(shape, dtype=torch.uint8, device=self.device)
-
-    def _scalars(self, t, n):
-        shared = t.numel() == self.Ns and n != 1
-        assert shared or t.shape == (n, self.Ns), (t.shape, n)
-        return _chk(t, self.Ns), 0 if shared else self.Ns
-
-    @staticmethod
-    def _dst(dst):
-        import numpy as np
-        return np.frombuffer(bytes(dst) + b"\0", np.uint8)      # the tag is host bytes in both forms
-
-    def hash_to_group(self, msgs, n, dst, nonuniform=False):
-        d, out = self._dst(dst), self._out(n, self.Ne)
-        nat.check(self.L.circl_hip_nistp_hash_to_group_dev(self.curve, *_rag_args(msgs), d.ctypes.data_as(C.c_void_p), len(dst), 1 if nonuniform else 0,
-                                                           _chk(out), n, _stream()), "nistp_hash_to_group_dev")
-        return out
-
-    def hash_to_scalar(self, msgs, n, dst):
-        d, out = self._dst(dst), self._out(n, self.Ns)
-        nat.check(self.L.circl_hip_nistp_hash_to_scalar_dev(self.curve, *_rag_args(msgs), d.ctypes.data_as(C.c_void_p), len(dst), _chk(out), n, _stream()),
-                  "nistp_hash_to_scalar_dev")
-        return out
-
-    def scalar_mult(self, scalars, elems=None, invert=False, n=None):
-        n = elems.shape[0] if elems is not None else (scalars.shape[0] if n is None else n)
-        out, ok = self._out(n, self.Ne), self._out(n)
-        nat.check(self.L.circl_hip_nistp_scalar_mult_dev(self.curve, *self._scalars(scalars, n), None if elems is None else _chk(elems, self.Ne),
-                                                         1 if invert else 0, _chk(out), _chk(ok), n, _stream()), "nistp_scalar_mult_dev")
-        return out, ok
-
-    def derive_keypair(self, mode, seeds, infos=None):
-        n = seeds.shape[0]
-        sk, pk, ok = self._out(n, self.Ns), self._out(n, self.Ne), self._out(n)
-        nat.check(self.L.circl_hip_oprf_nistp_derive_keypair_dev(self.curve, mode, _chk(seeds, 32), *_rag_args(infos), _chk(sk), _chk(pk), _chk(ok), n,
-                                                                 _stream()), "oprf_nistp_derive_keypair_dev")
-        return sk, pk, ok
-
-    def blind(self, mode, inputs, blinds):
-        n = blinds.shape[0]
-        out, ok = self._out(n, self.Ne), self._out(n)
-        nat.check(self.L.circl_hip_oprf_nistp_blind_dev(self.curve, mode, *_rag_args(inputs), _chk(blinds, self.Ns), _chk(out), _chk(ok), n, _stream()),
-                  "oprf_nistp_blind_dev")
-        return out, ok
-
-    def evaluate(self, sk, blinded):
-        n = blinded.shape[0]
-        out, ok = self._out(n, self.Ne), self._out(n)
-        nat.check(self.L.circl_hip_oprf_nistp_evaluate_dev(self.curve, *self._scalars(sk, n), _chk(blinded, self.Ne), _chk(out), _chk(ok), n, _stream()),
-                  "oprf_nistp_evaluate_dev")
-        return out, ok
-
-    def finalize(self, inputs, blinds, evaluated):
-        n = blinds.shape[0]
-        out, ok = self._out(n, self.Nh), self._out(n)
-        nat.check(self.L.circl_hip_oprf_nistp_finalize_dev(self.curve, *_rag_args(inputs), _chk(blinds, self.Ns), _chk(evaluated, self.Ne), _chk(out),
-                                                           _chk(ok), n, _stream()), "oprf_nistp_finalize_dev")
-        return out, ok
-
-    def full_evaluate(self, mode, sk, inputs, n):
-        out, ok = self._out(n, self.Nh), self._out(n)
-        nat.check(self.L.circl_hip_oprf_nistp_full_evaluate_dev(self.curve, mode, *self._scalars(sk, n), *_rag_args(inputs), _chk(out), _chk(ok), n,
-                                                                _stream()), "oprf_nistp_full_evaluate_dev")
-        return out, ok

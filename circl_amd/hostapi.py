@@ -1134,94 +1134,187 @@ class HpkeSuite:
         return out, ok
 
 
-# ---- ristretto255 (group/ristretto255.go) and base-mode OPRF (oprf/keys.go, client.go, server.go; RFC 9497, ristretto255-SHA512) ----
+# ---- ristretto255 (group/ristretto255.go), NIST P-256 / P-384 (group/short.go) and base-mode OPRF on them (oprf/keys.go, client.go, server.go;
+# RFC 9497, suites ristretto255-SHA512, P256-SHA256 and P384-SHA384) ----
 OPRF_MODE_OPRF, OPRF_MODE_VOPRF, OPRF_MODE_POPRF = range(3)
 R255_INVERT = 1
 
 
-def _scalar_rows(x, n=None):
-    """(rows, stride): one 32-byte scalar (bytes or a (32,) / (1, 32) array with n given) is shared by the batch, stride 0"""
-    a = _u8(x, 32)
+def _scalar_rows(x, n=None, width=32):
+    """(rows, stride): one scalar of `width` bytes (bytes or a (width,) / (1, width) array with n given) is shared by the batch, stride 0"""
+    a = _u8(x, width)
     if n is not None and len(a) == 1 and n != 1:
         return a, 0
     if n is not None and len(a) != n:
         raise ValueError("need 1 or %d scalar rows, got %d" % (n, len(a)))
-    return a, 32
+    return a, width
+
+
+class _OprfSuite:
+    """The group operations and the proof-free part of OPRF for one suite of the C ABI, written once.  The ristretto255_* / oprf_*
+    functions below and NistpOprf bind it.  group / oprf: the prefixes of the symbols (and of the names in error messages); lead: the
+    arguments every call starts with (the curve id, or none); Ns / Ne / Nh: bytes of a scalar, an element, an output; tail: the end of the
+    context string; nonuniform: hash_to_group takes a flags argument; err: what a ValueError of finalize is named by."""
+
+    def __init__(self, group, oprf, lead, Ns, Ne, Nh, tail, nonuniform, err):
+        self.group, self.oprf, self.lead, self.Ns, self.Ne, self.Nh, self.tail, self.nonuniform, self.err = group, oprf, lead, Ns, Ne, Nh, tail, nonuniform, err
+
+    def _call(self, name, *args):
+        nat.check(getattr(nat.lib(), "circl_hip_" + name)(*self.lead, *args), name)
+
+    def context_string(self, mode):
+        return b"OPRFV1-" + bytes([mode]) + self.tail
+
+    def _hash(self, name, width, msgs, dst, flags, device):
+        n = len(msgs)
+        (mb, mo), d, out = _blob(msgs), np.frombuffer(bytes(dst) + b"\0", np.uint8), np.empty((n, width), np.uint8)
+        self._call(self.group + name, _p(mb), _p(mo), _p(d), len(dst), *flags, _p(out), n, device)
+        return out
+
+    def hash_to_group(self, msgs, dst, nonuniform, device):
+        return self._hash("_hash_to_group", self.Ne, msgs, dst, (1 if nonuniform else 0,) if self.nonuniform else (), device)
+
+    def hash_to_scalar(self, msgs, dst, device):
+        return self._hash("_hash_to_scalar", self.Ns, msgs, dst, (), device)
+
+    def scalar_mult(self, scalars, elems, invert, n, device):
+        elems = None if elems is None else _u8(elems, self.Ne)
+        n = len(elems) if elems is not None else n
+        sc, stride = _scalar_rows(scalars, n, self.Ns)
+        n = len(sc) if n is None else n
+        out, ok = np.empty((n, self.Ne), np.uint8), np.empty(n, np.uint8)
+        self._call(self.group + "_scalar_mult", _p(sc), stride, _po(elems), R255_INVERT if invert else 0, _p(out), _p(ok), n, device)
+        return out, ok
+
+    def derive_keypair(self, mode, seeds, infos, device):
+        seeds = _u8(seeds, 32)
+        n = len(seeds)
+        (ib, io), sk, pk, ok = _rag(infos, n), np.empty((n, self.Ns), np.uint8), np.empty((n, self.Ne), np.uint8), np.empty(n, np.uint8)
+        self._call(self.oprf + "_derive_keypair", mode, _p(seeds), _po(ib), _po(io), _p(sk), _p(pk), _p(ok), n, device)
+        return sk, pk, ok
+
+    def blind(self, mode, inputs, blinds, device):
+        blinds = _u8(blinds, self.Ns)
+        n = len(blinds)
+        (ib, io), out, ok = _rag(inputs, n), np.empty((n, self.Ne), np.uint8), np.empty(n, np.uint8)
+        self._call(self.oprf + "_blind", mode, _po(ib), _po(io), _p(blinds), _p(out), _p(ok), n, device)
+        return out, ok
+
+    def evaluate(self, sk, blinded, device):
+        blinded = _u8(blinded, self.Ne)
+        n = len(blinded)
+        (key, stride), out, ok = _scalar_rows(sk, n, self.Ns), np.empty((n, self.Ne), np.uint8), np.empty(n, np.uint8)
+        self._call(self.oprf + "_evaluate", _p(key), stride, _p(blinded), _p(out), _p(ok), n, device)
+        return out, ok
+
+    def finalize(self, inputs, blinds, evaluated, device):
+        blinds, evaluated = _u8(blinds, self.Ns), _u8(evaluated, self.Ne)
+        n = len(blinds)
+        if len(evaluated) != n:
+            raise ValueError("%sfinalize: %d blinds, %d evaluated elements" % (self.err, n, len(evaluated)))
+        (ib, io), out, ok = _rag(inputs, n), np.empty((n, self.Nh), np.uint8), np.empty(n, np.uint8)
+        self._call(self.oprf + "_finalize", _po(ib), _po(io), _p(blinds), _p(evaluated), _p(out), _p(ok), n, device)
+        return out, ok
+
+    def full_evaluate(self, mode, sk, inputs, device):
+        n = len(inputs)
+        (key, stride), (ib, io), out, ok = _scalar_rows(sk, n, self.Ns), _blob(inputs), np.empty((n, self.Nh), np.uint8), np.empty(n, np.uint8)
+        self._call(self.oprf + "_full_evaluate", mode, _p(key), stride, _p(ib), _p(io), _p(out), _p(ok), n, device)
+        return out, ok
+
+
+_R255 = _OprfSuite("ristretto255", "oprf", (), 32, 32, 64, b"-ristretto255-SHA512", False, "oprf_")
 
 
 def ristretto255_hash_to_group(msgs, dst, device=0):
     """Ristretto255.HashToElement(msg_i, dst) -> (n, 32); one dst of 1..255 bytes for the batch"""
-    n = len(msgs)
-    (mb, mo), d, out = _blob(msgs), np.frombuffer(bytes(dst) + b"\0", np.uint8), np.empty((n, 32), np.uint8)
-    nat.check(nat.lib().circl_hip_ristretto255_hash_to_group(_p(mb), _p(mo), _p(d), len(dst), _p(out), n, device), "ristretto255_hash_to_group")
-    return out
+    return _R255.hash_to_group(msgs, dst, False, device)
 
 
 def ristretto255_hash_to_scalar(msgs, dst, device=0):
     """Ristretto255.HashToScalar(msg_i, dst) -> (n, 32)"""
-    n = len(msgs)
-    (mb, mo), d, out = _blob(msgs), np.frombuffer(bytes(dst) + b"\0", np.uint8), np.empty((n, 32), np.uint8)
-    nat.check(nat.lib().circl_hip_ristretto255_hash_to_scalar(_p(mb), _p(mo), _p(d), len(dst), _p(out), n, device), "ristretto255_hash_to_scalar")
-    return out
+    return _R255.hash_to_scalar(msgs, dst, device)
 
 
 def ristretto255_scalar_mult(scalars, elems=None, invert=False, n=None, device=0):
     """scalar_i elem_i (elems None: the generator; invert: by scalar_i^-1) -> (out (n, 32), ok (n,)).  One scalar row with n (or with
     several elems) is shared by the batch.  ok = 0 and a zero row for an element that does not decode, a scalar >= L, an inverse of 0."""
-    elems = None if elems is None else _u8(elems, 32)
-    n = len(elems) if elems is not None else n
-    sc, stride = _scalar_rows(scalars, n)
-    n = len(sc) if n is None else n
-    out, ok = np.empty((n, 32), np.uint8), np.empty(n, np.uint8)
-    nat.check(nat.lib().circl_hip_ristretto255_scalar_mult(_p(sc), stride, _po(elems), R255_INVERT if invert else 0, _p(out), _p(ok), n, device),
-              "ristretto255_scalar_mult")
-    return out, ok
+    return _R255.scalar_mult(scalars, elems, invert, n, device)
 
 
 def oprf_derive_keypair(mode, seeds, infos=None, device=0):
     """oprf.DeriveKey(suite, mode, seed_i, info_i) -> (sk (n, 32), pk (n, 32), ok (n,))"""
-    seeds = _u8(seeds, 32)
-    n = len(seeds)
-    (ib, io), sk, pk, ok = _rag(infos, n), np.empty((n, 32), np.uint8), np.empty((n, 32), np.uint8), np.empty(n, np.uint8)
-    nat.check(nat.lib().circl_hip_oprf_derive_keypair(mode, _p(seeds), _po(ib), _po(io), _p(sk), _p(pk), _p(ok), n, device), "oprf_derive_keypair")
-    return sk, pk, ok
+    return _R255.derive_keypair(mode, seeds, infos, device)
 
 
 def oprf_blind(mode, inputs, blinds, device=0):
     """Client.DeterministicBlind: blind_i HashToGroup(input_i) -> (blinded (n, 32), ok (n,)); the caller draws the blinds"""
-    blinds = _u8(blinds, 32)
-    n = len(blinds)
-    (ib, io), out, ok = _rag(inputs, n), np.empty((n, 32), np.uint8), np.empty(n, np.uint8)
-    nat.check(nat.lib().circl_hip_oprf_blind(mode, _po(ib), _po(io), _p(blinds), _p(out), _p(ok), n, device), "oprf_blind")
-    return out, ok
+    return _R255.blind(mode, inputs, blinds, device)
 
 
 def oprf_evaluate(sk, blinded, device=0):
     """base-mode Server.Evaluate: sk blinded_i -> (evaluated (n, 32), ok (n,)); sk = one key for the batch (32 bytes) or (n, 32) rows"""
-    blinded = _u8(blinded, 32)
-    n = len(blinded)
-    (key, stride), out, ok = _scalar_rows(sk, n), np.empty((n, 32), np.uint8), np.empty(n, np.uint8)
-    nat.check(nat.lib().circl_hip_oprf_evaluate(_p(key), stride, _p(blinded), _p(out), _p(ok), n, device), "oprf_evaluate")
-    return out, ok
+    return _R255.evaluate(sk, blinded, device)
 
 
 def oprf_finalize(inputs, blinds, evaluated, device=0):
     """base-mode Client.Finalize -> (outputs (n, 64), ok (n,))"""
-    blinds, evaluated = _u8(blinds, 32), _u8(evaluated, 32)
-    n = len(blinds)
-    if len(evaluated) != n:
-        raise ValueError("oprf_finalize: %d blinds, %d evaluated elements" % (n, len(evaluated)))
-    (ib, io), out, ok = _rag(inputs, n), np.empty((n, 64), np.uint8), np.empty(n, np.uint8)
-    nat.check(nat.lib().circl_hip_oprf_finalize(_po(ib), _po(io), _p(blinds), _p(evaluated), _p(out), _p(ok), n, device), "oprf_finalize")
-    return out, ok
+    return _R255.finalize(inputs, blinds, evaluated, device)
 
 
 def oprf_full_evaluate(mode, sk, inputs, device=0):
     """Server.FullEvaluate (mode 0) / VerifiableServer.FullEvaluate (mode 1) -> (outputs (n, 64), ok (n,)); sk as in oprf_evaluate"""
-    n = len(inputs)
-    (key, stride), (ib, io), out, ok = _scalar_rows(sk, n), _blob(inputs), np.empty((n, 64), np.uint8), np.empty(n, np.uint8)
-    nat.check(nat.lib().circl_hip_oprf_full_evaluate(mode, _p(key), stride, _p(ib), _p(io), _p(out), _p(ok), n, device), "oprf_full_evaluate")
-    return out, ok
+    return _R255.full_evaluate(mode, sk, inputs, device)
+
+
+class NistpOprf:
+    """The group operations and the proof-free part of OPRF on one NIST curve (circl_hip_nistp_*, circl_hip_oprf_nistp_*), shaped like the
+    ristretto255 functions above.  curve = 256 or 384.  Scalars, keys and blinds are big-endian rows of Ns = 32 / 48 bytes, elements SEC 1
+    compressed rows of Ne = 33 / 49 (the identity: the zero row), seeds rows of 32, OPRF outputs rows of Nh = 32 / 48.  A single scalar row
+    is shared by the batch.  Failed items have ok = 0 and zero rows."""
+
+    def __init__(self, curve, device=0):
+        if curve not in (256, 384):
+            raise ValueError("curve is 256 or 384")
+        self.curve, self.device = curve, device
+        self.Ns = curve // 8
+        self.Ne, self.Nh = self.Ns + 1, self.Ns
+        self._s = _OprfSuite("nistp", "oprf_nistp", (curve,), self.Ns, self.Ne, self.Nh, b"-P256-SHA256" if curve == 256 else b"-P384-SHA384", True, "")
+
+    def context_string(self, mode):
+        return self._s.context_string(mode)
+
+    def hash_to_group(self, msgs, dst, nonuniform=False):
+        """HashToElement(msg_i, dst) (nonuniform: HashToElementNonUniform) -> (n, Ne); one dst of 1..255 bytes for the batch"""
+        return self._s.hash_to_group(msgs, dst, nonuniform, self.device)
+
+    def hash_to_scalar(self, msgs, dst):
+        """HashToScalar(msg_i, dst) -> (n, Ns)"""
+        return self._s.hash_to_scalar(msgs, dst, self.device)
+
+    def scalar_mult(self, scalars, elems=None, invert=False, n=None):
+        """scalar_i elem_i (elems None: the generator; invert: by scalar_i^-1) -> (out (n, Ne), ok (n,))"""
+        return self._s.scalar_mult(scalars, elems, invert, n, self.device)
+
+    def derive_keypair(self, mode, seeds, infos=None):
+        """oprf.DeriveKey(suite, mode, seed_i, info_i) -> (sk (n, Ns), pk (n, Ne), ok (n,))"""
+        return self._s.derive_keypair(mode, seeds, infos, self.device)
+
+    def blind(self, mode, inputs, blinds):
+        """Client.DeterministicBlind -> (blinded (n, Ne), ok (n,)); the caller draws the blinds"""
+        return self._s.blind(mode, inputs, blinds, self.device)
+
+    def evaluate(self, sk, blinded):
+        """base-mode Server.Evaluate -> (evaluated (n, Ne), ok (n,)); sk = one key for the batch or (n, Ns) rows"""
+        return self._s.evaluate(sk, blinded, self.device)
+
+    def finalize(self, inputs, blinds, evaluated):
+        """base-mode Client.Finalize -> (outputs (n, Nh), ok (n,))"""
+        return self._s.finalize(inputs, blinds, evaluated, self.device)
+
+    def full_evaluate(self, mode, sk, inputs):
+        """Server.FullEvaluate (mode 0) / VerifiableServer.FullEvaluate (mode 1) -> (outputs (n, Nh), ok (n,)); sk as in evaluate"""
+        return self._s.full_evaluate(mode, sk, inputs, self.device)
 
 
 # ---- batch DLEQ proofs (zk/dleq, the ...RFC9497 forms) and the verifiable modes of OPRF (VOPRF, POPRF) --------------------------------
@@ -1229,7 +1322,7 @@ DLEQ_NO_IDENTITY = 1
 
 
 def oprf_context_string(mode):
-    return b"OPRFV1-" + bytes([mode]) + b"-ristretto255-SHA512"
+    return _R255.context_string(mode)
 
 
 def _req_off(req_off):
@@ -1465,99 +1558,3 @@ class AesGcm:
         nat.check(self.L.circl_hip_aesgcm_open(self.key_size, _p(self.keys), stride, _p(nonces), nstride, _po(seq), _p(cb), _p(po), _po(ab), _po(ao), _p(pt),
                                                _p(ok), n, self.device), "aesgcm_open")
         return _unrag(pt, po), ok
-
-
-# ---- NIST P-256 / P-384 (group/short.go) and base-mode OPRF on them (RFC 9497, suites P256-SHA256 and P384-SHA384) ---------------------
-class NistpOprf:
-    """The group operations and the proof-free part of OPRF on one NIST curve (circl_hip_nistp_*, circl_hip_oprf_nistp_*), shaped like the
-    ristretto255 functions above.  curve = 256 or 384.  Scalars, keys and blinds are big-endian rows of Ns = 32 / 48 bytes, elements SEC 1
-    compressed rows of Ne = 33 / 49 (the identity: the zero row), seeds rows of 32, OPRF outputs rows of Nh = 32 / 48.  A single scalar row
-    is shared by the batch.  Failed items have ok = 0 and zero rows."""
-
-    def __init__(self, curve, device=0):
-        if curve not in (256, 384):
-            raise ValueError("curve is 256 or 384")
-        self.curve, self.device, self.L = curve, device, nat.lib()
-        self.Ns = curve // 8
-        self.Ne, self.Nh = self.Ns + 1, self.Ns
-
-    def context_string(self, mode):
-        return b"OPRFV1-" + bytes([mode]) + (b"-P256-SHA256" if self.curve == 256 else b"-P384-SHA384")
-
-    def _scalar_rows(self, x, n=None):
-        a = _u8(x, self.Ns)
-        if n is not None and len(a) == 1 and n != 1:
-            return a, 0
-        if n is not None and len(a) != n:
-            raise ValueError("need 1 or %d scalar rows, got %d" % (n, len(a)))
-        return a, self.Ns
-
-    def hash_to_group(self, msgs, dst, nonuniform=False):
-        """HashToElement(msg_i, dst) (nonuniform: HashToElementNonUniform) -> (n, Ne); one dst of 1..255 bytes for the batch"""
-        n = len(msgs)
-        (mb, mo), d, out = _blob(msgs), np.frombuffer(bytes(dst) + b"\0", np.uint8), np.empty((n, self.Ne), np.uint8)
-        nat.check(self.L.circl_hip_nistp_hash_to_group(self.curve, _p(mb), _p(mo), _p(d), len(dst), 1 if nonuniform else 0, _p(out), n, self.device),
-                  "nistp_hash_to_group")
-        return out
-
-    def hash_to_scalar(self, msgs, dst):
-        """HashToScalar(msg_i, dst) -> (n, Ns)"""
-        n = len(msgs)
-        (mb, mo), d, out = _blob(msgs), np.frombuffer(bytes(dst) + b"\0", np.uint8), np.empty((n, self.Ns), np.uint8)
-        nat.check(self.L.circl_hip_nistp_hash_to_scalar(self.curve, _p(mb), _p(mo), _p(d), len(dst), _p(out), n, self.device), "nistp_hash_to_scalar")
-        return out
-
-    def scalar_mult(self, scalars, elems=None, invert=False, n=None):
-        """scalar_i elem_i (elems None: the generator; invert: by scalar_i^-1) -> (out (n, Ne), ok (n,))"""
-        elems = None if elems is None else _u8(elems, self.Ne)
-        n = len(elems) if elems is not None else n
-        sc, stride = self._scalar_rows(scalars, n)
-        n = len(sc) if n is None else n
-        out, ok = np.empty((n, self.Ne), np.uint8), np.empty(n, np.uint8)
-        nat.check(self.L.circl_hip_nistp_scalar_mult(self.curve, _p(sc), stride, _po(elems), 1 if invert else 0, _p(out), _p(ok), n, self.device),
-                  "nistp_scalar_mult")
-        return out, ok
-
-    def derive_keypair(self, mode, seeds, infos=None):
-        """oprf.DeriveKey(suite, mode, seed_i, info_i) -> (sk (n, Ns), pk (n, Ne), ok (n,))"""
-        seeds = _u8(seeds, 32)
-        n = len(seeds)
-        (ib, io), sk, pk, ok = _rag(infos, n), np.empty((n, self.Ns), np.uint8), np.empty((n, self.Ne), np.uint8), np.empty(n, np.uint8)
-        nat.check(self.L.circl_hip_oprf_nistp_derive_keypair(self.curve, mode, _p(seeds), _po(ib), _po(io), _p(sk), _p(pk), _p(ok), n, self.device),
-                  "oprf_nistp_derive_keypair")
-        return sk, pk, ok
-
-    def blind(self, mode, inputs, blinds):
-        """Client.DeterministicBlind -> (blinded (n, Ne), ok (n,)); the caller draws the blinds"""
-        blinds = _u8(blinds, self.Ns)
-        n = len(blinds)
-        (ib, io), out, ok = _rag(inputs, n), np.empty((n, self.Ne), np.uint8), np.empty(n, np.uint8)
-        nat.check(self.L.circl_hip_oprf_nistp_blind(self.curve, mode, _po(ib), _po(io), _p(blinds), _p(out), _p(ok), n, self.device), "oprf_nistp_blind")
-        return out, ok
-
-    def evaluate(self, sk, blinded):
-        """base-mode Server.Evaluate -> (evaluated (n, Ne), ok (n,)); sk = one key for the batch or (n, Ns) rows"""
-        blinded = _u8(blinded, self.Ne)
-        n = len(blinded)
-        (key, stride), out, ok = self._scalar_rows(sk, n), np.empty((n, self.Ne), np.uint8), np.empty(n, np.uint8)
-        nat.check(self.L.circl_hip_oprf_nistp_evaluate(self.curve, _p(key), stride, _p(blinded), _p(out), _p(ok), n, self.device), "oprf_nistp_evaluate")
-        return out, ok
-
-    def finalize(self, inputs, blinds, evaluated):
-        """base-mode Client.Finalize -> (outputs (n, Nh), ok (n,))"""
-        blinds, evaluated = _u8(blinds, self.Ns), _u8(evaluated, self.Ne)
-        n = len(blinds)
-        if len(evaluated) != n:
-            raise ValueError("finalize: %d blinds, %d evaluated elements" % (n, len(evaluated)))
-        (ib, io), out, ok = _rag(inputs, n), np.empty((n, self.Nh), np.uint8), np.empty(n, np.uint8)
-        nat.check(self.L.circl_hip_oprf_nistp_finalize(self.curve, _po(ib), _po(io), _p(blinds), _p(evaluated), _p(out), _p(ok), n, self.device),
-                  "oprf_nistp_finalize")
-        return out, ok
-
-    def full_evaluate(self, mode, sk, inputs):
-        """Server.FullEvaluate (mode 0) / VerifiableServer.FullEvaluate (mode 1) -> (outputs (n, Nh), ok (n,)); sk as in evaluate"""
-        n = len(inputs)
-        (key, stride), (ib, io), out, ok = self._scalar_rows(sk, n), _blob(inputs), np.empty((n, self.Nh), np.uint8), np.empty(n, np.uint8)
-        nat.check(self.L.circl_hip_oprf_nistp_full_evaluate(self.curve, mode, _p(key), stride, _p(ib), _p(io), _p(out), _p(ok), n, self.device),
-                  "oprf_nistp_full_evaluate")
-        return out, ok

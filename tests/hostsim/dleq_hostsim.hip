@@ -169,14 +169,14 @@ int run_poprf() {
     a.scalars = nullptr; a.elems = pk.w; a.elem_stride = 0; a.out = tweaked.w; a.out2 = a.out3 = nullptr;
     for (size_t i = 0; i < n; i++) { hs_poprf_item(dleq::kTweakClient, &a, i); if (!ok[i]) return fail("tweak (client) refused an item"); }
     if (memcmp(tg.w, tweaked.w, 32 * n)) return fail("t G != m G + pkS");
-    // blind, evaluate with t^-1 (base-mode items of oprf_kernels.h), finalize with the info; and the same in one step
+    // blind, evaluate with t^-1 (base-mode items of oprf_group_kernels.h), finalize with the info; and the same in one step
     for (size_t i = 0; i < n; i++) small_scalar(blinds.w + 8 * i, 500 + (uint32_t)i);
     oprf::Args o = {};
-    o.blob = in.p; o.off = in_off.data(); o.scalars = blinds.w; o.scalar_stride = 8; o.out = blinded.w; o.ok = ok.data(); o.n = n;
+    o.blob = in.p; o.off = in_off.data(); o.scalars = blinds.w; o.scalar_stride = 8; o.out = reinterpret_cast<uint8_t *>(blinded.w); o.ok = ok.data(); o.n = n;
     o.dst_len = dleq::mode2_tag(o.dst, true);
-    for (size_t i = 0; i < n; i++) { oprf::item<oprf::kBlind, oprf::WAVES>(o, i); if (!ok[i]) return fail("blind refused an item"); }
-    o.blob = nullptr; o.off = nullptr; o.scalars = tinv.w; o.elems = blinded.w; o.out = evaluated.w;
-    for (size_t i = 0; i < n; i++) { oprf::item<oprf::kEvaluate, oprf::WAVES>(o, i); if (!ok[i]) return fail("evaluate refused an item"); }
+    for (size_t i = 0; i < n; i++) { oprf::Item<oprf::R255, oprf::kBlind, oprf::WAVES>::run(o, i); if (!ok[i]) return fail("blind refused an item"); }
+    o.blob = nullptr; o.off = nullptr; o.scalars = tinv.w; o.elems = reinterpret_cast<const uint8_t *>(blinded.w); o.out = reinterpret_cast<uint8_t *>(evaluated.w);
+    for (size_t i = 0; i < n; i++) { oprf::Item<oprf::R255, oprf::kEvaluate, oprf::WAVES>::run(o, i); if (!ok[i]) return fail("evaluate refused an item"); }
     a.input = in.p; a.input_off = in_off.data(); a.scalars = blinds.w; a.scalar_stride = 8; a.elems = evaluated.w; a.elem_stride = 8; a.out = out.w;
     for (size_t i = 0; i < n; i++) { hs_poprf_item(dleq::kPoprfFinalize, &a, i); if (!ok[i]) return fail("poprf_finalize refused an item"); }
     a.scalars = sk.w; a.scalar_stride = 0; a.elems = nullptr; a.out = full.w;

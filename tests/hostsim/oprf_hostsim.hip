@@ -1,5 +1,5 @@
 // tests/hostsim/oprf_hostsim.hip -- TEST INFRASTRUCTURE: runs the lane-local __host__ __device__ functions of
-// circl_amd/csrc/ristretto255_dev.h and oprf_kernels.h on the CPU (their host instantiation), so that the CPU-only test tier can
+// circl_amd/csrc/ristretto255_dev.h and oprf_group_kernels.h on the CPU (their host instantiation), so that the CPU-only test tier can
 // check the very source the ristretto255 / OPRF kernels are built from against the checker tests/oprf.py.
 // Nothing here is linked into libcirclhip.so.
 //
@@ -14,7 +14,7 @@
 // costs minutes of compile time (every field product inlined into every caller), so the lane-local functions are plain inline here.
 #define CIRCL_HD __host__ __device__ inline
 
-#include "oprf_kernels.h"
+#include "oprf_group_kernels.h"
 
 using namespace circl;
 using ed25519::Ge;
@@ -46,7 +46,7 @@ void hs_from_uniform(uint32_t *out, const uint32_t *u) { r255::r255_encode(out, 
 
 void hs_xmd64(uint32_t *out, const uint8_t *pre, uint32_t pre_len, const uint8_t *body, uint64_t body_len, const uint8_t *suf, uint32_t suf_len,
               const uint8_t *dst, uint32_t dst_len) {
-    r255::xmd64<oprf::WAVES>(out, pre, pre_len, body, body_len, suf, suf_len, dst, dst_len);
+    hkdf::xmd<hkdf::Sha512, oprf::WAVES>(out, 64, pre, pre_len, body, body_len, suf, suf_len, dst, dst_len);
 }
 
 void hs_sc_mul(uint32_t *out, const uint32_t *a, const uint32_t *b) { r255::sc_mul(out, a, b); }
@@ -64,14 +64,14 @@ void hs_base(uint32_t *out, const uint32_t *k) { r255::r255_encode(out, r255::r2
 
 void hs_item(int op, const oprf::Args *a, uint64_t i) {
     switch (op) {
-        case oprf::kHashToGroup: oprf::item<oprf::kHashToGroup, oprf::WAVES>(*a, i); break;
-        case oprf::kHashToScalar: oprf::item<oprf::kHashToScalar, oprf::WAVES>(*a, i); break;
-        case oprf::kScalarMult: oprf::item<oprf::kScalarMult, oprf::WAVES>(*a, i); break;
-        case oprf::kDeriveKeyPair: oprf::item<oprf::kDeriveKeyPair, oprf::WAVES>(*a, i); break;
-        case oprf::kBlind: oprf::item<oprf::kBlind, oprf::WAVES>(*a, i); break;
-        case oprf::kEvaluate: oprf::item<oprf::kEvaluate, oprf::WAVES>(*a, i); break;
-        case oprf::kFinalize: oprf::item<oprf::kFinalize, oprf::WAVES>(*a, i); break;
-        case oprf::kFullEvaluate: oprf::item<oprf::kFullEvaluate, oprf::WAVES>(*a, i); break;
+        case oprf::kHashToGroup: oprf::Item<oprf::R255, oprf::kHashToGroup, oprf::WAVES>::run(*a, i); break;
+        case oprf::kHashToScalar: oprf::Item<oprf::R255, oprf::kHashToScalar, oprf::WAVES>::run(*a, i); break;
+        case oprf::kScalarMult: oprf::Item<oprf::R255, oprf::kScalarMult, oprf::WAVES>::run(*a, i); break;
+        case oprf::kDeriveKeyPair: oprf::Item<oprf::R255, oprf::kDeriveKeyPair, oprf::WAVES>::run(*a, i); break;
+        case oprf::kBlind: oprf::Item<oprf::R255, oprf::kBlind, oprf::WAVES>::run(*a, i); break;
+        case oprf::kEvaluate: oprf::Item<oprf::R255, oprf::kEvaluate, oprf::WAVES>::run(*a, i); break;
+        case oprf::kFinalize: oprf::Item<oprf::R255, oprf::kFinalize, oprf::WAVES>::run(*a, i); break;
+        case oprf::kFullEvaluate: oprf::Item<oprf::R255, oprf::kFullEvaluate, oprf::WAVES>::run(*a, i); break;
     }
 }
 
@@ -103,6 +103,7 @@ struct Rows {
     explicit Rows(size_t words) : w(static_cast<uint32_t *>(calloc(words ? words : 1, 4))) {}
     ~Rows() { free(w); }
     Rows(const Rows &) = delete;
+    uint8_t *b() { return reinterpret_cast<uint8_t *>(w); }
 };
 
 void set_dst(oprf::Args &a, const char *label, int mode) {
@@ -133,35 +134,35 @@ int run(int mode) {
     a.n = n;
     a.ok = ok.data();
     // keys
-    a.blob = info.blob; a.off = info.off.data(); a.elems = seeds.w; a.out = sk.w; a.out2 = pk.w;
+    a.blob = info.blob; a.off = info.off.data(); a.seeds = seeds.w; a.out = sk.b(); a.out2 = pk.b();
     set_dst(a, "DeriveKeyPair", mode);
     for (size_t i = 0; i < n; i++) { hs_item(oprf::kDeriveKeyPair, &a, i); if (!ok[i]) return fail("derive_keypair refused an item"); }
     // blinds: any non-zero canonical scalars; the keys serve
     for (size_t j = 0; j < 8 * n; j++) blinds.w[j] = sk.w[8 * ((j / 8 + 1) % n) + j % 8];
-    a.blob = in.blob; a.off = in.off.data(); a.scalars = blinds.w; a.scalar_stride = 8; a.elems = nullptr; a.out = blinded.w; a.out2 = nullptr;
+    a.blob = in.blob; a.off = in.off.data(); a.scalars = blinds.w; a.scalar_stride = 8; a.elems = nullptr; a.out = blinded.b(); a.out2 = nullptr;
     set_dst(a, "HashToGroup-", mode);
     for (size_t i = 0; i < n; i++) { hs_item(oprf::kBlind, &a, i); if (!ok[i]) return fail("blind refused an item"); }
     // evaluate under the shared key sk[0], finalize, and the same in one step
-    a.blob = nullptr; a.off = nullptr; a.scalars = sk.w; a.scalar_stride = 0; a.elems = blinded.w; a.out = evaluated.w;
+    a.blob = nullptr; a.off = nullptr; a.scalars = sk.w; a.scalar_stride = 0; a.elems = blinded.b(); a.out = evaluated.b();
     for (size_t i = 0; i < n; i++) { hs_item(oprf::kEvaluate, &a, i); if (!ok[i]) return fail("evaluate refused an item"); }
-    a.blob = in.blob; a.off = in.off.data(); a.scalars = blinds.w; a.scalar_stride = 8; a.elems = evaluated.w; a.out = out.w;
+    a.blob = in.blob; a.off = in.off.data(); a.scalars = blinds.w; a.scalar_stride = 8; a.elems = evaluated.b(); a.out = out.b();
     for (size_t i = 0; i < n; i++) { hs_item(oprf::kFinalize, &a, i); if (!ok[i]) return fail("finalize refused an item"); }
-    a.scalars = sk.w; a.scalar_stride = 0; a.elems = nullptr; a.out = full.w;
+    a.scalars = sk.w; a.scalar_stride = 0; a.elems = nullptr; a.out = full.b();
     for (size_t i = 0; i < n; i++) { hs_item(oprf::kFullEvaluate, &a, i); if (!ok[i]) return fail("full_evaluate refused an item"); }
     if (memcmp(out.w, full.w, 64 * n)) return fail("finalize(evaluate(blind(x))) != full_evaluate(x)");
     // scalar_mult by the inverse undoes a blinding: blind^-1 (blind P) = P = hash_to_group(x)
-    a.blob = nullptr; a.off = nullptr; a.scalars = blinds.w; a.scalar_stride = 8; a.elems = blinded.w; a.out = unblinded.w; a.flags = 1;
+    a.blob = nullptr; a.off = nullptr; a.scalars = blinds.w; a.scalar_stride = 8; a.elems = blinded.b(); a.out = unblinded.b(); a.flags = 1;
     for (size_t i = 0; i < n; i++) { hs_item(oprf::kScalarMult, &a, i); if (!ok[i]) return fail("scalar_mult refused an item"); }
-    a.flags = 0; a.blob = in.blob; a.off = in.off.data(); a.out = evaluated.w;
+    a.flags = 0; a.blob = in.blob; a.off = in.off.data(); a.out = evaluated.b();
     for (size_t i = 0; i < n; i++) hs_item(oprf::kHashToGroup, &a, i);
     if (memcmp(unblinded.w, evaluated.w, 32 * n)) return fail("blind^-1 (blind P) != P");
     for (size_t i = 0; i < n; i++) hs_item(oprf::kHashToScalar, &a, i);
     // failure masks: a zero blind, an element that does not decode
     memset(blinds.w, 0, 32);
     blinded.w[8] = 1;  // s = ...1: negative
-    a.scalars = blinds.w; a.out = unblinded.w;
+    a.scalars = blinds.w; a.out = unblinded.b();
     hs_item(oprf::kBlind, &a, 0);
-    a.scalars = sk.w; a.scalar_stride = 0; a.elems = blinded.w;
+    a.scalars = sk.w; a.scalar_stride = 0; a.elems = blinded.b();
     hs_item(oprf::kEvaluate, &a, 1);
     for (int j = 0; j < 16; j++)
         if (unblinded.w[j]) return fail("a failed item's row is not zero");

@@ -1,5 +1,5 @@
 // tests/hostsim/oprf_nistp_hostsim.hip -- TEST INFRASTRUCTURE: runs the lane-local __host__ __device__ functions of
-// circl_amd/csrc/nistp_dev.h and nistp_kernels.h on the CPU (their host instantiation), so that the CPU-only test tier can check the
+// circl_amd/csrc/nistp_dev.h and oprf_group_kernels.h on the CPU (their host instantiation), so that the CPU-only test tier can check the
 // very source the P-256 / P-384 kernels are built from against the checker tests/oprf_nistp.py.
 // Nothing here is linked into libcirclhip.so.
 //
@@ -14,10 +14,12 @@
 // Only the host side of this file is ever run, and it is compiled host-only: plain inline instead of the device's forced inlining.
 #define CIRCL_HD __host__ __device__ inline
 
-#include "nistp_kernels.h"
+#include "oprf_group_kernels.h"
 
 using namespace circl;
 using namespace circl::nistp;
+using oprf::Args;
+using oprf::WAVES;
 
 namespace {
 
@@ -84,18 +86,18 @@ struct Sim {
     static int sc_canonical(const uint32_t *a) { return (int)sc_is_canonical<C>(sc_load<C>(a)); }
     static void xmd_(uint32_t *out, uint32_t out_len, const uint8_t *pre, uint32_t pre_len, const uint8_t *body, uint64_t body_len, const uint8_t *suf,
                      uint32_t suf_len, const uint8_t *dst, uint32_t dst_len) {
-        xmd<typename C::Hash, WAVES>(out, out_len, pre, pre_len, body, body_len, suf, suf_len, dst, dst_len);
+        hkdf::xmd<typename C::Hash, WAVES>(out, out_len, pre, pre_len, body, body_len, suf, suf_len, dst, dst_len);
     }
     static void item(int op, const Args *a, uint64_t i) {
         switch (op) {
-            case kHashToGroup: Item<C, kHashToGroup, WAVES>::run(*a, i); break;
-            case kHashToScalar: Item<C, kHashToScalar, WAVES>::run(*a, i); break;
-            case kScalarMult: Item<C, kScalarMult, WAVES>::run(*a, i); break;
-            case kDeriveKeyPair: Item<C, kDeriveKeyPair, WAVES>::run(*a, i); break;
-            case kBlind: Item<C, kBlind, WAVES>::run(*a, i); break;
-            case kEvaluate: Item<C, kEvaluate, WAVES>::run(*a, i); break;
-            case kFinalize: Item<C, kFinalize, WAVES>::run(*a, i); break;
-            case kFullEvaluate: Item<C, kFullEvaluate, WAVES>::run(*a, i); break;
+            case oprf::kHashToGroup: oprf::Item<oprf::Nistp<C>, oprf::kHashToGroup, WAVES>::run(*a, i); break;
+            case oprf::kHashToScalar: oprf::Item<oprf::Nistp<C>, oprf::kHashToScalar, WAVES>::run(*a, i); break;
+            case oprf::kScalarMult: oprf::Item<oprf::Nistp<C>, oprf::kScalarMult, WAVES>::run(*a, i); break;
+            case oprf::kDeriveKeyPair: oprf::Item<oprf::Nistp<C>, oprf::kDeriveKeyPair, WAVES>::run(*a, i); break;
+            case oprf::kBlind: oprf::Item<oprf::Nistp<C>, oprf::kBlind, WAVES>::run(*a, i); break;
+            case oprf::kEvaluate: oprf::Item<oprf::Nistp<C>, oprf::kEvaluate, WAVES>::run(*a, i); break;
+            case oprf::kFinalize: oprf::Item<oprf::Nistp<C>, oprf::kFinalize, WAVES>::run(*a, i); break;
+            case oprf::kFullEvaluate: oprf::Item<oprf::Nistp<C>, oprf::kFullEvaluate, WAVES>::run(*a, i); break;
         }
     }
 };
@@ -336,37 +338,37 @@ struct Check {
         a.ok = ok.data();
         a.blob = info.blob; a.off = info.off.data(); a.seeds = seeds.w(); a.out = sk.b; a.out2 = pk.b;
         set_dst(a, "DeriveKeyPair", mode);
-        for (size_t i = 0; i < n; i++) { S::item(kDeriveKeyPair, &a, i); if (!ok[i]) return fail(C::CURVE, "derive_keypair refused an item"); }
+        for (size_t i = 0; i < n; i++) { S::item(oprf::kDeriveKeyPair, &a, i); if (!ok[i]) return fail(C::CURVE, "derive_keypair refused an item"); }
         // blinds: any non-zero canonical scalars; the keys serve
         for (size_t i = 0; i < n; i++) memcpy(blinds.b + NS * i, sk.b + NS * ((i + 1) % n), NS);
         a.blob = in.blob; a.off = in.off.data(); a.scalars = blinds.w(); a.scalar_stride = N; a.out = blinded.b; a.out2 = nullptr;
         set_dst(a, "HashToGroup-", mode);
-        for (size_t i = 0; i < n; i++) { S::item(kBlind, &a, i); if (!ok[i]) return fail(C::CURVE, "blind refused an item"); }
+        for (size_t i = 0; i < n; i++) { S::item(oprf::kBlind, &a, i); if (!ok[i]) return fail(C::CURVE, "blind refused an item"); }
         // evaluate under the shared key sk[0], finalize, and the same in one step
         a.blob = nullptr; a.off = nullptr; a.scalars = sk.w(); a.scalar_stride = 0; a.elems = blinded.b; a.out = evaluated.b;
-        for (size_t i = 0; i < n; i++) { S::item(kEvaluate, &a, i); if (!ok[i]) return fail(C::CURVE, "evaluate refused an item"); }
+        for (size_t i = 0; i < n; i++) { S::item(oprf::kEvaluate, &a, i); if (!ok[i]) return fail(C::CURVE, "evaluate refused an item"); }
         a.blob = in.blob; a.off = in.off.data(); a.scalars = blinds.w(); a.scalar_stride = N; a.elems = evaluated.b; a.out = out.b;
-        for (size_t i = 0; i < n; i++) { S::item(kFinalize, &a, i); if (!ok[i]) return fail(C::CURVE, "finalize refused an item"); }
+        for (size_t i = 0; i < n; i++) { S::item(oprf::kFinalize, &a, i); if (!ok[i]) return fail(C::CURVE, "finalize refused an item"); }
         a.scalars = sk.w(); a.scalar_stride = 0; a.elems = nullptr; a.out = full.b;
-        for (size_t i = 0; i < n; i++) { S::item(kFullEvaluate, &a, i); if (!ok[i]) return fail(C::CURVE, "full_evaluate refused an item"); }
+        for (size_t i = 0; i < n; i++) { S::item(oprf::kFullEvaluate, &a, i); if (!ok[i]) return fail(C::CURVE, "full_evaluate refused an item"); }
         if (memcmp(out.b, full.b, NH * n)) return fail(C::CURVE, "finalize(evaluate(blind(x))) != full_evaluate(x)");
         // scalar_mult by the inverse undoes a blinding: blind^-1 (blind P) = P = hash_to_group(x)
         a.blob = nullptr; a.off = nullptr; a.scalars = blinds.w(); a.scalar_stride = N; a.elems = blinded.b; a.out = unblinded.b; a.flags = 1;
-        for (size_t i = 0; i < n; i++) { S::item(kScalarMult, &a, i); if (!ok[i]) return fail(C::CURVE, "scalar_mult refused an item"); }
+        for (size_t i = 0; i < n; i++) { S::item(oprf::kScalarMult, &a, i); if (!ok[i]) return fail(C::CURVE, "scalar_mult refused an item"); }
         a.flags = 0; a.blob = in.blob; a.off = in.off.data(); a.out = evaluated.b;
-        for (size_t i = 0; i < n; i++) S::item(kHashToGroup, &a, i);
+        for (size_t i = 0; i < n; i++) S::item(oprf::kHashToGroup, &a, i);
         if (memcmp(unblinded.b, evaluated.b, NE * n)) return fail(C::CURVE, "blind^-1 (blind P) != P");
         a.flags = 1;
-        for (size_t i = 0; i < n; i++) S::item(kHashToGroup, &a, i);
+        for (size_t i = 0; i < n; i++) S::item(oprf::kHashToGroup, &a, i);
         a.flags = 0; a.out = sk.b;
-        for (size_t i = 0; i < n; i++) S::item(kHashToScalar, &a, i);
+        for (size_t i = 0; i < n; i++) S::item(oprf::kHashToScalar, &a, i);
         // failure masks: a zero blind, an element that does not decode
         memset(blinds.b, 0, NS);
         blinded.b[NE] = 4;
         a.scalars = blinds.w(); a.scalar_stride = N; a.out = unblinded.b;
-        S::item(kBlind, &a, 0);
+        S::item(oprf::kBlind, &a, 0);
         a.scalars = sk.w(); a.scalar_stride = 0; a.elems = blinded.b;
-        S::item(kEvaluate, &a, 1);
+        S::item(oprf::kEvaluate, &a, 1);
         for (size_t j = 0; j < 2 * NE; j++)
             if (unblinded.b[j]) return fail(C::CURVE, "a failed item's row is not zero");
         if (ok[0] || ok[1]) return fail(C::CURVE, "a bad blind or element passed");

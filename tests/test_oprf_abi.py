@@ -132,6 +132,10 @@ def test_misaligned_device_pointers(L):
     assert call(L, "oprf_evaluate", "_dev", blinded=odd) == nat.EWORKSPACE
     assert call(L, "oprf_finalize", "_dev", off=odd4) == nat.EWORKSPACE
     assert call(L, "oprf_full_evaluate", "_dev", sk=odd) == nat.EWORKSPACE
+    # element rows are read and written as words in this group
+    assert call(L, "ristretto255_scalar_mult", "_dev", elems=odd) == nat.EWORKSPACE
+    assert call(L, "oprf_blind", "_dev", out=odd) == nat.EWORKSPACE
+    assert call(L, "oprf_finalize", "_dev", evaluated=odd) == nat.EWORKSPACE
 
 
 def test_no_gpu_means_loud_failure():

@@ -1,4 +1,4 @@
-"""CPU-side checks of the ristretto255 / OPRF device source: ristretto255_dev.h and the item functions of oprf_kernels.h compiled for the
+"""CPU-side checks of the ristretto255 / OPRF device source: ristretto255_dev.h and the item functions of oprf_group_kernels.h compiled for the
 host (tests/hostsim/oprf_hostsim.hip) against the checker tests/oprf.py and the fixture, and the same source as a stand-alone program
 under AddressSanitizer / UBSan."""
 import ctypes as C
@@ -16,13 +16,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 G = load_golden("oprf_ristretto255.json.gz")
 SRC = os.path.join(ROOT, "tests", "hostsim", "oprf_hostsim.hip")
 vp, u64, u32 = C.c_void_p, C.c_uint64, C.c_uint32
-H2G, H2S, MULT, DERIVE, BLIND, EVALUATE, FINALIZE, FULL = range(8)      # oprf_kernels.h Op
+H2G, H2S, MULT, DERIVE, BLIND, EVALUATE, FINALIZE, FULL = range(8)      # oprf_group_kernels.h Op
 P, L = oprf.P, oprf.L
 
 
-class Args(C.Structure):  # oprf_kernels.h Args
-    _fields_ = [("blob", vp), ("off", vp), ("scalars", vp), ("scalar_stride", C.c_size_t), ("elems", vp), ("out", vp), ("out2", vp), ("ok", vp),
-                ("flags", u32), ("dst_len", u32), ("n", C.c_size_t), ("dst", C.c_uint8 * 256)]
+class Args(C.Structure):  # oprf_group_kernels.h Args
+    _fields_ = [("blob", vp), ("off", vp), ("scalars", vp), ("scalar_stride", C.c_size_t), ("elems", vp), ("seeds", vp), ("out", vp), ("out2", vp),
+                ("ok", vp), ("flags", u32), ("dst_len", u32), ("n", C.c_size_t), ("dst", C.c_uint8 * 256)]
 
 
 def _stale(out):
@@ -160,7 +160,7 @@ def test_constant_time_multiplication(hs):
 
 
 # ---- the item functions ---------------------------------------------------------------------------------------------------------
-def run_item(hs, op, inp=None, scalar=None, elem=None, dst=b"", flags=0, out_bytes=32, two=False):
+def run_item(hs, op, inp=None, scalar=None, elem=None, seed=None, dst=b"", flags=0, out_bytes=32, two=False):
     """one item through item<op> at index 1 of a batch of 3: (out[, out2], ok); the rows of the neighbours must stay untouched"""
     a = Args()
     keep = []
@@ -178,6 +178,8 @@ def run_item(hs, op, inp=None, scalar=None, elem=None, dst=b"", flags=0, out_byt
         a.scalars, a.scalar_stride = rows(scalar), 8
     if elem is not None:
         a.elems = rows(elem)
+    if seed is not None:
+        a.seeds = rows(seed)
     out, out2, ok = (np.full(3 * out_bytes // 4, 0xA5A5A5A5, np.uint32) for _ in range(3))
     ok = np.full(3, 7, np.uint8)
     a.out, a.out2, a.ok, a.flags, a.dst_len, a.n = _p(out), _p(out2) if two else None, _p(ok), flags, len(dst), 3
@@ -211,7 +213,7 @@ class Sim:
         return run_item(self.hs, MULT, scalar=scalar, elem=elem, flags=flags)
 
     def derive_keypair(self, mode, seed, info):
-        return run_item(self.hs, DERIVE, inp=info, elem=seed, dst=dst_of(b"DeriveKeyPair", mode), two=True)
+        return run_item(self.hs, DERIVE, inp=info, seed=seed, dst=dst_of(b"DeriveKeyPair", mode), two=True)
 
     def blind(self, mode, inp, bl):
         return run_item(self.hs, BLIND, inp=inp, scalar=bl, dst=dst_of(b"HashToGroup-", mode))

@@ -151,6 +151,7 @@ def test_misaligned_device_pointers(L, curve):
         assert call(L, "nistp_hash_to_group", "_dev", curve, out=odd) == nat.ENODEV
         assert call(L, "nistp_scalar_mult", "_dev", curve, elems=odd, out=odd) == nat.ENODEV
         assert call(L, "oprf_nistp_derive_keypair", "_dev", curve, pk=odd) == nat.ENODEV
+        assert call(L, "oprf_nistp_blind", "_dev", curve, out=odd) == nat.ENODEV
         assert call(L, "oprf_nistp_evaluate", "_dev", curve, blinded=odd, out=odd) == nat.ENODEV
         assert call(L, "oprf_nistp_finalize", "_dev", curve, evaluated=odd) == nat.ENODEV
 

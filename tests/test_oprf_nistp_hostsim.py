@@ -1,4 +1,4 @@
-"""CPU-side checks of the P-256 / P-384 device source: nistp_dev.h and the item functions of nistp_kernels.h compiled for the host
+"""CPU-side checks of the P-256 / P-384 device source: nistp_dev.h and the item functions of oprf_group_kernels.h compiled for the host
 (tests/hostsim/oprf_nistp_hostsim.hip) against the checker tests/oprf_nistp.py and the fixture, and the same source as a stand-alone
 program under AddressSanitizer / UBSan."""
 import ctypes as C
@@ -16,11 +16,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 G = load_golden("oprf_nistp.json.gz")
 SRC = os.path.join(ROOT, "tests", "hostsim", "oprf_nistp_hostsim.hip")
 vp, u64, u32, ci = C.c_void_p, C.c_uint64, C.c_uint32, C.c_int
-H2G, H2S, MULT, DERIVE, BLIND, EVALUATE, FINALIZE, FULL = range(8)      # nistp_kernels.h Op
+H2G, H2S, MULT, DERIVE, BLIND, EVALUATE, FINALIZE, FULL = range(8)      # oprf_group_kernels.h Op
 CURVES = (256, 384)
 
 
-class Args(C.Structure):  # nistp_kernels.h Args
+class Args(C.Structure):  # oprf_group_kernels.h Args
     _fields_ = [("blob", vp), ("off", vp), ("scalars", vp), ("scalar_stride", C.c_size_t), ("elems", vp), ("seeds", vp), ("out", vp), ("out2", vp),
                 ("ok", vp), ("flags", u32), ("dst_len", u32), ("n", C.c_size_t), ("dst", C.c_uint8 * 256)]
 
