@@ -66,8 +66,10 @@ SYMBOLS = [
                   for d in ("", "_dev")] + ["circl_hip_dleq_workspace_size", "circl_hip_ascon_key_size"] + [
     f + d for f in ("circl_hip_ascon_seal", "circl_hip_ascon_open", "circl_hip_aesgcm_seal", "circl_hip_aesgcm_open") for d in ("", "_dev")] + [
     f + d for f in ("circl_hip_nistp_hash_to_group", "circl_hip_nistp_hash_to_scalar", "circl_hip_nistp_scalar_mult", "circl_hip_oprf_nistp_derive_keypair",
-                    "circl_hip_oprf_nistp_blind", "circl_hip_oprf_nistp_evaluate", "circl_hip_oprf_nistp_finalize", "circl_hip_oprf_nistp_full_evaluate")
-    for d in ("", "_dev")]
+                    "circl_hip_oprf_nistp_blind", "circl_hip_oprf_nistp_evaluate", "circl_hip_oprf_nistp_finalize", "circl_hip_oprf_nistp_full_evaluate",
+                    "circl_hip_nistp_dleq_prove", "circl_hip_nistp_dleq_verify", "circl_hip_oprf_nistp_poprf_tweak", "circl_hip_oprf_nistp_poprf_finalize",
+                    "circl_hip_oprf_nistp_poprf_full_evaluate")
+    for d in ("", "_dev")] + ["circl_hip_nistp_dleq_workspace_size"]
 
 OK, EPARAM, ENODEV, EHIP, ENOMEM, EWORKSPACE, EBUSY, EAGAIN = 0, -1, -2, -3, -4, -5, -6, -7
 ALL_DEVICES = -1
@@ -289,8 +291,15 @@ def lib():
         L.circl_hip_dleq_prove_dev.argtypes = [vp, sz] + dleq + [vp] + tail + [vp, vp, sz, sz, vp, sz, vp]
         L.circl_hip_dleq_verify.argtypes = dleq + [vp] + tail + [vp, sz, i]
         L.circl_hip_dleq_verify_dev.argtypes = dleq + [vp] + tail + [vp, sz, sz, vp, sz, vp]
+        L.circl_hip_nistp_dleq_workspace_size.restype, L.circl_hip_nistp_dleq_workspace_size.argtypes = sz, [i, sz, sz]
+        L.circl_hip_nistp_dleq_prove.argtypes = [i, vp, sz] + dleq + [vp] + tail + [vp, vp, sz, i]
+        L.circl_hip_nistp_dleq_prove_dev.argtypes = [i, vp, sz] + dleq + [vp] + tail + [vp, vp, sz, sz, vp, sz, vp]
+        L.circl_hip_nistp_dleq_verify.argtypes = [i] + dleq + [vp] + tail + [vp, sz, i]
+        L.circl_hip_nistp_dleq_verify_dev.argtypes = [i] + dleq + [vp] + tail + [vp, sz, sz, vp, sz, vp]
         for name, args in (("oprf_poprf_tweak", [vp, sz, vp, sz, vp, vp, vp, vp, vp, vp]), ("oprf_poprf_finalize", [vp] * 8),
-                           ("oprf_poprf_full_evaluate", [vp, sz] + [vp] * 6)):
+                           ("oprf_poprf_full_evaluate", [vp, sz] + [vp] * 6),
+                           ("oprf_nistp_poprf_tweak", [i, vp, sz, vp, sz, vp, vp, vp, vp, vp, vp]), ("oprf_nistp_poprf_finalize", [i] + [vp] * 8),
+                           ("oprf_nistp_poprf_full_evaluate", [i, vp, sz] + [vp] * 6)):
             getattr(L, "circl_hip_" + name).argtypes = args + [sz, i]
             getattr(L, "circl_hip_" + name + "_dev").argtypes = args + [sz, vp]
         L.circl_hip_ascon_key_size.restype, L.circl_hip_ascon_key_size.argtypes = sz, [i]

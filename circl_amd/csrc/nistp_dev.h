@@ -414,6 +414,27 @@ CIRCL_HD Pt<C> pt_select(const Pt<C> &a, const Pt<C> &b, bool take_b) {
 }
 template <class C>
 CIRCL_HD bool pt_is_identity(const Pt<C> &p) { return fe_is_zero(p.Z); }
+// a point as 3 N words, X || Y || Z: what a lane hands to another lane or to a workspace
+template <class C>
+CIRCL_HD void pt_store(uint32_t *w, const Pt<C> &p) {
+#pragma unroll
+    for (int i = 0; i < C::N; i++) {
+        w[i] = p.X.v[i];
+        w[C::N + i] = p.Y.v[i];
+        w[2 * C::N + i] = p.Z.v[i];
+    }
+}
+template <class C>
+CIRCL_HD Pt<C> pt_load(const uint32_t *w) {
+    Pt<C> p;
+#pragma unroll
+    for (int i = 0; i < C::N; i++) {
+        p.X.v[i] = w[i];
+        p.Y.v[i] = w[C::N + i];
+        p.Z.v[i] = w[2 * C::N + i];
+    }
+    return p;
+}
 
 // eprint 2015/1060 algorithm 4: the complete addition for a = -3, 12 products and 2 by b
 template <class C>

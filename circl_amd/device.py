@@ -563,25 +563,16 @@ class _OprfGroupDevice:
         self._call(self._oprf + "_full_evaluate_dev", mode, *self._scalars(sk, n), *_rag_args(inputs), _chk(out), _chk(ok), n)
         return out, ok
 
+    # ---- batch DLEQ proofs and the verifiable modes (circl_hip_[nistp_]dleq_*_dev, circl_hip_oprf_[nistp_]poprf_*_dev) ----
+    # _dleq_sym: the prefix of the proofs' symbols; _tail: the end of the context string; a proof is a row of 2 Ns bytes
+    def _ctx(self, mode):
+        return b"OPRFV1-" + bytes([mode]) + self._tail
 
-class OprfDevice(_OprfGroupDevice):
-    """ristretto255 and base-mode OPRF (suite ristretto255-SHA512) on resident tensors (circl_hip_ristretto255_*_dev, circl_hip_oprf_*_dev),
-    on torch's current stream.  Elements, scalars, keys and blinds are (n, 32) uint8 tensors, OPRF outputs (n, 64); ragged inputs are Ragged
-    objects (or None: every item empty).  A key or scalar of shape (32,) or (1, 32) is shared by the batch.  Failed items have ok = 0 and zero
-    rows."""
-    _group, _oprf, _lead, _nonuniform, Ns, Ne, Nh = "ristretto255", "oprf", (), False, 32, 32, 64
-
-    def __init__(self, device="cuda"):
-        self.device = device
-        self.L = nat.lib()
-
-    def hash_to_group(self, msgs, n, dst):
-        return super().hash_to_group(msgs, n, dst)
-
-    # ---- batch DLEQ proofs and the verifiable modes (circl_hip_dleq_*_dev, circl_hip_oprf_poprf_*_dev) ----
-    @staticmethod
-    def _ctx(mode):
-        return b"OPRFV1-" + bytes([mode]) + b"-ristretto255-SHA512"
+    def _elem_rows(self, t, n):
+        """(pointer, stride) of n element rows (public keys), or of one row shared by the batch"""
+        shared = t.numel() == self.Ne and n != 1
+        assert shared or t.shape == (n, self.Ne), (t.shape, n)
+        return _chk(t, self.Ne), 0 if shared else self.Ne
 
     def _requests(self, req_off):
         """(offsets on the device as an int64 tensor, n_req, n_elems, elements per request as a device tensor) of host offsets"""
@@ -594,20 +585,19 @@ class OprfDevice(_OprfGroupDevice):
         import numpy as np
         off_d, n, n_el, _ = self._requests(req_off)
         d = np.frombuffer(bytes(dst) + b"\0", np.uint8)
-        wsb = self.L.circl_hip_dleq_workspace_size(n, n_el)
+        wsb = getattr(self.L, "circl_hip_" + self._dleq_sym + "_workspace_size")(*self._lead, n, n_el)
         ws, ok = self._out(max(wsb, 256)), self._out(n)
         tail = (d.ctypes.data_as(C.c_void_p), len(dst), flags)
-        common = (*self._scalars(kA, n), _chk(B, 32), _chk(kB, 32), off_d.data_ptr())
+        common = (*self._elem_rows(kA, n), _chk(B, self.Ne), _chk(kB, self.Ne), off_d.data_ptr())
         if verify:
-            nat.check(self.L.circl_hip_dleq_verify_dev(*common, _chk(proofs, 64), *tail, _chk(ok), n, n_el, _chk(ws), wsb, _stream()), "dleq_verify_dev")
+            self._call(self._dleq_sym + "_verify_dev", *common, _chk(proofs, 2 * self.Ns), *tail, _chk(ok), n, n_el, _chk(ws), wsb)
             return ok
-        proofs = self._out(n, 64)
-        nat.check(self.L.circl_hip_dleq_prove_dev(*self._scalars(k, n), *common, _chk(r, 32), *tail, _chk(proofs), _chk(ok), n, n_el, _chk(ws), wsb,
-                                                  _stream()), "dleq_prove_dev")
+        proofs = self._out(n, 2 * self.Ns)
+        self._call(self._dleq_sym + "_prove_dev", *self._scalars(k, n), *common, _chk(r, self.Ns), *tail, _chk(proofs), _chk(ok), n, n_el, _chk(ws), wsb)
         return proofs, ok
 
     def dleq_prove(self, k, kA, B, kB, req_off, r, dst, flags=0):
-        """req_off: n_req + 1 HOST offsets in elements -> (proofs (n_req, 64), ok (n_req,))"""
+        """req_off: n_req + 1 HOST offsets in elements -> (proofs (n_req, 2 Ns), ok (n_req,))"""
         return self._dleq(False, k, kA, B, kB, req_off, r, None, dst, flags)
 
     def dleq_verify(self, kA, B, kB, req_off, proofs, dst, flags=0):
@@ -616,26 +606,22 @@ class OprfDevice(_OprfGroupDevice):
     def poprf_tweak(self, infos, n, sk=None, pkS=None):
         """with sk -> (t, t_inv, t G, ok); with pkS -> (tweaked key, ok)"""
         assert (sk is None) != (pkS is None)
-        t, tinv, tw, ok = self._out(n, 32), self._out(n, 32), self._out(n, 32), self._out(n)
+        t, tinv, tw, ok = self._out(n, self.Ns), self._out(n, self.Ns), self._out(n, self.Ne), self._out(n)
         if pkS is None:
-            nat.check(self.L.circl_hip_oprf_poprf_tweak_dev(*self._scalars(sk, n), None, 0, *_rag_args(infos), _chk(t), _chk(tinv), _chk(tw), _chk(ok), n,
-                                                            _stream()), "oprf_poprf_tweak_dev")
+            self._call(self._oprf + "_poprf_tweak_dev", *self._scalars(sk, n), None, 0, *_rag_args(infos), _chk(t), _chk(tinv), _chk(tw), _chk(ok), n)
             return t, tinv, tw, ok
-        nat.check(self.L.circl_hip_oprf_poprf_tweak_dev(None, 0, *self._scalars(pkS, n), *_rag_args(infos), None, None, _chk(tw), _chk(ok), n, _stream()),
-                  "oprf_poprf_tweak_dev")
+        self._call(self._oprf + "_poprf_tweak_dev", None, 0, *self._elem_rows(pkS, n), *_rag_args(infos), None, None, _chk(tw), _chk(ok), n)
         return tw, ok
 
     def poprf_finalize(self, inputs, infos, blinds, evaluated):
         n = blinds.shape[0]
-        out, ok = self._out(n, 64), self._out(n)
-        nat.check(self.L.circl_hip_oprf_poprf_finalize_dev(*_rag_args(inputs), *_rag_args(infos), _chk(blinds, 32), _chk(evaluated, 32), _chk(out), _chk(ok), n,
-                                                           _stream()), "oprf_poprf_finalize_dev")
+        out, ok = self._out(n, self.Nh), self._out(n)
+        self._call(self._oprf + "_poprf_finalize_dev", *_rag_args(inputs), *_rag_args(infos), _chk(blinds, self.Ns), _chk(evaluated, self.Ne), _chk(out), _chk(ok), n)
         return out, ok
 
     def poprf_full_evaluate(self, sk, inputs, infos, n):
-        out, ok = self._out(n, 64), self._out(n)
-        nat.check(self.L.circl_hip_oprf_poprf_full_evaluate_dev(*self._scalars(sk, n), *_rag_args(inputs), *_rag_args(infos), _chk(out), _chk(ok), n,
-                                                                _stream()), "oprf_poprf_full_evaluate_dev")
+        out, ok = self._out(n, self.Nh), self._out(n)
+        self._call(self._oprf + "_poprf_full_evaluate_dev", *self._scalars(sk, n), *_rag_args(inputs), *_rag_args(infos), _chk(out), _chk(ok), n)
         return out, ok
 
     def evaluate_verifiable(self, mode, sk, blinded, req_off, r, info=b""):
@@ -644,12 +630,12 @@ class OprfDevice(_OprfGroupDevice):
         assert mode in (1, 2)
         _, n, n_el, counts = self._requests(req_off)
         if mode == 1:
-            k = sk.reshape(1, 32)
+            k = sk.reshape(1, self.Ns)
             kA, key_ok = self.scalar_mult(k, n=1)
             evaluated, _ = self.evaluate(k, blinded)
             B, kB = blinded, evaluated
         else:
-            k, tinv, kA, key_ok = self.poprf_tweak(Ragged([info], self.device), 1, sk=sk.reshape(1, 32))
+            k, tinv, kA, key_ok = self.poprf_tweak(Ragged([info], self.device), 1, sk=sk.reshape(1, self.Ns))
             evaluated, _ = self.evaluate(tinv, blinded)
             B, kB = evaluated, blinded
         proofs, ok = self.dleq_prove(k, kA, B, kB, req_off, r, self._ctx(mode), 1)
@@ -658,22 +644,37 @@ class OprfDevice(_OprfGroupDevice):
         return evaluated * torch.repeat_interleave(ok, counts)[:, None], proofs, ok
 
     def finalize_verifiable(self, mode, pkS, inputs, blinds, blinded, evaluated, req_off, proofs, info=b""):
-        """The verifiable client's Finalize of modes 1 and 2 -> (outputs (n_elems, 64), ok per request); the outputs of EVERY element of a request
+        """The verifiable client's Finalize of modes 1 and 2 -> (outputs (n_elems, Nh), ok per request); the outputs of EVERY element of a request
         whose proof or any element failed are zero.  inputs: a Ragged of n_elems items."""
         assert mode in (1, 2)
         off_d, n, n_el, counts = self._requests(req_off)
-        shared = lambda t: t.reshape(1, 32)
+        shared = lambda t: t.reshape(1, self.Ne)
         if mode == 1:
             ok = self.dleq_verify(shared(pkS), blinded, evaluated, req_off, proofs, self._ctx(mode), 1)
             out, item_ok = self.finalize(inputs, blinds, evaluated)
         else:
-            tweaked, key_ok = self.poprf_tweak(Ragged([info], self.device), 1, pkS=pkS.reshape(1, 32))
+            tweaked, key_ok = self.poprf_tweak(Ragged([info], self.device), 1, pkS=pkS.reshape(1, self.Ne))
             ok = self.dleq_verify(shared(tweaked), evaluated, blinded, req_off, proofs, self._ctx(mode), 1) & key_ok[0]
             out, item_ok = self.poprf_finalize(inputs, Ragged([info] * n_el, self.device), blinds, evaluated)
         failed = torch.zeros(n, dtype=torch.int64, device=self.device)
         failed.index_add_(0, torch.repeat_interleave(torch.arange(n, device=self.device), counts), (item_ok == 0).to(torch.int64))
         ok = ok & (failed == 0).to(torch.uint8)
         return out * torch.repeat_interleave(ok, counts)[:, None], ok
+
+
+class OprfDevice(_OprfGroupDevice):
+    """ristretto255 and base-mode OPRF (suite ristretto255-SHA512) on resident tensors (circl_hip_ristretto255_*_dev, circl_hip_oprf_*_dev),
+    on torch's current stream.  Elements, scalars, keys and blinds are (n, 32) uint8 tensors, OPRF outputs (n, 64); ragged inputs are Ragged
+    objects (or None: every item empty).  A key or scalar of shape (32,) or (1, 32) is shared by the batch.  Failed items have ok = 0 and zero
+    rows."""
+    _group, _oprf, _dleq_sym, _lead, _nonuniform, Ns, Ne, Nh, _tail = "ristretto255", "oprf", "dleq", (), False, 32, 32, 64, b"-ristretto255-SHA512"
+
+    def __init__(self, device="cuda"):
+        self.device = device
+        self.L = nat.lib()
+
+    def hash_to_group(self, msgs, n, dst):
+        return super().hash_to_group(msgs, n, dst)
 
 
 class AsconCipherDevice:
@@ -755,7 +756,7 @@ class NistpOprfDevice(_OprfGroupDevice):
     big-endian rows (Ns = 32 / 48), elements (n, Ne) SEC 1 compressed rows (Ne = 33 / 49; the identity: the zero row), seeds (n, 32), OPRF
     outputs (n, Nh = Ns); ragged inputs are Ragged objects (or None: every item empty).  A key or scalar of shape (Ns,) or (1, Ns) is shared
     by the batch.  Failed items have ok = 0 and zero rows."""
-    _group, _oprf, _nonuniform = "nistp", "oprf_nistp", True
+    _group, _oprf, _dleq_sym, _nonuniform = "nistp", "oprf_nistp", "nistp_dleq", True
 
     def __init__(self, curve, device="cuda"):
         if curve not in (256, 384):
@@ -763,3 +764,4 @@ class NistpOprfDevice(_OprfGroupDevice):
         self.curve, self.device, self.L, self._lead = curve, device, nat.lib(), (curve,)
         self.Ns = curve // 8
         self.Ne, self.Nh = self.Ns + 1, self.Ns
+        self._tail = b"-P256-SHA256" if curve == 256 else b"-P384-SHA384"

@@ -1316,6 +1316,37 @@ class NistpOprf:
         """Server.FullEvaluate (mode 0) / VerifiableServer.FullEvaluate (mode 1) -> (outputs (n, Nh), ok (n,)); sk as in evaluate"""
         return self._s.full_evaluate(mode, sk, inputs, self.device)
 
+    # the DLEQ proofs and the verifiable modes (circl_hip_nistp_dleq_*, circl_hip_oprf_nistp_poprf_*): proofs are rows of 2 Ns bytes, c || s
+    def dleq_prove(self, k, kA, B, kB, req_off, r, dst, flags=0):
+        """ProveBatchWithRandomnessRFC9497 per request -> (proofs (n_req, 2 Ns), ok (n_req,)); the arguments of dleq_prove"""
+        return _DleqSuite(self._s).prove(k, kA, B, kB, req_off, r, dst, flags, self.device)
+
+    def dleq_verify(self, kA, B, kB, req_off, proofs, dst, flags=0):
+        """VerifyBatchRFC9497 per request -> ok (n_req,), the verdicts"""
+        return _DleqSuite(self._s).verify(kA, B, kB, req_off, proofs, dst, flags, self.device)
+
+    def poprf_tweak(self, infos, sk=None, pkS=None):
+        """mode 2.  With sk -> (t, t_inv, t G, ok); with pkS -> (tweaked key, ok).  One key or n rows."""
+        return _DleqSuite(self._s).poprf_tweak(infos, sk, pkS, self.device)
+
+    def poprf_finalize(self, inputs, infos, blinds, evaluated):
+        """PartialObliviousClient.Finalize without the proof -> (outputs (n, Nh), ok (n,))"""
+        return _DleqSuite(self._s).poprf_finalize(inputs, infos, blinds, evaluated, self.device)
+
+    def poprf_full_evaluate(self, sk, inputs, infos):
+        """PartialObliviousServer.FullEvaluate -> (outputs (n, Nh), ok (n,)); sk as in evaluate"""
+        return _DleqSuite(self._s).poprf_full_evaluate(sk, inputs, infos, self.device)
+
+    def evaluate_verifiable(self, mode, sk, blinded, req_off, r, info=b""):
+        """VerifiableServer.Evaluate (mode 1) / PartialObliviousServer.Evaluate (mode 2) under ONE key (and one info) ->
+        (evaluated (n_elems, Ne), proofs (n_req, 2 Ns), ok (n_req,)); as oprf_evaluate_verifiable"""
+        return _DleqSuite(self._s).evaluate_verifiable(mode, sk, blinded, req_off, r, info, self.device)
+
+    def finalize_verifiable(self, mode, pkS, inputs, blinds, blinded, evaluated, req_off, proofs, info=b""):
+        """VerifiableClient.Finalize (mode 1) / PartialObliviousClient.Finalize (mode 2) -> (outputs (n_elems, Nh), ok (n_req,)); the outputs
+        of every element of a request whose proof or any element failed are zero"""
+        return _DleqSuite(self._s).finalize_verifiable(mode, pkS, inputs, blinds, blinded, evaluated, req_off, proofs, info, self.device)
+
 
 # ---- batch DLEQ proofs (zk/dleq, the ...RFC9497 forms) and the verifiable modes of OPRF (VOPRF, POPRF) --------------------------------
 DLEQ_NO_IDENTITY = 1
@@ -1332,71 +1363,11 @@ def _req_off(req_off):
     return off, len(off) - 1
 
 
-def _elems(x, off):
-    a = _u8(x, 32) if len(x) else np.zeros((0, 32), np.uint8)
+def _elems(x, off, width=32):
+    a = _u8(x, width) if len(x) else np.zeros((0, width), np.uint8)
     if len(a) != int(off[-1]):
         raise ValueError("%d element rows, the offsets end at %d" % (len(a), int(off[-1])))
-    return a if len(a) else np.zeros((1, 32), np.uint8)      # (an address even for a call of empty requests)
-
-
-def dleq_prove(k, kA, B, kB, req_off, r, dst, flags=0, device=0):
-    """ProveBatchWithRandomnessRFC9497 per request -> (proofs (n_req, 64), ok (n_req,)).  Request g owns element rows req_off[g] .. req_off[g+1]
-    of B and kB; k and kA: one row for the call or n_req rows; r: n_req rows drawn by the caller; dst: the caller's tag (0 .. 242 bytes)."""
-    off, n = _req_off(req_off)
-    (key, ks), (pub, ps), r, B, kB = _scalar_rows(k, n), _scalar_rows(kA, n), _u8(r, 32), _elems(B, off), _elems(kB, off)
-    if len(r) != n:
-        raise ValueError("dleq_prove: %d requests, %d rows of randomness" % (n, len(r)))
-    d, proofs, ok = np.frombuffer(bytes(dst) + b"\0", np.uint8), np.empty((n, 64), np.uint8), np.empty(n, np.uint8)
-    nat.check(nat.lib().circl_hip_dleq_prove(_p(key), ks, _p(pub), ps, _p(B), _p(kB), _p(off), _p(r), _p(d), len(dst), flags, _p(proofs), _p(ok), n, device),
-              "dleq_prove")
-    return proofs, ok
-
-
-def dleq_verify(kA, B, kB, req_off, proofs, dst, flags=0, device=0):
-    """VerifyBatchRFC9497 per request -> ok (n_req,), the verdicts"""
-    off, n = _req_off(req_off)
-    (pub, ps), proofs, B, kB = _scalar_rows(kA, n), _u8(proofs, 64), _elems(B, off), _elems(kB, off)
-    if len(proofs) != n:
-        raise ValueError("dleq_verify: %d requests, %d proofs" % (n, len(proofs)))
-    d, ok = np.frombuffer(bytes(dst) + b"\0", np.uint8), np.empty(n, np.uint8)
-    nat.check(nat.lib().circl_hip_dleq_verify(_p(pub), ps, _p(B), _p(kB), _p(off), _p(proofs), _p(d), len(dst), flags, _p(ok), n, device), "dleq_verify")
-    return ok
-
-
-def oprf_poprf_tweak(infos, sk=None, pkS=None, device=0):
-    """mode 2.  With sk (secretFromInfo) -> (t, t_inv, t G, ok); with pkS (pointFromInfo) -> (tweaked key, ok).  One key or n rows."""
-    n = len(infos)
-    if (sk is None) == (pkS is None):
-        raise ValueError("oprf_poprf_tweak: give sk or pkS")
-    (ib, io), ok = _blob(infos), np.empty(n, np.uint8)
-    key, stride = _scalar_rows(sk if pkS is None else pkS, n)
-    t, tinv, tw = (np.empty((n, 32), np.uint8) for _ in range(3))
-    if pkS is None:
-        nat.check(nat.lib().circl_hip_oprf_poprf_tweak(_p(key), stride, None, 0, _p(ib), _p(io), _p(t), _p(tinv), _p(tw), _p(ok), n, device), "oprf_poprf_tweak")
-        return t, tinv, tw, ok
-    nat.check(nat.lib().circl_hip_oprf_poprf_tweak(None, 0, _p(key), stride, _p(ib), _p(io), None, None, _p(tw), _p(ok), n, device), "oprf_poprf_tweak")
-    return tw, ok
-
-
-def oprf_poprf_finalize(inputs, infos, blinds, evaluated, device=0):
-    """PartialObliviousClient.Finalize without the proof -> (outputs (n, 64), ok (n,))"""
-    blinds, evaluated = _u8(blinds, 32), _u8(evaluated, 32)
-    n = len(blinds)
-    if len(evaluated) != n:
-        raise ValueError("oprf_poprf_finalize: %d blinds, %d evaluated elements" % (n, len(evaluated)))
-    (ib, io), (fb, fo), out, ok = _rag(inputs, n), _rag(infos, n), np.empty((n, 64), np.uint8), np.empty(n, np.uint8)
-    nat.check(nat.lib().circl_hip_oprf_poprf_finalize(_po(ib), _po(io), _po(fb), _po(fo), _p(blinds), _p(evaluated), _p(out), _p(ok), n, device),
-              "oprf_poprf_finalize")
-    return out, ok
-
-
-def oprf_poprf_full_evaluate(sk, inputs, infos, device=0):
-    """PartialObliviousServer.FullEvaluate -> (outputs (n, 64), ok (n,)); sk as in oprf_evaluate"""
-    n = len(inputs)
-    (key, stride), (ib, io), (fb, fo), out, ok = _scalar_rows(sk, n), _blob(inputs), _rag(infos, n), np.empty((n, 64), np.uint8), np.empty(n, np.uint8)
-    nat.check(nat.lib().circl_hip_oprf_poprf_full_evaluate(_p(key), stride, _p(ib), _p(io), _po(fb), _po(fo), _p(out), _p(ok), n, device),
-              "oprf_poprf_full_evaluate")
-    return out, ok
+    return a if len(a) else np.zeros((1, width), np.uint8)      # (an address even for a call of empty requests)
 
 
 def _per_element(off, rows):
@@ -1404,54 +1375,155 @@ def _per_element(off, rows):
     return np.repeat(rows, np.diff(off.astype(np.int64)), axis=0)
 
 
+class _DleqSuite:
+    """The DLEQ proofs, the mode-2 (POPRF) items and the verifiable modes of OPRF for one suite of the C ABI, written once over an
+    _OprfSuite.  The dleq_* / oprf_poprf_* / oprf_*_verifiable functions below and the methods of NistpOprf bind it."""
+
+    def __init__(self, suite):
+        self.s = suite
+        self.dleq = "dleq" if suite.group == "ristretto255" else suite.group + "_dleq"       # the prefixes of the symbols
+
+    def prove(self, k, kA, B, kB, req_off, r, dst, flags, device):
+        s, name = self.s, self.dleq + "_prove"
+        off, n = _req_off(req_off)
+        (key, ks), (pub, ps), r = _scalar_rows(k, n, s.Ns), _scalar_rows(kA, n, s.Ne), _u8(r, s.Ns)
+        B, kB = _elems(B, off, s.Ne), _elems(kB, off, s.Ne)
+        if len(r) != n:
+            raise ValueError("%s: %d requests, %d rows of randomness" % (name, n, len(r)))
+        d, proofs, ok = np.frombuffer(bytes(dst) + b"\0", np.uint8), np.empty((n, 2 * s.Ns), np.uint8), np.empty(n, np.uint8)
+        s._call(name, _p(key), ks, _p(pub), ps, _p(B), _p(kB), _p(off), _p(r), _p(d), len(dst), flags, _p(proofs), _p(ok), n, device)
+        return proofs, ok
+
+    def verify(self, kA, B, kB, req_off, proofs, dst, flags, device):
+        s, name = self.s, self.dleq + "_verify"
+        off, n = _req_off(req_off)
+        (pub, ps), proofs, B, kB = _scalar_rows(kA, n, s.Ne), _u8(proofs, 2 * s.Ns), _elems(B, off, s.Ne), _elems(kB, off, s.Ne)
+        if len(proofs) != n:
+            raise ValueError("%s: %d requests, %d proofs" % (name, n, len(proofs)))
+        d, ok = np.frombuffer(bytes(dst) + b"\0", np.uint8), np.empty(n, np.uint8)
+        s._call(name, _p(pub), ps, _p(B), _p(kB), _p(off), _p(proofs), _p(d), len(dst), flags, _p(ok), n, device)
+        return ok
+
+    def poprf_tweak(self, infos, sk, pkS, device):
+        s, name = self.s, self.s.oprf + "_poprf_tweak"
+        n = len(infos)
+        if (sk is None) == (pkS is None):
+            raise ValueError("%s: give sk or pkS" % name)
+        (ib, io), ok = _blob(infos), np.empty(n, np.uint8)
+        key, stride = _scalar_rows(sk, n, s.Ns) if pkS is None else _scalar_rows(pkS, n, s.Ne)
+        t, tinv, tw = np.empty((n, s.Ns), np.uint8), np.empty((n, s.Ns), np.uint8), np.empty((n, s.Ne), np.uint8)
+        if pkS is None:
+            s._call(name, _p(key), stride, None, 0, _p(ib), _p(io), _p(t), _p(tinv), _p(tw), _p(ok), n, device)
+            return t, tinv, tw, ok
+        s._call(name, None, 0, _p(key), stride, _p(ib), _p(io), None, None, _p(tw), _p(ok), n, device)
+        return tw, ok
+
+    def poprf_finalize(self, inputs, infos, blinds, evaluated, device):
+        s, name = self.s, self.s.oprf + "_poprf_finalize"
+        blinds, evaluated = _u8(blinds, s.Ns), _u8(evaluated, s.Ne)
+        n = len(blinds)
+        if len(evaluated) != n:
+            raise ValueError("%s: %d blinds, %d evaluated elements" % (name, n, len(evaluated)))
+        (ib, io), (fb, fo), out, ok = _rag(inputs, n), _rag(infos, n), np.empty((n, s.Nh), np.uint8), np.empty(n, np.uint8)
+        s._call(name, _po(ib), _po(io), _po(fb), _po(fo), _p(blinds), _p(evaluated), _p(out), _p(ok), n, device)
+        return out, ok
+
+    def poprf_full_evaluate(self, sk, inputs, infos, device):
+        s = self.s
+        n = len(inputs)
+        (key, stride), (ib, io), (fb, fo) = _scalar_rows(sk, n, s.Ns), _blob(inputs), _rag(infos, n)
+        out, ok = np.empty((n, s.Nh), np.uint8), np.empty(n, np.uint8)
+        s._call(s.oprf + "_poprf_full_evaluate", _p(key), stride, _p(ib), _p(io), _po(fb), _po(fo), _p(out), _p(ok), n, device)
+        return out, ok
+
+    def evaluate_verifiable(self, mode, sk, blinded, req_off, r, info, device):
+        s = self.s
+        if mode not in (OPRF_MODE_VOPRF, OPRF_MODE_POPRF):
+            raise ValueError("oprf_evaluate_verifiable: mode 1 or 2")
+        off, n = _req_off(req_off)
+        blinded = _elems(blinded, off, s.Ne)[:int(off[-1])]
+        if mode == OPRF_MODE_VOPRF:
+            k = _u8(sk, s.Ns)[:1]
+            kA, key_ok = s.scalar_mult(k, None, False, 1, device)
+            evaluated, _ = s.evaluate(k, blinded, device) if len(blinded) else (blinded, None)
+            B, kB = blinded, evaluated
+        else:
+            k, tinv, kA, key_ok = self.poprf_tweak([info], sk, None, device)
+            evaluated, _ = s.evaluate(tinv, blinded, device) if len(blinded) else (blinded, None)
+            B, kB = evaluated, blinded
+        proofs, ok = self.prove(k, kA, B, kB, off, r, s.context_string(mode), DLEQ_NO_IDENTITY, device)
+        ok &= key_ok[0]
+        proofs[ok == 0] = 0
+        evaluated = np.array(evaluated, copy=True)
+        evaluated[_per_element(off, ok) == 0] = 0
+        return evaluated, proofs, ok
+
+    def finalize_verifiable(self, mode, pkS, inputs, blinds, blinded, evaluated, req_off, proofs, info, device):
+        s = self.s
+        if mode not in (OPRF_MODE_VOPRF, OPRF_MODE_POPRF):
+            raise ValueError("oprf_finalize_verifiable: mode 1 or 2")
+        off, n = _req_off(req_off)
+        n_el = int(off[-1])
+        blinded, evaluated = _elems(blinded, off, s.Ne)[:n_el], _elems(evaluated, off, s.Ne)[:n_el]
+        blinds = _u8(blinds, s.Ns) if n_el else np.zeros((0, s.Ns), np.uint8)
+        if len(inputs) != n_el or len(blinds) != n_el:
+            raise ValueError("oprf_finalize_verifiable: %d elements, %d inputs, %d blinds" % (n_el, len(inputs), len(blinds)))
+        none = (np.zeros((0, s.Nh), np.uint8), np.zeros(0, np.uint8))
+        if mode == OPRF_MODE_VOPRF:
+            ok = self.verify(pkS, blinded, evaluated, off, proofs, s.context_string(mode), DLEQ_NO_IDENTITY, device)
+            out, item_ok = s.finalize(inputs, blinds, evaluated, device) if n_el else none
+        else:
+            tweaked, key_ok = self.poprf_tweak([info], None, pkS, device)
+            ok = self.verify(tweaked, evaluated, blinded, off, proofs, s.context_string(mode), DLEQ_NO_IDENTITY, device) & key_ok[0]
+            out, item_ok = self.poprf_finalize(inputs, [info] * n_el, blinds, evaluated, device) if n_el else none
+        failed = np.zeros(n, np.int64)      # elements of each request that finalize refused
+        np.add.at(failed, _per_element(off, np.arange(n)), item_ok == 0)
+        ok = ok & (failed == 0).astype(np.uint8)
+        out = np.array(out, copy=True)
+        out[_per_element(off, ok) == 0] = 0
+        return out, ok
+
+
+_R255_DLEQ = _DleqSuite(_R255)
+
+
+def dleq_prove(k, kA, B, kB, req_off, r, dst, flags=0, device=0):
+    """ProveBatchWithRandomnessRFC9497 per request -> (proofs (n_req, 64), ok (n_req,)).  Request g owns element rows req_off[g] .. req_off[g+1]
+    of B and kB; k and kA: one row for the call or n_req rows; r: n_req rows drawn by the caller; dst: the caller's tag (0 .. 242 bytes)."""
+    return _R255_DLEQ.prove(k, kA, B, kB, req_off, r, dst, flags, device)
+
+
+def dleq_verify(kA, B, kB, req_off, proofs, dst, flags=0, device=0):
+    """VerifyBatchRFC9497 per request -> ok (n_req,), the verdicts"""
+    return _R255_DLEQ.verify(kA, B, kB, req_off, proofs, dst, flags, device)
+
+
+def oprf_poprf_tweak(infos, sk=None, pkS=None, device=0):
+    """mode 2.  With sk (secretFromInfo) -> (t, t_inv, t G, ok); with pkS (pointFromInfo) -> (tweaked key, ok).  One key or n rows."""
+    return _R255_DLEQ.poprf_tweak(infos, sk, pkS, device)
+
+
+def oprf_poprf_finalize(inputs, infos, blinds, evaluated, device=0):
+    """PartialObliviousClient.Finalize without the proof -> (outputs (n, 64), ok (n,))"""
+    return _R255_DLEQ.poprf_finalize(inputs, infos, blinds, evaluated, device)
+
+
+def oprf_poprf_full_evaluate(sk, inputs, infos, device=0):
+    """PartialObliviousServer.FullEvaluate -> (outputs (n, 64), ok (n,)); sk as in oprf_evaluate"""
+    return _R255_DLEQ.poprf_full_evaluate(sk, inputs, infos, device)
+
+
 def oprf_evaluate_verifiable(mode, sk, blinded, req_off, r, info=b"", device=0):
     """VerifiableServer.Evaluate (mode 1) / PartialObliviousServer.Evaluate (mode 2) for n_req requests under ONE key (and one info) ->
     (evaluated (n_elems, 32), proofs (n_req, 64), ok (n_req,)).  r: the proof randomness, one row per request, drawn by the caller.  A request
     with a failed element or proof has ok = 0, a zero proof row and zero evaluated rows."""
-    if mode not in (OPRF_MODE_VOPRF, OPRF_MODE_POPRF):
-        raise ValueError("oprf_evaluate_verifiable: mode 1 or 2")
-    off, n = _req_off(req_off)
-    blinded = _elems(blinded, off)[:int(off[-1])]
-    if mode == OPRF_MODE_VOPRF:
-        k = _u8(sk, 32)[:1]
-        kA, key_ok = ristretto255_scalar_mult(k, n=1, device=device)
-        evaluated, _ = oprf_evaluate(k, blinded, device) if len(blinded) else (blinded, None)
-        B, kB = blinded, evaluated
-    else:
-        k, tinv, kA, key_ok = oprf_poprf_tweak([info], sk=sk, device=device)
-        evaluated, _ = oprf_evaluate(tinv, blinded, device) if len(blinded) else (blinded, None)
-        B, kB = evaluated, blinded
-    proofs, ok = dleq_prove(k, kA, B, kB, off, r, oprf_context_string(mode), DLEQ_NO_IDENTITY, device)
-    ok &= key_ok[0]
-    proofs[ok == 0] = 0
-    evaluated = np.array(evaluated, copy=True)
-    evaluated[_per_element(off, ok) == 0] = 0
-    return evaluated, proofs, ok
+    return _R255_DLEQ.evaluate_verifiable(mode, sk, blinded, req_off, r, info, device)
 
 
 def oprf_finalize_verifiable(mode, pkS, inputs, blinds, blinded, evaluated, req_off, proofs, info=b"", device=0):
     """VerifiableClient.Finalize (mode 1) / PartialObliviousClient.Finalize (mode 2) -> (outputs (n_elems, 64), ok (n_req,)).  The outputs of
     EVERY element of a request whose proof or any element failed are zero."""
-    if mode not in (OPRF_MODE_VOPRF, OPRF_MODE_POPRF):
-        raise ValueError("oprf_finalize_verifiable: mode 1 or 2")
-    off, n = _req_off(req_off)
-    n_el = int(off[-1])
-    blinded, evaluated, blinds = _elems(blinded, off)[:n_el], _elems(evaluated, off)[:n_el], _u8(blinds, 32) if n_el else np.zeros((0, 32), np.uint8)
-    if len(inputs) != n_el or len(blinds) != n_el:
-        raise ValueError("oprf_finalize_verifiable: %d elements, %d inputs, %d blinds" % (n_el, len(inputs), len(blinds)))
-    if mode == OPRF_MODE_VOPRF:
-        ok = dleq_verify(pkS, blinded, evaluated, off, proofs, oprf_context_string(mode), DLEQ_NO_IDENTITY, device)
-        out, item_ok = oprf_finalize(inputs, blinds, evaluated, device) if n_el else (np.zeros((0, 64), np.uint8), np.zeros(0, np.uint8))
-    else:
-        tweaked, key_ok = oprf_poprf_tweak([info], pkS=pkS, device=device)
-        ok = dleq_verify(tweaked, evaluated, blinded, off, proofs, oprf_context_string(mode), DLEQ_NO_IDENTITY, device) & key_ok[0]
-        out, item_ok = oprf_poprf_finalize(inputs, [info] * n_el, blinds, evaluated, device) if n_el else (np.zeros((0, 64), np.uint8), np.zeros(0, np.uint8))
-    failed = np.zeros(n, np.int64)      # elements of each request that finalize refused
-    np.add.at(failed, _per_element(off, np.arange(n)), item_ok == 0)
-    ok = ok & (failed == 0).astype(np.uint8)
-    out = np.array(out, copy=True)
-    out[_per_element(off, ok) == 0] = 0
-    return out, ok
+    return _R255_DLEQ.finalize_verifiable(mode, pkS, inputs, blinds, blinded, evaluated, req_off, proofs, info, device)
 
 
 # ---- Ascon AEAD: Ascon128, Ascon128a, Ascon80pq (cipher/ascon/ascon.go) ----

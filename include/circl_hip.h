@@ -983,7 +983,8 @@ int circl_hip_oprf_full_evaluate_dev(int mode, const uint8_t *sk, size_t sk_stri
  *                    "OPRFV1-" || mode || "-P256-SHA256" / "-P384-SHA384", I2OSP(Ne, 2) in the Finalize hash, modes 0, 1, 2 (full_evaluate:
  *                    0, 1; 2 is CIRCL_HIP_EPARAM).  full_evaluate keeps the hashed point and the evaluated element out of memory.
  * The _dev forms want 4-byte aligned scalar, seed, sk and output rows and 8-byte aligned offsets (CIRCL_HIP_EWORKSPACE otherwise);
- * element rows may lie anywhere.  OUT OF SCOPE: P-521, the DLEQ proofs (VOPRF / POPRF proofs) on these curves, the Go bridge. */
+ * element rows may lie anywhere.  The DLEQ proofs and the mode-2 (POPRF) items on these curves are the circl_hip_nistp_dleq_* /
+ * circl_hip_oprf_nistp_poprf_* block further down.  OUT OF SCOPE: P-521, the Go bridge. */
 #define CIRCL_HIP_P256 256
 #define CIRCL_HIP_P384 384
 #define CIRCL_HIP_NISTP_NONUNIFORM 1u /* hash_to_group flags */
@@ -1044,7 +1045,8 @@ int circl_hip_oprf_nistp_full_evaluate_dev(int curve, int mode, const uint8_t *s
  * rows, 8-byte aligned offsets and workspace), n_elems = req_off[n_req] - req_off[0] given explicitly, and a workspace of at least
  * dleq_workspace_size(n_req, n_elems) bytes (monotone in both; about 5 bytes per element plus 320 per request; nothing secret is
  * ever written to it), else CIRCL_HIP_EWORKSPACE.  k and r are wiped from the host forms' staging.
- * OUT OF SCOPE: the bound-base Prove / VerifyBatch forms with a caller's base A; every group other than ristretto255; the Go bridge.
+ * OUT OF SCOPE: the bound-base Prove / VerifyBatch forms with a caller's base A; P-521 (P-256 and P-384 are the block after this one);
+ * the Go bridge.
  *   poprf_tweak:          secretFromInfo / pointFromInfo, m_i = HashToScalar("Info" || I2(len) || info_i).  With sk (pkS NULL), the
  *                         server's side: t = sk + m, t_inv = t^-1, tweaked = t G; ok = 0 for t = 0 (ErrInverseZero) or sk zero or >= L.
  *                         With pkS (sk NULL; t and t_inv not written), the client's: tweaked = m G + pkS; ok = 0 if that is the identity
@@ -1077,6 +1079,55 @@ int circl_hip_oprf_poprf_finalize_dev(const uint8_t *input_blob, const uint64_t 
                                       const uint8_t *blinds, const uint8_t *evaluated, uint8_t *out, uint8_t *ok, size_t n, void *stream);
 int circl_hip_oprf_poprf_full_evaluate_dev(const uint8_t *sk, size_t sk_stride, const uint8_t *input_blob, const uint64_t *input_off, const uint8_t *info_blob,
                                            const uint64_t *info_off, uint8_t *out, uint8_t *ok, size_t n, void *stream);
+
+/* ---- batch DLEQ proofs and the mode-2 (POPRF) items on NIST P-256 / P-384 (zk/dleq with Params{G, H: SHA-256 / SHA-384, DST}; RFC 9497
+ * suites P256-SHA256 and P384-SHA384) ---------------------------------------------------------------------------------------------
+ * The ristretto255 DLEQ block above, on a curve chosen per call: curve = CIRCL_HIP_P256 or CIRCL_HIP_P384 comes first, anything else is
+ * CIRCL_HIP_EPARAM (nistp_dleq_workspace_size returns 0); the other arguments are those of the ristretto255 entry point of the same
+ * name.  Row shapes follow the NIST block, for P-256 / P-384:
+ *   k, r, t, t_inv, blinds   BIG-ENDIAN rows of Ns = 32 / 48 bytes; the k and sk strides are 0 (one key for the call) or Ns
+ *   kA, B, kB, pkS, tweaked  packed SEC 1 COMPRESSED rows of Ne = 33 / 49 bytes; the kA and pkS strides are 0 or Ne
+ *   proofs                   c || s, 2 Ns = 64 / 96 bytes, as Proof.MarshalBinary writes them
+ *   OPRF outputs             Nh = 32 / 48 bytes
+ * req_off counts ELEMENTS.  The transcript is the one above with the suite's hash, I2(Ne) in front of every element, I2(Nh) in front of
+ * the seed, and HashToScalar = expand_message_xmd to L = 48 / 72 bytes reduced mod n.  The mode-2 context string is "OPRFV1-" || 2 ||
+ * "-P256-SHA256" / "-P384-SHA384".
+ * THE CONTRACT CARRIES OVER UNCHANGED: it is checked before a device is looked for; dst is host bytes in both forms, 0 <= dst_len <=
+ * 242; the only flag bit is CIRCL_HIP_DLEQ_NO_IDENTITY; the host forms check that req_off starts at 0 and never decreases; the _dev
+ * forms want 4-byte aligned scalar and proof rows and 8-byte aligned offsets and workspace (element rows may lie anywhere), n_elems
+ * given explicitly and a workspace of nistp_dleq_workspace_size(curve, n_req, n_elems) bytes (CIRCL_HIP_EWORKSPACE otherwise; nothing
+ * secret is written to it); n_req == 0 is CIRCL_HIP_OK; failure is a mask (ok = 0 and zero rows, neighbours untouched); k, r, t, t_inv
+ * and the client's inputs are wiped from the host forms' staging.
+ * THE DELIBERATE DIFFERENCES FROM THE REFERENCE, as above and in the NIST block: a request of 0 or of more than 65535 pairs fails; k or r
+ * that is zero or >= n fails (the reference does not test r); verification fails with c or s >= n; only COMPRESSED encodings are accepted
+ * (decoding is strict: prefix 02 / 03, x < p, on the curve); the identity is the all-zero row.
+ * The launches are profiled under the ids of the ristretto255 launches of the same operation (37..41).
+ * OUT OF SCOPE: P-521; the bound-base Prove / VerifyBatch forms; the Go bridge.  circl_hip_oprf_nistp_full_evaluate keeps refusing
+ * mode 2: mode 2 is circl_hip_oprf_nistp_poprf_full_evaluate. */
+size_t circl_hip_nistp_dleq_workspace_size(int curve, size_t n_req, size_t n_elems);
+int circl_hip_nistp_dleq_prove(int curve, const uint8_t *k, size_t k_stride, const uint8_t *kA, size_t kA_stride, const uint8_t *B, const uint8_t *kB,
+                               const uint64_t *req_off, const uint8_t *r, const uint8_t *dst, size_t dst_len, uint32_t flags, uint8_t *proofs, uint8_t *ok,
+                               size_t n_req, int device);
+int circl_hip_nistp_dleq_verify(int curve, const uint8_t *kA, size_t kA_stride, const uint8_t *B, const uint8_t *kB, const uint64_t *req_off, const uint8_t *proofs,
+                                const uint8_t *dst, size_t dst_len, uint32_t flags, uint8_t *ok, size_t n_req, int device);
+int circl_hip_nistp_dleq_prove_dev(int curve, const uint8_t *k, size_t k_stride, const uint8_t *kA, size_t kA_stride, const uint8_t *B, const uint8_t *kB,
+                                   const uint64_t *req_off, const uint8_t *r, const uint8_t *dst, size_t dst_len, uint32_t flags, uint8_t *proofs, uint8_t *ok,
+                                   size_t n_req, size_t n_elems, void *d_workspace, size_t workspace_bytes, void *stream);
+int circl_hip_nistp_dleq_verify_dev(int curve, const uint8_t *kA, size_t kA_stride, const uint8_t *B, const uint8_t *kB, const uint64_t *req_off,
+                                    const uint8_t *proofs, const uint8_t *dst, size_t dst_len, uint32_t flags, uint8_t *ok, size_t n_req, size_t n_elems,
+                                    void *d_workspace, size_t workspace_bytes, void *stream);
+int circl_hip_oprf_nistp_poprf_tweak(int curve, const uint8_t *sk, size_t sk_stride, const uint8_t *pkS, size_t pk_stride, const uint8_t *info_blob,
+                                     const uint64_t *info_off, uint8_t *t, uint8_t *t_inv, uint8_t *tweaked, uint8_t *ok, size_t n, int device);
+int circl_hip_oprf_nistp_poprf_finalize(int curve, const uint8_t *input_blob, const uint64_t *input_off, const uint8_t *info_blob, const uint64_t *info_off,
+                                        const uint8_t *blinds, const uint8_t *evaluated, uint8_t *out, uint8_t *ok, size_t n, int device);
+int circl_hip_oprf_nistp_poprf_full_evaluate(int curve, const uint8_t *sk, size_t sk_stride, const uint8_t *input_blob, const uint64_t *input_off,
+                                             const uint8_t *info_blob, const uint64_t *info_off, uint8_t *out, uint8_t *ok, size_t n, int device);
+int circl_hip_oprf_nistp_poprf_tweak_dev(int curve, const uint8_t *sk, size_t sk_stride, const uint8_t *pkS, size_t pk_stride, const uint8_t *info_blob,
+                                         const uint64_t *info_off, uint8_t *t, uint8_t *t_inv, uint8_t *tweaked, uint8_t *ok, size_t n, void *stream);
+int circl_hip_oprf_nistp_poprf_finalize_dev(int curve, const uint8_t *input_blob, const uint64_t *input_off, const uint8_t *info_blob, const uint64_t *info_off,
+                                            const uint8_t *blinds, const uint8_t *evaluated, uint8_t *out, uint8_t *ok, size_t n, void *stream);
+int circl_hip_oprf_nistp_poprf_full_evaluate_dev(int curve, const uint8_t *sk, size_t sk_stride, const uint8_t *input_blob, const uint64_t *input_off,
+                                                 const uint8_t *info_blob, const uint64_t *info_off, uint8_t *out, uint8_t *ok, size_t n, void *stream);
 
 /* ---- Ascon AEAD: Ascon128, Ascon128a, Ascon80pq (cipher/ascon/ascon.go; Ascon v1.2) ------------------------------------------
  * mode = the reference's Mode values.  One item per lane, one launch per call, no workspace.  Every other mode is
@@ -1192,6 +1243,7 @@ int circl_hip_aesgcm_open_dev(int key_bytes, const uint8_t *key, size_t key_stri
 #define CIRCL_HIP_KERNEL_OPRF_EVALUATE 34        /* OPRF Evaluate (base mode)       */
 #define CIRCL_HIP_KERNEL_OPRF_FINALIZE 35        /* OPRF Finalize (base mode)       */
 #define CIRCL_HIP_KERNEL_OPRF_FULL_EVALUATE 36   /* OPRF FullEvaluate               */
+/* ids 37..41: the ristretto255 launches, and the circl_hip_nistp_dleq_* / circl_hip_oprf_nistp_poprf_* launches of the same operation */
 #define CIRCL_HIP_KERNEL_DLEQ_COMPOSITE 37        /* DLEQ: d_j B_j per element, segmented sums */
 #define CIRCL_HIP_KERNEL_DLEQ_FINISH 38           /* DLEQ: the prover's / verifier's tail per request */
 #define CIRCL_HIP_KERNEL_OPRF_POPRF_TWEAK 39      /* POPRF secretFromInfo / pointFromInfo */
