@@ -1,26 +1,28 @@
 // dleq_group_kernels.h -- batch DLEQ proofs (zk/dleq with Params{G, H, DST}, the ...RFC9497 forms: fixed generator, the base not bound;
 // RFC 9497 section 2.2) and the mode-2 (POPRF) item operations of oprf/client.go and oprf/server.go, written once over a group
-// description G of oprf_group_kernels.h.  Instantiated for P256 and P384 (api_dleq_nistp.hip).  ristretto255 still runs on
-// dleq_kernels.h, whose names and layouts tests pin; this header asks of a group only what Ops<G> below lists, so that ristretto255 can
-// move onto it by supplying Ops<oprf::R255>.
+// description G of oprf_group_kernels.h.  Instantiated for R255 (api_dleq.hip) and for P256 and P384 (api_dleq_nistp.hip); beyond that
+// description it asks of a group what Ops<G> below lists.
 //
-// The launch shape is that of dleq_kernels.h.  A proof belongs to a REQUEST: a ragged group of 1 .. 65535 element pairs (B_j, kB_j).
+// A proof belongs to a REQUEST: a ragged group of 1 .. 65535 element pairs (B_j, kB_j).  Two launches per call:
 //   composite<G, VERIFY>  one lane per ELEMENT.  The lane finds its request by an upper-bound search over the offsets (empty requests
 //                         are skipped), recomputes the request's seed, hashes d_j and multiplies: d_j B_j, and d_j kB_j when verifying.
-//                         Then a segmented reduction inside the wavefront: six __shfl_down steps over the PW = 3 N words of a point (24
-//                         for P-256, 36 for P-384) and the request index; a lane adds what it received only if the sender exists and is
-//                         of the same request.  The first lane of every request segment of the wave writes the segment's sum to
+//                         Then a segmented reduction inside the wavefront: six __shfl_down steps over the PW words of a point (40 for
+//                         ristretto255, 24 for P-256, 36 for P-384) and the request index; a lane adds what it received only if the
+//                         sender exists and is of the same request.  Requests are contiguous, so the first lane of every request
+//                         segment of the wave ends up with the segment's sum, and writes it to
 //                         workspace slot (wave + request): unique and increasing along the (wave, request) pairs, at most
 //                         ceil(n_elems / 64) + n_req slots.  Every lane reaches every shuffle: a lane beyond n_elems or with a failed
-//                         element carries the identity (Z = 0; the addition formulas are complete), and a failed element raises the
-//                         request's flag in the workspace.
+//                         element carries the identity (the addition formulas are complete), and a failed element raises the request's
+//                         flag in the workspace.
 //   finish<G, VERIFY>     one lane per REQUEST: adds the request's slots (contiguous, at most 1025) and runs the prover's or verifier's
 //                         tail.  kA is decoded here, once per request, not once per element.
 // d_j and the elements are public; the prover's k M, r M, r G and s = r - c k act on secrets and use the constant-time routines.  Nothing
-// secret reaches the workspace.  The hashes and the multiplication are functions of their own (noinline).
+// secret reaches the workspace.  The hashes and the tails' multiplications are functions of their own (noinline); the other
+// multiplications and the additions are too where Ops<G>::CALLS says so; k times the generator is the group's fixed-base routine where
+// it has one (base_mul).
 //
-// TWO DECISIONS that ristretto255's header did not have to take:
-//   element rows   are packed, unaligned rows of G::NE bytes (G::Row = uint8_t), read with G::elem_load; kA and pkS too.
+//   element rows   are addressed as the group addresses them (oprf::elem_rows<G>, G::ROW): words for ristretto255, packed unaligned
+//                  bytes for the NIST curves; kA and pkS too, and their strides are BYTES for every group.
 //   offsets        the host pipeline's blobs carry BYTE offsets, and 33 and 49 are no powers of two, so a shift cannot scale them.
 //                  Args::off_div is a DIVISOR: 1 where the offsets count elements (the _dev forms), G::NE where they count bytes (the
 //                  host pipeline's chunks).  The kernels compare it with those two values only, so the division is by a constant.
@@ -41,13 +43,61 @@ constexpr uint32_t kNoIdentity = 1u;     // flags bit 0
 constexpr int kTagHead = 13;             // "HashToScalar-"
 
 // What the proofs ask of a group beyond oprf_group_kernels.h's description: the group law on two public or secret points, a point as
-// words, and the scalar field's sum and r - c k.
+// words, the scalar field's sum and r - c k, and the suite's name as the group description spells it (G::ctx_tail()).
 template <class G>
 struct Ops;
+template <>
+struct Ops<oprf::R255> {
+    using Ge = ed25519::Ge;
+    using Scalar = oprf::R255::Scalar;
+    static constexpr int PW = 40;
+    static constexpr bool CALLS = false;
+    static CIRCL_HD Ge identity() { return ed25519::ge_identity(); }
+    static CIRCL_HD Ge add(const Ge &p, const Ge &q) { return r255::r255_add(p, q); }
+    static CIRCL_HD void store(uint32_t *w, const Ge &p) {
+#pragma unroll
+        for (int i = 0; i < 10; i++) {
+            w[i] = p.X.v[i];
+            w[10 + i] = p.Y.v[i];
+            w[20 + i] = p.Z.v[i];
+            w[30 + i] = p.T.v[i];
+        }
+    }
+    static CIRCL_HD Ge load(const uint32_t *w) {
+        Ge p;
+#pragma unroll
+        for (int i = 0; i < 10; i++) {
+            p.X.v[i] = w[i];
+            p.Y.v[i] = w[10 + i];
+            p.Z.v[i] = w[20 + i];
+            p.T.v[i] = w[30 + i];
+        }
+        return p;
+    }
+    static CIRCL_HD void sc_add(Scalar &out, const Scalar &a, const Scalar &b) {
+        const uint32_t one[8] = {1, 0, 0, 0, 0, 0, 0, 0};
+        ed25519::sc_muladd(out, a, one, b);
+    }
+    // r - c k mod L, for c below L: (L - c) k + r (c = 0 gives L, which the product reduces)
+    static CIRCL_HD void sc_sub_mul(Scalar &out, const Scalar &r, const Scalar &c, const Scalar &k) {
+        uint32_t nc[8];
+        uint64_t borrow = 0;
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+            const uint64_t t = (uint64_t)ed25519::order_word(i) - c[i] - borrow;
+            nc[i] = (uint32_t)t;
+            borrow = (t >> 32) & 1u;
+        }
+        ed25519::sc_muladd(out, nc, k, r);
+    }
+    static CIRCL_HD bool sc_equal(const Scalar &a, const Scalar &b) { return ed25519::words_equal(a, b); }
+    static CIRCL_HD const char *ctx_tail() { return oprf::R255::ctx_tail(); }
+};
 template <class C>
 struct Ops<oprf::Nistp<C>> {
     using G = oprf::Nistp<C>;
     static constexpr int PW = 3 * C::N;   // words of a point in a lane's hands and in the workspace
+    static constexpr bool CALLS = true;   // mul() and add() below
     static CIRCL_HD typename G::Point identity() { return nistp::pt_identity<C>(); }
     static CIRCL_HD typename G::Point add(const typename G::Point &p, const typename G::Point &q) { return nistp::pt_add<C>(p, q); }
     static CIRCL_HD void store(uint32_t *w, const typename G::Point &p) { nistp::pt_store<C>(w, p); }
@@ -58,16 +108,16 @@ struct Ops<oprf::Nistp<C>> {
         out = nistp::fe_sub<typename C::Fn>(r, nistp::sc_mul<C>(c, k));
     }
     static CIRCL_HD bool sc_equal(const typename G::Scalar &a, const typename G::Scalar &b) { return nistp::fe_equal(a, b); }
-    static CIRCL_HD const char *ctx_tail() { return C::CURVE == 256 ? "-P256-SHA256" : "-P384-SHA384"; }
+    static CIRCL_HD const char *ctx_tail() { return G::ctx_tail(); }
 };
 
 struct Args {
     const uint64_t *off;       // n_req + 1 offsets, in elements times off_div
     uint32_t off_div;          // 1, or G::NE (the host pipeline's byte offsets)
-    const uint8_t *B, *kB;     // rows of NE bytes, indexed by the ABSOLUTE element index off[g] / off_div
+    const uint8_t *B, *kB;     // element rows (oprf::elem_rows<G>), indexed by the ABSOLUTE element index off[g] / off_div
     const uint32_t *k;         // prove: rows of NS / 4 words, k_stride words apart (0: one key for the call)
     size_t k_stride;
-    const uint8_t *kA;         // rows of NE bytes, kA_stride BYTES apart (0: one key for the call)
+    const uint8_t *kA;         // element rows, kA_stride BYTES apart (0: one key for the call)
     size_t kA_stride;
     const uint32_t *r;         // prove: rows of NS / 4 words
     uint32_t *proofs;          // rows of NS / 2 words, c || s: prove writes them, verify reads them
@@ -166,6 +216,29 @@ template <class G, int WV>
 CIRCL_HKDF_STREAM_CALL(WV) void add_call(typename G::Point &out, const typename G::Point &p, const typename G::Point &q) {
     out = Ops<G>::add(p, q);
 }
+// k P and P + Q outside the tails, as Ops<G>::CALLS says: through the calls above (the NIST curves, whose kernels would not hold a second
+// copy of either), or in line (ristretto255: its composite multiplies once or twice and adds in the shuffle loop; as calls the points
+// cross by address and composite's scratch grows by 400 and 608 bytes per lane, profiles/dleq_fold_static.txt)
+template <class G>
+CIRCL_HD void mul(typename G::Point &out, const typename G::Scalar &k, const typename G::Point &p) {
+    if constexpr (Ops<G>::CALLS) mul_call<G, WAVES>(out, k, p);
+    else out = G::mul(k, p);
+}
+template <class G>
+CIRCL_HD void add(typename G::Point &out, const typename G::Point &p, const typename G::Point &q) {
+    if constexpr (Ops<G>::CALLS) add_call<G, WAVES>(out, p, q);
+    else out = Ops<G>::add(p, q);
+}
+// k times the generator: the group's fixed-base routine (FIXED_BASE: ristretto255's comb), or the one multiplication run on generator()
+template <class G>
+CIRCL_HD void base_mul(typename G::Point &out, const typename G::Scalar &k) {
+    if constexpr (G::FIXED_BASE) {
+        out = G::base(k);
+    } else {
+        const typename G::Point gen = G::generator();
+        mul_call<G, WAVES>(out, k, gen);
+    }
+}
 
 // The lane-local part of composite: m = d_j B_j and, when verifying, z = d_j kB_j for absolute element e of request g.  Returns 0
 // (and identities) where the request cannot be proven: more than 65535 pairs, an element that does not decode, an identity element
@@ -174,9 +247,9 @@ template <class G, bool VERIFY>
 CIRCL_HD uint32_t element(typename G::Point &m, typename G::Point &z, const Args &a, size_t g, uint64_t e) {
     const uint64_t first = elem_off<G>(a, g), cnt = elem_off<G>(a, g + 1) - first;
     uint32_t ka[G::EW], b[G::EW], kb[G::EW], seed[G::NH / 4], ib, ikb;
-    G::elem_load(ka, a.kA + g * a.kA_stride);
-    G::elem_load(b, a.B + (size_t)G::NE * e);
-    G::elem_load(kb, a.kB + (size_t)G::NE * e);
+    G::elem_load(ka, oprf::elem_rows<G>(a.kA + g * a.kA_stride));
+    G::elem_load(b, oprf::elem_rows<G>(a.B) + (size_t)G::ROW * e);
+    G::elem_load(kb, oprf::elem_rows<G>(a.kB) + (size_t)G::ROW * e);
     typename G::Point pb, pkb;
     uint32_t good = (cnt <= kMaxBatch ? 1u : 0u) & G::decode(pb, b, &ib) & G::decode(pkb, kb, &ikb);
     if (a.flags & kNoIdentity) good &= (ib | ikb) ^ 1u;
@@ -186,8 +259,8 @@ CIRCL_HD uint32_t element(typename G::Point &m, typename G::Point &z, const Args
     typename G::Scalar d;
     seed_hash<G, WAVES>(seed, ka, a.tag, a.tag_len);
     composite_scalar<G>(d, seed, (uint32_t)(e - first), b, kb, a.tag, a.tag_len);
-    mul_call<G, WAVES>(m, d, pb);
-    if (VERIFY) mul_call<G, WAVES>(z, d, pkb);
+    mul<G>(m, d, pb);
+    if (VERIFY) mul<G>(z, d, pkb);
     return 1;
 }
 
@@ -199,14 +272,13 @@ CIRCL_HD void prove_tail(const Args &a, size_t g, const typename G::Point &M, ui
     typename G::Scalar k, r, c, s;
     G::sc_load(k, a.k + g * a.k_stride);
     G::sc_load(r, a.r + (size_t)SW * g);
-    G::elem_load(rows, a.kA + g * a.kA_stride);
+    G::elem_load(rows, oprf::elem_rows<G>(a.kA + g * a.kA_stride));
     typename G::Point p;
     good &= oprf::secret_scalar_ok<G>(k) & oprf::secret_scalar_ok<G>(r) & G::decode(p, rows);
     mul_call<G, WAVES>(p, k, M);
     G::encode(rows + G::EW, M);
     G::encode(rows + 2 * G::EW, p);
-    const typename G::Point gen = G::generator();
-    mul_call<G, WAVES>(p, r, gen);
+    base_mul<G>(p, r);
     G::encode(rows + 3 * G::EW, p);
     mul_call<G, WAVES>(p, r, M);
     G::encode(rows + 4 * G::EW, p);
@@ -230,19 +302,18 @@ CIRCL_HD void verify_tail(const Args &a, size_t g, const typename G::Point &M, c
     typename G::Scalar c, s, c2;
     G::sc_load(c, a.proofs + (size_t)2 * SW * g);
     G::sc_load(s, a.proofs + (size_t)2 * SW * g + SW);
-    G::elem_load(rows, a.kA + g * a.kA_stride);
+    G::elem_load(rows, oprf::elem_rows<G>(a.kA + g * a.kA_stride));
     typename G::Point pa, t, u;
     good &= G::sc_is_canonical(c) & G::sc_is_canonical(s) & G::decode(pa, rows);
     G::encode(rows + G::EW, M);
     G::encode(rows + 2 * G::EW, Z);
-    const typename G::Point gen = G::generator();
     mul_call<G, WAVES>(u, c, pa);
-    mul_call<G, WAVES>(t, s, gen);
-    add_call<G, WAVES>(t, t, u);
+    base_mul<G>(t, s);
+    add<G>(t, t, u);
     G::encode(rows + 3 * G::EW, t);
     mul_call<G, WAVES>(t, s, M);
     mul_call<G, WAVES>(u, c, Z);
-    add_call<G, WAVES>(t, t, u);
+    add<G>(t, t, u);
     G::encode(rows + 4 * G::EW, t);
     challenge_scalar<G>(c2, rows, a.tag, a.tag_len);
     good &= Ops<G>::sc_equal(c2, c) ? 1u : 0u;
@@ -276,7 +347,7 @@ static __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES
         const bool take = threadIdx.x + d < 64 && g2 == g;
         if (take) {
             typename G::Point s;
-            add_call<G, WAVES>(s, Ops<G>::load(mw), Ops<G>::load(rw));
+            add<G>(s, Ops<G>::load(mw), Ops<G>::load(rw));
             Ops<G>::store(mw, s);
         }
         if (VERIFY) {
@@ -284,7 +355,7 @@ static __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES
             for (int i = 0; i < PW; i++) rw[i] = __shfl_down(zw[i], d);
             if (take) {
                 typename G::Point s;
-                add_call<G, WAVES>(s, Ops<G>::load(zw), Ops<G>::load(rw));
+                add<G>(s, Ops<G>::load(zw), Ops<G>::load(rw));
                 Ops<G>::store(zw, s);
             }
         }
@@ -313,8 +384,8 @@ static __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES
 #pragma unroll 1
         for (size_t w = (size_t)(first / 64); w <= w1; w++) {
             const uint32_t *slot = a.partial + (w + g) * (VERIFY ? 2 * PW : PW);
-            add_call<G, WAVES>(M, M, Ops<G>::load(slot));
-            if (VERIFY) add_call<G, WAVES>(Z, Z, Ops<G>::load(slot + PW));
+            add<G>(M, M, Ops<G>::load(slot));
+            if (VERIFY) add<G>(Z, Z, Ops<G>::load(slot + PW));
         }
     }
     if (VERIFY) verify_tail<G>(a, g, M, Z, good);
@@ -331,9 +402,9 @@ struct ItemArgs {
     const uint64_t *info_off;
     const uint32_t *scalars;   // sk (tweak server, full_evaluate; scalar_stride words apart, 0: one key) or blinds (finalize)
     size_t scalar_stride;
-    const uint8_t *elems;      // pkS (tweak client; elem_stride BYTES apart, 0: one key) or evaluated elements (finalize): rows of NE bytes
+    const uint8_t *elems;      // pkS (tweak client; elem_stride BYTES apart, 0: one key) or evaluated elements (finalize): element rows
     size_t elem_stride;
-    uint8_t *out, *out2, *out3;   // tweak server: t, t^-1 (words), t G (NE bytes); tweak client: the tweaked key; finalize / full_evaluate: NH / 4 words
+    uint8_t *out, *out2, *out3;   // tweak server: t, t^-1 (words), t G (an element row); tweak client: the tweaked key; finalize / full_evaluate: NH / 4 words
     uint8_t *ok;               // may be nullptr
     size_t n;
 };
@@ -412,8 +483,7 @@ struct PoprfItem<G, kTweakServer> {
         const uint32_t good = tweaked_secret<G>(t, a, i, info, info_len);
         G::sc_inv(tinv, t);
         typename G::Point p;
-        const typename G::Point gen = G::generator();
-        mul_call<G, WAVES>(p, t, gen);
+        base_mul<G>(p, t);
         G::encode(enc, p);
         G::sc_store(oprf::word_rows(a.out) + (size_t)SW * i, t, good);
         G::sc_store(oprf::word_rows(a.out2) + (size_t)SW * i, tinv, good);
@@ -433,13 +503,12 @@ struct PoprfItem<G, kTweakClient> {
         const bool fits = info_len <= oprf::kMaxInputBytes;
         uint32_t enc[G::EW];
         typename G::Scalar m;
-        G::elem_load(enc, a.elems + i * a.elem_stride);
+        G::elem_load(enc, oprf::elem_rows<G>(a.elems + i * a.elem_stride));
         typename G::Point p, q;
         uint32_t good = G::decode(p, enc) & (fits ? 1u : 0u);
         info_scalar<G>(m, info, fits ? info_len : 0);
-        const typename G::Point gen = G::generator();
-        mul_call<G, WAVES>(q, m, gen);
-        add_call<G, WAVES>(p, q, p);
+        base_mul<G>(q, m);
+        add<G>(p, q, p);
         good &= G::encode(enc, p) ^ 1u;   // the tweaked key is the identity
         G::elem_store(oprf::elem_rows<G>(a.out) + (size_t)G::ROW * i, enc, good);
         if (a.ok) a.ok[i] = (uint8_t)good;
@@ -456,12 +525,12 @@ struct PoprfItem<G, kPoprfFinalize> {
         uint32_t enc[G::EW], h[HW], ident;
         typename G::Scalar k, kinv;
         G::sc_load(k, a.scalars + i * a.scalar_stride);
-        G::elem_load(enc, a.elems + (size_t)G::NE * i);
+        G::elem_load(enc, oprf::elem_rows<G>(a.elems) + (size_t)G::ROW * i);
         typename G::Point p;
         uint32_t good = oprf::secret_scalar_ok<G>(k) & G::decode(p, enc, &ident) & (fits ? 1u : 0u);
         good &= ident ^ 1u;
         G::sc_inv(kinv, k);
-        mul_call<G, WAVES>(p, kinv, p);
+        mul<G>(p, kinv, p);
         G::encode(enc, p);
         finalize_hash2<G, WAVES>(h, m, fits ? len : 0, info, fits ? info_len : 0, enc);
         store_masked<HW>(oprf::word_rows(a.out) + (size_t)HW * i, h, good);
@@ -489,7 +558,7 @@ struct PoprfItem<G, kPoprfFullEvaluate> {
         const uint32_t tag_len = mode2_tag<G>(tag, true);
         hkdf::xmd<typename G::Hash, WAVES>(u, G::LEN_ELEM, nullptr, 0, m, fits ? len : 0, nullptr, 0, tag, tag_len);
         typename G::Point p = G::from_uniform(u, false);
-        mul_call<G, WAVES>(p, tinv, p);
+        mul<G>(p, tinv, p);
         good &= G::encode(enc, p) ^ 1u;   // the hashed point was the identity
         finalize_hash2<G, WAVES>(h, m, fits ? len : 0, info, info_len <= oprf::kMaxInputBytes ? info_len : 0, enc);
         store_masked<HW>(oprf::word_rows(a.out) + (size_t)HW * i, h, good);

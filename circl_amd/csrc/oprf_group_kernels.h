@@ -27,6 +27,7 @@
 //                              generator() supplies the point and the one multiplication runs on it (the NIST curves)
 //   base(k)                    k times the generator
 //   from_uniform(u, nonuniform)
+//   ctx_tail()                 the end of the suite's context string, its name: the one place that spells it
 //   wipe(Scalar &), wipe(Point &)
 //
 // Rows: scalars, keys and blinds are NS bytes read as words; seeds are 32 bytes and OPRF outputs NH bytes, words too; elements are packed
@@ -122,6 +123,7 @@ struct R255 {
     static CIRCL_HD Point mul(const Scalar &k, const Point &p) { return r255::r255_mul(k, p); }
     static CIRCL_HD Point base(const Scalar &k) { return r255::r255_base(k); }
     static CIRCL_HD Point from_uniform(const uint32_t *u, bool) { return r255::r255_from_uniform(u); }
+    static constexpr CIRCL_HD const char *ctx_tail() { return "-ristretto255-SHA512"; }
     static CIRCL_HD void wipe(Scalar &k) { oprf::wipe<8>(k); }
     static CIRCL_HD void wipe(Point &p) { oprf::wipe(p); }
 };
@@ -151,6 +153,7 @@ struct Nistp {
     static CIRCL_HD Point base(const Scalar &k) { return nistp::nistp_base<C>(k); }
     static CIRCL_HD Point generator() { return nistp::pt_generator<C>(); }
     static CIRCL_HD Point from_uniform(const uint32_t *u, bool nonuniform) { return nistp::nistp_from_uniform<C>(u, nonuniform); }
+    static constexpr CIRCL_HD const char *ctx_tail() { return C::CURVE == 256 ? "-P256-SHA256" : "-P384-SHA384"; }
     static CIRCL_HD void wipe(Scalar &k) { oprf::wipe<C::N>(k.v); }
     static CIRCL_HD void wipe(Point &p) {
         wipe(p.X);
@@ -160,6 +163,15 @@ struct Nistp {
 };
 using P256 = Nistp<nistp::P256>;
 using P384 = Nistp<nistp::P384>;
+
+// what the host layers (oprf_host.h, dleq_host.h) read off a group description: a row per group
+enum GroupId : int { kNoGroup = -1, kR255 = 0, kP256, kP384, kGroups };
+struct Suite {
+    size_t ns, ne, nh, elem_align;   // a scalar row, an element row, an OPRF output; what an element row's address must be a multiple of
+    const char *ctx_tail;            // the end of the suite's context string
+};
+template <class G> constexpr Suite suite_of() { return {G::NS, G::NE, G::NH, alignof(typename G::Row), G::ctx_tail()}; }
+constexpr Suite kSuites[kGroups] = {suite_of<R255>(), suite_of<P256>(), suite_of<P384>()};
 
 // ---- the operations, once ---------------------------------------------------------------------------------------------------------------
 // 1 for a scalar a key or a blind may be: canonical and not zero

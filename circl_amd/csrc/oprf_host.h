@@ -16,15 +16,6 @@
 namespace circl {
 namespace oprf {
 
-enum GroupId : int { kNoGroup = -1, kR255 = 0, kP256, kP384, kGroups };
-
-struct Suite {
-    size_t ns, ne, nh, elem_align;   // a scalar row, an element row, an OPRF output; what an element row's address must be a multiple of
-    const char *ctx_tail;            // the end of the suite's context string
-};
-template <class G> constexpr Suite suite_of(const char *ctx_tail) { return {G::NS, G::NE, G::NH, alignof(typename G::Row), ctx_tail}; }
-constexpr Suite kSuites[kGroups] = {suite_of<R255>("-ristretto255-SHA512"), suite_of<P256>("-P256-SHA256"), suite_of<P384>("-P384-SHA384")};
-
 struct Call {
     int group = kNoGroup, op = kHashToGroup, mode = 0;
     const uint8_t *blob = nullptr;       // msg / info / input

@@ -1,8 +1,8 @@
 // tests/hostsim/dleq_hostsim.hip -- TEST INFRASTRUCTURE: runs the lane-local __host__ __device__ functions of
-// circl_amd/csrc/dleq_kernels.h on the CPU (their host instantiation): the element function of the composite kernel, both tails of the
-// finish kernel and the POPRF item functions, so that the CPU-only test tier can check the very source the kernels are built from
-// against the checker tests/dleq.py.  The partial sums are added one after the other here; the shuffle tree of the composite kernel is
-// device code and is covered by tests/test_gpu_dleq.py.  Nothing here is linked into libcirclhip.so.
+// circl_amd/csrc/dleq_group_kernels.h on the CPU (their host instantiation for ristretto255): the element function of the composite
+// kernel, both tails of the finish kernel and the POPRF item functions, so that the CPU-only test tier can check the very source the
+// kernels are built from against the checker tests/dleq.py.  The partial sums are added one after the other here; the shuffle tree of
+// the composite kernel is device code and is covered by tests/test_gpu_dleq.py.  Nothing here is linked into libcirclhip.so.
 //
 // With -DDLEQ_HOSTSIM_MAIN it is a stand-alone program for a sanitizer build: blobs and element arrays are heap blocks of exactly their
 // size, requests of 1, 2 and 5 elements are proven and verified, and the POPRF items must agree with each other.
@@ -14,53 +14,55 @@
 // (see oprf_hostsim.hip: host-only, so plain inline instead of the device's forced inlining)
 #define CIRCL_HD __host__ __device__ inline
 
-#include "dleq_kernels.h"
+#include "dleq_group_kernels.h"
 
 using namespace circl;
 using ed25519::Ge;
+using oprf::R255;
+using O = gdleq::Ops<R255>;
 
 extern "C" {
 
-uint64_t hs_dleq_request_of(const dleq::Args *a, uint64_t e) { return dleq::request_of(*a, e); }
+uint64_t hs_dleq_request_of(const gdleq::Args *a, uint64_t e) { return gdleq::request_of<R255>(*a, e); }
 
 // the element function: m and z as 40 words each; returns its verdict
-int hs_dleq_element(int verify, const dleq::Args *a, uint64_t g, uint64_t e, uint32_t *m, uint32_t *z) {
+int hs_dleq_element(int verify, const gdleq::Args *a, uint64_t g, uint64_t e, uint32_t *m, uint32_t *z) {
     Ge pm, pz;
-    const uint32_t good = verify ? dleq::element<true>(pm, pz, *a, g, e) : dleq::element<false>(pm, pz, *a, g, e);
-    dleq::ge_store(m, pm);
-    dleq::ge_store(z, pz);
+    const uint32_t good = verify ? gdleq::element<R255, true>(pm, pz, *a, g, e) : gdleq::element<R255, false>(pm, pz, *a, g, e);
+    O::store(m, pm);
+    O::store(z, pz);
     return (int)good;
 }
 
 // One whole call the way the two kernels run it, one lane after the other: every element through element<>, the request's flag, the
 // sums in element order, then the tail.  a->bad must hold n_req words; a->partial is not used.
-void hs_dleq_call(int verify, const dleq::Args *a) {
-    const uint64_t e0 = dleq::elem_off(*a, 0);
+void hs_dleq_call(int verify, const gdleq::Args *a) {
+    const uint64_t e0 = gdleq::elem_off<R255>(*a, 0);
     for (size_t g = 0; g < a->n_req; g++) a->bad[g] = 0;
     for (size_t g = 0; g < a->n_req; g++) {
-        const uint64_t first = dleq::elem_off(*a, g), cnt = dleq::elem_off(*a, g + 1) - first;
+        const uint64_t first = gdleq::elem_off<R255>(*a, g), cnt = gdleq::elem_off<R255>(*a, g + 1) - first;
         Ge M = ed25519::ge_identity(), Z = ed25519::ge_identity();
         for (uint64_t e = first; e < first + cnt && e - e0 < a->n_elems; e++) {
-            if (dleq::request_of(*a, e) != g) a->bad[g] = 1u;   // (the search must find the request that owns e)
+            if (gdleq::request_of<R255>(*a, e) != g) a->bad[g] = 1u;   // (the search must find the request that owns e)
             Ge pm, pz;
-            const uint32_t good = verify ? dleq::element<true>(pm, pz, *a, g, e) : dleq::element<false>(pm, pz, *a, g, e);
+            const uint32_t good = verify ? gdleq::element<R255, true>(pm, pz, *a, g, e) : gdleq::element<R255, false>(pm, pz, *a, g, e);
             if (!good) a->bad[g] = 1u;
             M = r255::r255_add(M, pm);
             if (verify) Z = r255::r255_add(Z, pz);
         }
-        const uint32_t good = (cnt >= 1 && cnt <= dleq::kMaxBatch && !a->bad[g]) ? 1u : 0u;
+        const uint32_t good = (cnt >= 1 && cnt <= gdleq::kMaxBatch && !a->bad[g]) ? 1u : 0u;
         if (!good) M = Z = ed25519::ge_identity();
-        if (verify) dleq::verify_tail(*a, g, M, Z, good);
-        else dleq::prove_tail(*a, g, M, good);
+        if (verify) gdleq::verify_tail<R255>(*a, g, M, Z, good);
+        else gdleq::prove_tail<R255>(*a, g, M, good);
     }
 }
 
-void hs_poprf_item(int op, const dleq::ItemArgs *a, uint64_t i) {
+void hs_poprf_item(int op, const gdleq::ItemArgs *a, uint64_t i) {
     switch (op) {
-        case dleq::kTweakServer: dleq::item<dleq::kTweakServer>(*a, i); break;
-        case dleq::kTweakClient: dleq::item<dleq::kTweakClient>(*a, i); break;
-        case dleq::kPoprfFinalize: dleq::item<dleq::kPoprfFinalize>(*a, i); break;
-        case dleq::kPoprfFullEvaluate: dleq::item<dleq::kPoprfFullEvaluate>(*a, i); break;
+        case gdleq::kTweakServer: gdleq::PoprfItem<R255, gdleq::kTweakServer>::run(*a, i); break;
+        case gdleq::kTweakClient: gdleq::PoprfItem<R255, gdleq::kTweakClient>::run(*a, i); break;
+        case gdleq::kPoprfFinalize: gdleq::PoprfItem<R255, gdleq::kPoprfFinalize>::run(*a, i); break;
+        case gdleq::kPoprfFullEvaluate: gdleq::PoprfItem<R255, gdleq::kPoprfFullEvaluate>::run(*a, i); break;
     }
 }
 
@@ -89,17 +91,19 @@ struct Bytes {
     Bytes(const Bytes &) = delete;
 };
 
+uint8_t *bytes(uint32_t *w) { return reinterpret_cast<uint8_t *>(w); }
+
 int fail(const char *what) {
     printf("FAIL %s\n", what);
     return 1;
 }
 
-void set_tag(dleq::Args &a, int mode) {
+void set_tag(gdleq::Args &a, int mode) {
     const char *s = "HashToScalar-OPRFV1-";
     size_t at = 0;
     for (; *s; s++) a.tag[at++] = (uint8_t)*s;
     a.tag[at++] = (uint8_t)mode;
-    for (s = "-ristretto255-SHA512"; *s; s++) a.tag[at++] = (uint8_t)*s;
+    for (s = R255::ctx_tail(); *s; s++) a.tag[at++] = (uint8_t)*s;
     a.tag_len = (uint32_t)at;
 }
 
@@ -131,10 +135,10 @@ int run_proofs() {
         r255::r255_encode(B.w + 8 * e, p);
         r255::r255_encode(kB.w + 8 * e, r255::r255_mul(k.w + 8 * g, p));
     }
-    dleq::Args a = {};
-    a.off = offs.data();
-    a.B = B.w; a.kB = kB.w; a.k = k.w; a.k_stride = 8; a.kA = kA.w; a.kA_stride = 8; a.r = r.w; a.proofs = proofs.w; a.ok = ok.data();
-    a.bad = bad.w; a.n_req = n_req; a.n_elems = n; a.flags = dleq::kNoIdentity;
+    gdleq::Args a = {};
+    a.off = offs.data(); a.off_div = 1;
+    a.B = bytes(B.w); a.kB = bytes(kB.w); a.k = k.w; a.k_stride = 8; a.kA = bytes(kA.w); a.kA_stride = 32; a.r = r.w; a.proofs = proofs.w; a.ok = ok.data();
+    a.bad = bad.w; a.n_req = n_req; a.n_elems = n; a.flags = gdleq::kNoIdentity;
     set_tag(a, 1);
     hs_dleq_call(0, &a);
     if (ok[0] != 1 || ok[1] != 1 || ok[2] != 0 || ok[3] != 1) return fail("prove: ok");
@@ -162,25 +166,25 @@ int run_poprf() {
     std::vector<uint8_t> ok(n);
     small_scalar(sk.w, 12345);
     r255::r255_encode(pk.w, r255::r255_base(sk.w));
-    dleq::ItemArgs a = {};
-    a.info = info.p; a.info_off = info_off.data(); a.scalars = sk.w; a.scalar_stride = 0; a.out = t.w; a.out2 = tinv.w; a.out3 = tg.w;
+    gdleq::ItemArgs a = {};
+    a.info = info.p; a.info_off = info_off.data(); a.scalars = sk.w; a.scalar_stride = 0; a.out = bytes(t.w); a.out2 = bytes(tinv.w); a.out3 = bytes(tg.w);
     a.ok = ok.data(); a.n = n;
-    for (size_t i = 0; i < n; i++) { hs_poprf_item(dleq::kTweakServer, &a, i); if (!ok[i]) return fail("tweak (server) refused an item"); }
-    a.scalars = nullptr; a.elems = pk.w; a.elem_stride = 0; a.out = tweaked.w; a.out2 = a.out3 = nullptr;
-    for (size_t i = 0; i < n; i++) { hs_poprf_item(dleq::kTweakClient, &a, i); if (!ok[i]) return fail("tweak (client) refused an item"); }
+    for (size_t i = 0; i < n; i++) { hs_poprf_item(gdleq::kTweakServer, &a, i); if (!ok[i]) return fail("tweak (server) refused an item"); }
+    a.scalars = nullptr; a.elems = bytes(pk.w); a.elem_stride = 0; a.out = bytes(tweaked.w); a.out2 = a.out3 = nullptr;
+    for (size_t i = 0; i < n; i++) { hs_poprf_item(gdleq::kTweakClient, &a, i); if (!ok[i]) return fail("tweak (client) refused an item"); }
     if (memcmp(tg.w, tweaked.w, 32 * n)) return fail("t G != m G + pkS");
     // blind, evaluate with t^-1 (base-mode items of oprf_group_kernels.h), finalize with the info; and the same in one step
     for (size_t i = 0; i < n; i++) small_scalar(blinds.w + 8 * i, 500 + (uint32_t)i);
     oprf::Args o = {};
-    o.blob = in.p; o.off = in_off.data(); o.scalars = blinds.w; o.scalar_stride = 8; o.out = reinterpret_cast<uint8_t *>(blinded.w); o.ok = ok.data(); o.n = n;
-    o.dst_len = dleq::mode2_tag(o.dst, true);
+    o.blob = in.p; o.off = in_off.data(); o.scalars = blinds.w; o.scalar_stride = 8; o.out = bytes(blinded.w); o.ok = ok.data(); o.n = n;
+    o.dst_len = gdleq::mode2_tag<R255>(o.dst, true);
     for (size_t i = 0; i < n; i++) { oprf::Item<oprf::R255, oprf::kBlind, oprf::WAVES>::run(o, i); if (!ok[i]) return fail("blind refused an item"); }
-    o.blob = nullptr; o.off = nullptr; o.scalars = tinv.w; o.elems = reinterpret_cast<const uint8_t *>(blinded.w); o.out = reinterpret_cast<uint8_t *>(evaluated.w);
+    o.blob = nullptr; o.off = nullptr; o.scalars = tinv.w; o.elems = bytes(blinded.w); o.out = bytes(evaluated.w);
     for (size_t i = 0; i < n; i++) { oprf::Item<oprf::R255, oprf::kEvaluate, oprf::WAVES>::run(o, i); if (!ok[i]) return fail("evaluate refused an item"); }
-    a.input = in.p; a.input_off = in_off.data(); a.scalars = blinds.w; a.scalar_stride = 8; a.elems = evaluated.w; a.elem_stride = 8; a.out = out.w;
-    for (size_t i = 0; i < n; i++) { hs_poprf_item(dleq::kPoprfFinalize, &a, i); if (!ok[i]) return fail("poprf_finalize refused an item"); }
-    a.scalars = sk.w; a.scalar_stride = 0; a.elems = nullptr; a.out = full.w;
-    for (size_t i = 0; i < n; i++) { hs_poprf_item(dleq::kPoprfFullEvaluate, &a, i); if (!ok[i]) return fail("poprf_full_evaluate refused an item"); }
+    a.input = in.p; a.input_off = in_off.data(); a.scalars = blinds.w; a.scalar_stride = 8; a.elems = bytes(evaluated.w); a.elem_stride = 32; a.out = bytes(out.w);
+    for (size_t i = 0; i < n; i++) { hs_poprf_item(gdleq::kPoprfFinalize, &a, i); if (!ok[i]) return fail("poprf_finalize refused an item"); }
+    a.scalars = sk.w; a.scalar_stride = 0; a.elems = nullptr; a.out = bytes(full.w);
+    for (size_t i = 0; i < n; i++) { hs_poprf_item(gdleq::kPoprfFullEvaluate, &a, i); if (!ok[i]) return fail("poprf_full_evaluate refused an item"); }
     if (memcmp(out.w, full.w, 64 * n)) return fail("poprf_finalize(evaluate(blind(x))) != poprf_full_evaluate(x)");
     return 0;
 }

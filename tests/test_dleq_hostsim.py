@@ -1,6 +1,6 @@
-"""CPU-side checks of the DLEQ / POPRF device source: the element function, both tails and the POPRF item functions of dleq_kernels.h
-compiled for the host (tests/hostsim/dleq_hostsim.hip) against the checker tests/dleq.py and the fixture, and the same source as a
-stand-alone program under AddressSanitizer / UBSan."""
+"""CPU-side checks of the DLEQ / POPRF device source: the element function, both tails and the POPRF item functions of
+dleq_group_kernels.h for ristretto255, compiled for the host (tests/hostsim/dleq_hostsim.hip), against the checker tests/dleq.py and the
+fixture, and the same source as a stand-alone program under AddressSanitizer / UBSan."""
 import ctypes as C
 import os
 import subprocess
@@ -18,17 +18,17 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 G = load_golden("oprf_ristretto255.json.gz")
 SRC = os.path.join(ROOT, "tests", "hostsim", "dleq_hostsim.hip")
 vp, u64, u32, sz = C.c_void_p, C.c_uint64, C.c_uint32, C.c_size_t
-TWEAK_SERVER, TWEAK_CLIENT, FINALIZE, FULL = range(4)       # dleq_kernels.h ItemOp
+TWEAK_SERVER, TWEAK_CLIENT, FINALIZE, FULL = range(4)       # dleq_group_kernels.h ItemOp
 L = oprf.L
 
 
-class Args(C.Structure):  # dleq_kernels.h Args
-    _fields_ = [("off", vp), ("off_shift", u32), ("B", vp), ("kB", vp), ("k", vp), ("k_stride", sz), ("kA", vp), ("kA_stride", sz), ("r", vp),
+class Args(C.Structure):  # dleq_group_kernels.h Args
+    _fields_ = [("off", vp), ("off_div", u32), ("B", vp), ("kB", vp), ("k", vp), ("k_stride", sz), ("kA", vp), ("kA_stride", sz), ("r", vp),
                 ("proofs", vp), ("ok", vp), ("partial", vp), ("bad", vp), ("n_req", sz), ("n_elems", sz), ("flags", u32), ("tag_len", u32),
                 ("tag", C.c_uint8 * 256)]
 
 
-class ItemArgs(C.Structure):  # dleq_kernels.h ItemArgs
+class ItemArgs(C.Structure):  # dleq_group_kernels.h ItemArgs
     _fields_ = [("input", vp), ("input_off", vp), ("info", vp), ("info_off", vp), ("scalars", vp), ("scalar_stride", sz), ("elems", vp),
                 ("elem_stride", sz), ("out", vp), ("out2", vp), ("out3", vp), ("ok", vp), ("n", sz)]
 
@@ -67,19 +67,19 @@ def _rows(rows, width=32):
     return a
 
 
-def sim_call(hs, verify, ctx, kA, reqs, k=None, r=None, proofs=None, flags=0, shift=0, lead=0):
+def sim_call(hs, verify, ctx, kA, reqs, k=None, r=None, proofs=None, flags=0, div=1, lead=0):
     """One call through the host instantiation.  reqs: a list of (B rows, kB rows); kA / k: one row (shared) or a list (per request).
-    shift: the offsets' unit (5: bytes, as the host pipeline passes them); lead: elements in front of the first request (a chunk whose
+    div: the offsets' unit (32: bytes, as the host pipeline passes them); lead: elements in front of the first request (a chunk whose
     offsets do not start at 0).  Returns (proof rows, ok) for prove, ok for verify."""
-    n_req = len(reqs)
+    n_req, shift = len(reqs), {1: 0, 32: 5}[div]
     off = np.array([lead] + [lead + sum(len(b) for b, _ in reqs[:g + 1]) for g in range(n_req)], np.uint64) << np.uint64(shift)
     pad = [bytes(32)] * lead
     B, kB = _rows(pad + [x for b, _ in reqs for x in b]), _rows(pad + [x for _, kb in reqs for x in kb])
     shared = lambda x: isinstance(x, bytes)
     a = Args()
-    a.off, a.off_shift, a.B, a.kB = _p(off), shift, _p(B), _p(kB)
+    a.off, a.off_div, a.B, a.kB = _p(off), div, _p(B), _p(kB)
     ka = _rows([kA] if shared(kA) else kA)
-    a.kA, a.kA_stride = _p(ka), 0 if shared(kA) else 8
+    a.kA, a.kA_stride = _p(ka), 0 if shared(kA) else 32
     if not verify:
         kk, rr = _rows([k] if shared(k) else k), _rows(r)
         a.k, a.k_stride, a.r = _p(kk), 0 if shared(k) else 8, _p(rr)
@@ -104,9 +104,9 @@ def test_the_fixture_proofs_in_one_call_per_mode(hs):
         ctx = cases[0][1]
         reqs = [(c[4], c[5]) for c in cases]
         ks, kAs, rs, want = [c[2] for c in cases], [c[3] for c in cases], [c[6] for c in cases], [c[7] for c in cases]
-        for shift, lead in ((0, 0), (5, 0), (5, 3)):
-            assert sim_call(hs, False, ctx, kAs, reqs, k=ks, r=rs, flags=1, shift=shift, lead=lead) == (want, [1, 1, 1]), (mode, shift, lead)
-            assert sim_call(hs, True, ctx, kAs, reqs, proofs=want, flags=1, shift=shift, lead=lead) == [1, 1, 1]
+        for div, lead in ((1, 0), (32, 0), (32, 3)):
+            assert sim_call(hs, False, ctx, kAs, reqs, k=ks, r=rs, flags=1, div=div, lead=lead) == (want, [1, 1, 1]), (mode, div, lead)
+            assert sim_call(hs, True, ctx, kAs, reqs, proofs=want, flags=1, div=div, lead=lead) == [1, 1, 1]
         if mode == 1:       # one key for the call
             assert sim_call(hs, False, ctx, kAs[0], reqs, k=ks[0], r=rs) == (want, [1, 1, 1])
         bad = [want[0], flip(want[1], 9), flip(want[2], 300)]
@@ -184,7 +184,7 @@ def run_item(hs, op, inp=None, info=None, scalar=None, elem=None, outs=1, out_by
     if scalar is not None:
         a.scalars, a.scalar_stride = rows(scalar), 8
     if elem is not None:
-        a.elems, a.elem_stride = rows(elem), 8
+        a.elems, a.elem_stride = rows(elem), 32
     w = out_bytes // 4
     o = [np.full(3 * w, 0xA5A5A5A5, np.uint32) for _ in range(outs)]
     ok = np.full(3, 7, np.uint8)
