@@ -3,7 +3,7 @@ ROCM ?= /opt/rocm
 HIPCC ?= $(ROCM)/bin/hipcc
 ARCH ?= gfx950
 
-UNITS = host_runtime host_coalesce api_mlkem api_mldsa api_prims api_x25519 api_hybrid api_ed25519 api_curve448 api_frodo api_hpke api_hpke_ctx api_oprf api_dleq api_ascon api_aesgcm api_nistp api_dleq_nistp
+UNITS = host_runtime host_coalesce api_mlkem api_mldsa api_prims api_x25519 api_hybrid api_ed25519 api_curve448 api_frodo api_hpke api_hpke_ctx api_oprf api_dleq api_ascon api_aesgcm api_nistp api_dleq_nistp api_prio3
 OBJS = $(UNITS:%=build/%.o)
 HIPFLAGS = --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -Wno-unused-variable
 

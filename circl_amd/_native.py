@@ -69,7 +69,10 @@ SYMBOLS = [
                     "circl_hip_oprf_nistp_blind", "circl_hip_oprf_nistp_evaluate", "circl_hip_oprf_nistp_finalize", "circl_hip_oprf_nistp_full_evaluate",
                     "circl_hip_nistp_dleq_prove", "circl_hip_nistp_dleq_verify", "circl_hip_oprf_nistp_poprf_tweak", "circl_hip_oprf_nistp_poprf_finalize",
                     "circl_hip_oprf_nistp_poprf_full_evaluate")
-    for d in ("", "_dev")] + ["circl_hip_nistp_dleq_workspace_size"]
+    for d in ("", "_dev")] + ["circl_hip_nistp_dleq_workspace_size"] + [
+    "circl_hip_prio3_leader_share_size", "circl_hip_prio3_prep_share_size", "circl_hip_prio3_rand_size", "circl_hip_prio3_workspace_size",
+    "circl_hip_prio3_unshard"] + [f + d for f in ("circl_hip_prio3_shard", "circl_hip_prio3_prep_init", "circl_hip_prio3_prep_finish", "circl_hip_prio3_aggregate")
+                                  for d in ("", "_dev")]
 
 OK, EPARAM, ENODEV, EHIP, ENOMEM, EWORKSPACE, EBUSY, EAGAIN = 0, -1, -2, -3, -4, -5, -6, -7
 ALL_DEVICES = -1
@@ -307,6 +310,17 @@ def lib():
                            ("aesgcm_seal", [i, vp, sz, vp, sz] + [vp] * 6), ("aesgcm_open", [i, vp, sz, vp, sz] + [vp] * 7)):
             getattr(L, "circl_hip_" + name).argtypes = args + [sz, i]
             getattr(L, "circl_hip_" + name + "_dev").argtypes = args + [sz, vp]
+        u64 = C.c_uint64
+        task = [i, u64, i, vp, sz]       # kind, max_measurement, shares, ctx, ctx_len
+        L.circl_hip_prio3_leader_share_size.restype, L.circl_hip_prio3_leader_share_size.argtypes = sz, [i, u64]
+        L.circl_hip_prio3_prep_share_size.restype, L.circl_hip_prio3_prep_share_size.argtypes = sz, [i]
+        L.circl_hip_prio3_rand_size.restype, L.circl_hip_prio3_rand_size.argtypes = sz, [i]
+        L.circl_hip_prio3_workspace_size.restype, L.circl_hip_prio3_workspace_size.argtypes = sz, [i, u64, sz]
+        for name, args, ws in (("prio3_shard", [vp] * 4, True), ("prio3_prep_init", [i] + [vp] * 6, True), ("prio3_prep_finish", [vp] * 2, False),
+                               ("prio3_aggregate", [vp] * 3, True)):
+            getattr(L, "circl_hip_" + name).argtypes = task + args + [sz, i]
+            getattr(L, "circl_hip_" + name + "_dev").argtypes = task + args + [sz] + ([vp, sz] if ws else []) + [vp]
+        L.circl_hip_prio3_unshard.argtypes = task + [vp, u64, vp]
         for f in ("seed", "eseed", "pk", "sk", "ct", "ss"):
             fn = getattr(L, "circl_hip_hybrid_%s_size" % f)
             fn.restype, fn.argtypes = sz, [i]

@@ -765,3 +765,58 @@ class NistpOprfDevice(_OprfGroupDevice):
         self.Ns = curve // 8
         self.Ne, self.Nh = self.Ns + 1, self.Ns
         self._tail = b"-P256-SHA256" if curve == 256 else b"-P384-SHA384"
+
+
+class Prio3Device:
+    """Prio3Count / Prio3Sum on resident tensors (circl_hip_prio3_*_dev), on torch's current stream; shaped like hostapi.Prio3.  Measurements
+    are an (n,) int64 / uint64 tensor, every other array a contiguous uint8 tensor whose storage is 8-byte aligned; the verify key is a
+    (32,) tensor, the aggregate share an (8,) tensor that aggregate() updates in place.  The workspace grows to the largest batch seen
+    and holds the last call's per-report state, as secret as its inputs."""
+
+    def __init__(self, kind, max_measurement, shares, ctx, device="cuda"):
+        self.device, self.L = device, nat.lib()
+        self.kind, self.max, self.shares, self.ctx = kind, max_measurement, shares, bytes(ctx)
+        self.task = (kind, max_measurement, shares, self.ctx, len(self.ctx))
+        self.leader_share_size = self.L.circl_hip_prio3_leader_share_size(kind, max_measurement) if 0 <= max_measurement < 2**64 else 0
+        self.prep_share_size = self.L.circl_hip_prio3_prep_share_size(kind)
+        self.rand_size = self.L.circl_hip_prio3_rand_size(shares)
+        if not (self.leader_share_size and self.prep_share_size and self.rand_size) or len(self.ctx) > 255:
+            raise ValueError("prio3: kind 1 (max_measurement 0) or 2 (1 .. 2^63 - 1), 2 .. 255 shares, a context of at most 255 bytes")
+        self.ws = None
+
+    def _out(self, *shape):
+        return torch.empty(shape, dtype=torch.uint8, device=self.device)
+
+    def _ws(self, n):
+        need = self.L.circl_hip_prio3_workspace_size(self.kind, self.max, n)
+        if self.ws is None or self.ws.numel() < need:
+            self.ws = self._out(need)
+        return self.ws.data_ptr(), self.ws.numel()
+
+    def shard(self, measurements, rand):
+        n = measurements.shape[0]
+        assert measurements.is_cuda and measurements.element_size() == 8 and measurements.is_contiguous()
+        leader, ok = self._out(n, self.leader_share_size), self._out(n)
+        nat.check(self.L.circl_hip_prio3_shard_dev(*self.task, measurements.data_ptr(), _chk(rand, self.rand_size), _chk(leader), _chk(ok), n, *self._ws(n), _stream()),
+                  "prio3_shard_dev")
+        return leader, ok
+
+    def prep_init(self, agg_id, verify_key, nonces, input_shares):
+        n = nonces.shape[0]
+        prep, out, ok = self._out(n, self.prep_share_size), self._out(n, 8), self._out(n)
+        nat.check(self.L.circl_hip_prio3_prep_init_dev(*self.task, agg_id, _chk(verify_key, 32), _chk(nonces, 16),
+                                                       _chk(input_shares, self.leader_share_size if agg_id == 0 else 32), _chk(prep), _chk(out), _chk(ok), n,
+                                                       *self._ws(n), _stream()), "prio3_prep_init_dev")
+        return prep, out, ok
+
+    def prep_finish(self, prep_shares):
+        n = prep_shares.shape[0]
+        ok = self._out(n)
+        nat.check(self.L.circl_hip_prio3_prep_finish_dev(*self.task, _chk(prep_shares), _chk(ok), n, _stream()), "prio3_prep_finish_dev")
+        return ok
+
+    def aggregate(self, agg_share, out_shares, mask=None):
+        n = out_shares.shape[0]
+        nat.check(self.L.circl_hip_prio3_aggregate_dev(*self.task, _chk(out_shares, 8), None if mask is None else _chk(mask), _chk(agg_share, 8), n, *self._ws(n),
+                                                       _stream()), "prio3_aggregate_dev")
+        return agg_share

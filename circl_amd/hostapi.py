@@ -1630,3 +1630,69 @@ class AesGcm:
         nat.check(self.L.circl_hip_aesgcm_open(self.key_size, _p(self.keys), stride, _p(nonces), nstride, _po(seq), _p(cb), _p(po), _po(ab), _po(ao), _p(pt),
                                                _p(ok), n, self.device), "aesgcm_open")
         return _unrag(pt, po), ok
+
+
+# ---- Prio3Count / Prio3Sum: batch VDAF preparation (vdaf/prio3/count, vdaf/prio3/sum; draft-irtf-cfrg-vdaf-13 section 7) ----
+PRIO3_COUNT, PRIO3_SUM = 1, 2
+
+
+class Prio3:
+    """Prio3Count (kind 1, max_measurement 0) or Prio3Sum (kind 2, max_measurement 1 .. 2^63 - 1) over batches of reports on host
+    buffers.  shares aggregators (2 .. 255), ctx the application context (at most 255 bytes).  Rows are the reference's MarshalBinary:
+    elements of 8 little-endian bytes.  Failed reports have ok = 0 and zero rows."""
+
+    def __init__(self, kind, max_measurement, shares, ctx, device=0):
+        self.device, self.L = device, nat.lib()
+        self.kind, self.max, self.shares, self.ctx = kind, max_measurement, shares, bytes(ctx)
+        self.task = (kind, max_measurement, shares, self.ctx, len(self.ctx))
+        self.leader_share_size = self.L.circl_hip_prio3_leader_share_size(kind, max_measurement) if 0 <= max_measurement < 2**64 else 0
+        self.prep_share_size = self.L.circl_hip_prio3_prep_share_size(kind)
+        self.rand_size = self.L.circl_hip_prio3_rand_size(shares)
+        if not (self.leader_share_size and self.prep_share_size and self.rand_size) or len(self.ctx) > 255:
+            raise ValueError("prio3: kind 1 (max_measurement 0) or 2 (1 .. 2^63 - 1), 2 .. 255 shares, a context of at most 255 bytes")
+
+    def shard(self, measurements, rand):
+        """measurements (n,), rand (n, 32 shares): helpers' seeds then the prove seed -> (leader shares (n, leader_share_size), ok (n,));
+        helper j's input share is rand[:, 32 (j - 1) : 32 j]"""
+        m, rand = np.ascontiguousarray(measurements, np.uint64), _u8(rand, self.rand_size)
+        n = m.shape[0]
+        if rand.shape[0] != n:
+            raise ValueError("prio3_shard: %d measurements, %d rows of rand" % (n, rand.shape[0]))
+        leader, ok = np.empty((n, self.leader_share_size), np.uint8), np.empty(n, np.uint8)
+        nat.check(self.L.circl_hip_prio3_shard(*self.task, _p(m), _p(rand), _p(leader), _p(ok), n, self.device), "prio3_shard")
+        return leader, ok
+
+    def prep_init(self, agg_id, verify_key, nonces, input_shares):
+        """input_shares: the leader shares (agg_id 0) or (n, 32) seeds -> (prep shares (n, prep_share_size), out shares (n, 8), ok (n,))"""
+        vk, nonces = _u8(verify_key, 32), _u8(nonces, 16)
+        shares = _u8(input_shares, self.leader_share_size if agg_id == 0 else 32)
+        n = nonces.shape[0]
+        if shares.shape[0] != n or vk.shape[0] != 1:
+            raise ValueError("prio3_prep_init: %d nonces, %d input shares, %d verify keys" % (n, shares.shape[0], vk.shape[0]))
+        prep, out, ok = np.empty((n, self.prep_share_size), np.uint8), np.empty((n, 8), np.uint8), np.empty(n, np.uint8)
+        nat.check(self.L.circl_hip_prio3_prep_init(*self.task, agg_id, _p(vk), _p(nonces), _p(shares), _p(prep), _p(out), _p(ok), n, self.device), "prio3_prep_init")
+        return prep, out, ok
+
+    def prep_finish(self, prep_shares):
+        """PrepSharesToPrep: prep_shares (n, shares, prep_share_size), an item's shares in aggregator order -> ok (n,)"""
+        ps = _u8(prep_shares, self.shares * self.prep_share_size)
+        ok = np.empty(ps.shape[0], np.uint8)
+        nat.check(self.L.circl_hip_prio3_prep_finish(*self.task, _p(ps), _p(ok), ps.shape[0], self.device), "prio3_prep_finish")
+        return ok
+
+    def aggregate(self, agg_share, out_shares, mask=None):
+        """AggregateUpdate over the batch -> the new aggregate share (8 bytes); mask (n,): only the items where it is not zero"""
+        out, agg = _u8(out_shares, 8), _u8(agg_share, 8).copy()
+        mask = None if mask is None else np.ascontiguousarray(mask, np.uint8)
+        if mask is not None and mask.shape != (out.shape[0],):
+            raise ValueError("prio3_aggregate: a mask has one byte per out share")
+        nat.check(self.L.circl_hip_prio3_aggregate(*self.task, _p(out), None if mask is None else _p(mask), _p(agg), out.shape[0], self.device), "prio3_aggregate")
+        return agg.tobytes()
+
+    def unshard(self, agg_shares, num_measurements):
+        """the aggregate result (an int) from the `shares` aggregate shares; no device is used"""
+        a, res = _u8(b"".join(bytes(x) for x in agg_shares), 8), C.c_uint64(0)
+        if a.shape[0] != self.shares:
+            raise ValueError("prio3_unshard: one aggregate share per aggregator")
+        nat.check(self.L.circl_hip_prio3_unshard(*self.task, _p(a), num_measurements, C.byref(res)), "prio3_unshard")
+        return res.value

@@ -1201,6 +1201,72 @@ int circl_hip_aesgcm_open_dev(int key_bytes, const uint8_t *key, size_t key_stri
                               const uint8_t *ct_blob, const uint64_t *pt_off, const uint8_t *aad_blob, const uint64_t *aad_off, uint8_t *pt_blob, uint8_t *ok,
                               size_t n, void *stream);
 
+/* ---- Prio3Count and Prio3Sum: batch VDAF preparation (the reference's vdaf/prio3/count and vdaf/prio3/sum) -------------------------
+ * draft-irtf-cfrg-vdaf-13 section 7 over Field64 (p = 2^64 - 2^32 + 1) and XofTurboShake128, one report per lane.  A batch is n reports
+ * under ONE task, spelled the same way in every call:
+ *   kind             CIRCL_HIP_PRIO3_COUNT or CIRCL_HIP_PRIO3_SUM (the algorithm ids 1 and 2);
+ *   max_measurement  0 for Count; 1 .. 2^63 - 1 for Sum (0 is refused: the reference accepts that degenerate type, this library does not);
+ *   shares           2 .. 255 aggregators;
+ *   ctx, ctx_len     the application context string, a HOST pointer in both forms (a task parameter like the scalars: it travels to the
+ *                    kernels by value); ctx_len <= 255, a longer one is CIRCL_HIP_EPARAM (the reference allows 65527; DAP uses about 40).
+ * Anything else is CIRCL_HIP_EPARAM, decided before a device is looked for; so are NULL pointers (ok may be NULL in shard and prep_init,
+ * mask in aggregate).  n == 0 is CIRCL_HIP_OK.  All encodings are the reference's MarshalBinary: an element is 8 little-endian
+ * bytes, canonical (< p).  Sizes, b = the bit length of max_measurement, P = the next power of two >= 1 + gadget calls:
+ *   Count: leader share 8 (1 + 5) = 48 bytes, prep share 32;   Sum: leader share 8 (2b + 2P), prep share 24;   rand 32 shares;
+ *   nonce 16, verify key 32, out share 8, aggregate share 8.  The size queries return 0 for a type that is not served.
+ *
+ *   shard        measurement[n] (uint64), rand[n][32 shares] (the seeds of helpers 1 .. shares - 1, then the prove seed, as the reference
+ *                reads them) -> leader_share[n][..], ok[n].  Helper j's input share is bytes 32 (j - 1) .. 32 j of the caller's own rand
+ *                row and is written nowhere.  ok = 0 and a zero row: a measurement out of range (Count > 1, Sum > max_measurement), or a
+ *                sampler that was refused 10 words in a row.
+ *   prep_init    agg_id (one per call, < shares), verify_key[32] (one per call), nonce[n][16], input_share[n][..] (the leader share for
+ *                agg_id 0, otherwise the 32-byte seed) -> prep_share[n][..], out_share[n][8], ok[n].  The out share is the prepare
+ *                state: without joint randomness PrepNext is the identity and the prep message is empty, so neither has a call.  ok = 0
+ *                and zero rows: a leader share with an element that is not canonical, an evaluation point t with t^P = 1, an exhausted
+ *                sampler.
+ *   prep_finish  PrepSharesToPrep: prep_shares[n][shares x prep share], item-major, an item's shares in aggregator order -> ok[n], Decide
+ *                on the summed verifier; an element that is not canonical is ok = 0.
+ *   aggregate    AggregateUpdate over the batch: agg_share[8] (read and updated) += the out_share[n][8] with mask[i] != 0 (mask == NULL:
+ *                all of them).  Exact modular sums: the result does not depend on the order.  Elements are reduced mod p as read.
+ *   unshard      host only, looks for no device: agg_shares[shares][8], num_measurements -> *result, the reference's Decode.  For Sum,
+ *                num_measurements x max_measurement that is not an element (ErrAggregateBound) is CIRCL_HIP_EPARAM, as is an aggregate share
+ *                that is not canonical.
+ * The _dev forms of shard, prep_init and aggregate take a workspace of circl_hip_prio3_workspace_size(kind, max_measurement, n) bytes
+ * (monotone in n; 8 (2 arity P + 2b + 1) bytes per report rounded up to 64 reports, at least 8 KB; aggregate alone needs the 8 KB): the
+ * reports' wires and folded polynomials, as secret afterwards as the call's inputs.  A workspace that is too small, or a pointer that is
+ * not 8-byte aligned (ok and mask excepted), is CIRCL_HIP_EWORKSPACE.  The host forms allocate the workspace in the pipeline.
+ * Measurements, rand, input shares, the verify key, out shares and the aggregate share are secret: the host forms wipe their staging
+ * and zero the device staging of every chunk.  Nonces, prep shares and verdicts are not.
+ * The launches run without a profiling scope: there is no CIRCL_HIP_KERNEL_* id for them.
+ * Not served: Prio3SumVec, Prio3Histogram and Prio3MultihotCountVec (Field128, joint randomness, a workgroup per report); more than one
+ * proof (the reference fixes it at 1 as well); key tables, the coalescer and the asynchronous queue; the Go bridge. */
+#define CIRCL_HIP_PRIO3_COUNT 1
+#define CIRCL_HIP_PRIO3_SUM 2
+size_t circl_hip_prio3_leader_share_size(int kind, uint64_t max_measurement);
+size_t circl_hip_prio3_prep_share_size(int kind);
+size_t circl_hip_prio3_rand_size(int shares);
+size_t circl_hip_prio3_workspace_size(int kind, uint64_t max_measurement, size_t n);
+int circl_hip_prio3_shard(int kind, uint64_t max_measurement, int shares, const uint8_t *ctx, size_t ctx_len, const uint64_t *measurement, const uint8_t *rand,
+                          uint8_t *leader_share, uint8_t *ok, size_t n, int device);
+int circl_hip_prio3_prep_init(int kind, uint64_t max_measurement, int shares, const uint8_t *ctx, size_t ctx_len, int agg_id, const uint8_t *verify_key,
+                              const uint8_t *nonce, const uint8_t *input_share, uint8_t *prep_share, uint8_t *out_share, uint8_t *ok, size_t n, int device);
+int circl_hip_prio3_prep_finish(int kind, uint64_t max_measurement, int shares, const uint8_t *ctx, size_t ctx_len, const uint8_t *prep_shares, uint8_t *ok,
+                                size_t n, int device);
+int circl_hip_prio3_aggregate(int kind, uint64_t max_measurement, int shares, const uint8_t *ctx, size_t ctx_len, const uint8_t *out_share, const uint8_t *mask,
+                              uint8_t *agg_share, size_t n, int device);
+int circl_hip_prio3_unshard(int kind, uint64_t max_measurement, int shares, const uint8_t *ctx, size_t ctx_len, const uint8_t *agg_shares,
+                            uint64_t num_measurements, uint64_t *result);
+/* the device-resident forms: the same arguments as device pointers (ctx stays a host pointer), on the caller's stream */
+int circl_hip_prio3_shard_dev(int kind, uint64_t max_measurement, int shares, const uint8_t *ctx, size_t ctx_len, const uint64_t *measurement,
+                              const uint8_t *rand, uint8_t *leader_share, uint8_t *ok, size_t n, void *d_workspace, size_t workspace_bytes, void *stream);
+int circl_hip_prio3_prep_init_dev(int kind, uint64_t max_measurement, int shares, const uint8_t *ctx, size_t ctx_len, int agg_id, const uint8_t *verify_key,
+                                  const uint8_t *nonce, const uint8_t *input_share, uint8_t *prep_share, uint8_t *out_share, uint8_t *ok, size_t n,
+                                  void *d_workspace, size_t workspace_bytes, void *stream);
+int circl_hip_prio3_prep_finish_dev(int kind, uint64_t max_measurement, int shares, const uint8_t *ctx, size_t ctx_len, const uint8_t *prep_shares, uint8_t *ok,
+                                    size_t n, void *stream);
+int circl_hip_prio3_aggregate_dev(int kind, uint64_t max_measurement, int shares, const uint8_t *ctx, size_t ctx_len, const uint8_t *out_share,
+                                  const uint8_t *mask, uint8_t *agg_share, size_t n, void *d_workspace, size_t workspace_bytes, void *stream);
+
 /* ---- kernel-level profiling (used by bench.py for the roofline figures) --------------------
  * While enabled, every *_dev call brackets each kernel it enqueues with HIP events recorded on
  * the caller's stream.  circl_hip_profile_read synchronises the pending events, returns the
