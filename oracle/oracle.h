@@ -87,6 +87,11 @@ int orc_mldsa_verify_batch(int param, const uint8_t *pk, const uint8_t *sig, con
                            const uint64_t *msg_off, const uint8_t *ctx_blob, const uint64_t *ctx_off,
                            uint8_t *ok, size_t n, int threads);
 
+/* ---- Prio3 (prio3_search.c): a counter-derived seed or nonce whose XofTurboShake128 stream holds a word >= p ---- */
+int orc_prio3_search(const uint8_t *pre, size_t prelen, const uint8_t *suf, size_t suflen, size_t candlen,
+                     uint64_t start, uint64_t trials, unsigned nwords, int edge, int threads,
+                     uint64_t *counter, unsigned *index, uint64_t *perms);
+
 /* Dilithium ring primitives */
 void orc_dilithium_ntt(uint32_t p[256]);
 void orc_dilithium_invntt(uint32_t p[256]);

@@ -22,7 +22,7 @@ DSA_SIZES = {44: (1312, 2560, 2420), 65: (1952, 4032, 3309), 87: (2592, 4896, 46
 
 
 def build(force=False):
-    srcs = [os.path.join(_HERE, f) for f in ("keccak.c", "kyber.c", "dilithium.c", "batch.c", "x25519.c", "keccak.h", "oracle.h")]
+    srcs = [os.path.join(_HERE, f) for f in ("keccak.c", "kyber.c", "dilithium.c", "batch.c", "x25519.c", "prio3_search.c", "keccak.h", "oracle.h")]
     vsrcs = [os.path.join(_HERE, "vec", f) for f in ("mlkem_vec.c", "dispatch.c")] + [os.path.join(_HERE, "Makefile")]
     if (force or not os.path.exists(_LIB) or any(os.path.getmtime(s) > os.path.getmtime(_LIB) for s in srcs)
             or not os.path.exists(_VLIB) or any(os.path.getmtime(s) > os.path.getmtime(_VLIB) for s in vsrcs)):
@@ -425,3 +425,25 @@ def x25519(scalar, point=None):
     pt = None if point is None else _u8(point).reshape(n, 32)
     lib().orc_x25519_batch(_p(scalar), None if pt is None else _p(pt), _p(out), _p(ok), C.c_size_t(n))
     return out, ok
+
+
+# ---------------- Prio3: seeds that make the rejection sampler refuse (oracle/prio3_search.c) ----------------
+PRIO3_SEARCH_PAD = 0x5c
+
+
+def prio3_candidate(counter, candlen):
+    """the seed or nonce that orc_prio3_search derives from a counter"""
+    return int(counter).to_bytes(8, "little") + bytes([PRIO3_SEARCH_PAD]) * (candlen - 8)
+
+
+def prio3_search(pre, suf, candlen, start, trials, nwords, edge=False, threads=None):
+    """The smallest counter in [start, start + trials) for which TurboSHAKE128(pre || prio3_candidate(counter) || suf, D = 1) has a
+    64-bit word >= 2^64 - 2^32 + 1 among its first nwords (edge: among the words 20, 41, ... that end a block).
+    -> (counter or None, index of that word or None, permutations run)"""
+    pre_a = _u8(bytes(pre) + b"\0"); suf_a = _u8(bytes(suf) + b"\0")
+    counter, index, perms = C.c_uint64(0), C.c_uint(0), C.c_uint64(0)
+    r = lib().orc_prio3_search(_p(pre_a), C.c_size_t(len(pre)), _p(suf_a), C.c_size_t(len(suf)), C.c_size_t(candlen), C.c_uint64(start),
+                               C.c_uint64(trials), C.c_uint(nwords), C.c_int(int(edge)), C.c_int(min(16, threads or ncpu())),
+                               C.byref(counter), C.byref(index), C.byref(perms))
+    assert r in (0, 1), r
+    return (int(counter.value), int(index.value), int(perms.value)) if r else (None, None, int(perms.value))
